@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the cyclic-reduction hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one fused solve + log-det (`mahal_and_det`, reference
 cyclic_reduction.py:380-438) of one synthetic SPD block-tridiagonal system whose
@@ -18,17 +18,25 @@ N > 1 : BASELINE.json configs[3] -- ONE system of 2^24 block rows, d = 4, fp64, 
 compulsory bytes B_A = ((2n-1) d^2 + n d) s + 2s of SURVEY.md 8(d), divided by
 the wall time); solves/s is reported beside it.
 
-Extra objects in the JSON line: `roofline` (dominant kernel against the 8 TB/s
-HBM peak, timed with HIP events on the launch stream) and `cpu_baseline` (the
-oracle = torch-CPU restatement of the reference, timed on the host cores).
+A plain run does only what the headline needs: it builds the system, launches the step untimed for
+`--prewarm-seconds` (at least `--prewarm` launches), runs the W warm-up and K timed steps, checks the
+result against its closed form, writes the outputs of the last timed step (`--dump-outputs DIR`:
+DIR/mahal.npy and DIR/logdet.npy, float64) and prints the line.  `roofline` and `cpu_baseline` are null.
 
-Order of the run: the secondary measurements (`extras`) first, then the headline's W warm-up and K
-timed steps, then the CPU baseline.  A GPU that has been idle for a long time (a fresh box's first
-process) runs its first fraction of a second of kernels in a low power state: measured 77-81 us per
-step for the headline under `--steps 20 --warmup 5` as the first GPU work on a box, 73-74.5 us a few
-seconds after ANY other GPU work (a previous process, unrelated kernels).  With the secondary
-measurements first the headline does not depend on what ran on the box before; `--headline-first`
-restores the other order.
+`--full` adds everything else.  Extra objects in the JSON line: `roofline` (dominant kernel against
+the 8 TB/s HBM peak, timed with HIP events on the launch stream, in a second pass of K steps),
+`cpu_baseline` (the oracle = torch-CPU restatement of the reference, timed on the host cores) and
+`extras` (the cold protocol, other ops, sizes and precisions; with several GPUs the same system on one
+GPU and the weak-scaling point).
+
+Order of a `--full` run: the cold protocol, the secondary measurements (`extras`), then the headline's
+W warm-up and K timed steps, then the CPU baseline.  A GPU that has been idle for a long time (a fresh
+box's first process) runs its first fraction of a second of kernels in a low power state: measured
+77-81 us per step for the headline under `--steps 20 --warmup 5` as the first GPU work on a box,
+73-74.5 us a few seconds after ANY other GPU work (a previous process, unrelated kernels).  With the
+secondary measurements first the headline does not depend on what ran on the box before;
+`--headline-first` restores the other order.  A plain run has no secondary measurements: its
+time-bounded pre-warm plays their part.
 """
 import argparse
 import ctypes
@@ -584,6 +592,14 @@ def parse_args(argv=None):
     ap.add_argument("--prewarm", type=int, default=100,
                     help="one GPU: untimed launches of the headline step before the W warm-up steps (steady state of repeated "
                          "evaluation on the same buffers; 0: none)")
+    ap.add_argument("--prewarm-seconds", type=float, default=2.0,
+                    help="one GPU, plain run: keep launching the headline step untimed for at least this long before the W "
+                         "warm-up steps (the GPU leaves its idle power state; --full runs its secondary measurements instead)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: cold protocol, secondary ops and configs, roofline "
+                         "pass, PMC / kernel-table figures, CPU baseline, single-GPU comparison of a several-GPU run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (DIR/mahal.npy, DIR/logdet.npy, float64)")
     return ap.parse_args(argv)
 
 
@@ -711,7 +727,7 @@ def rank_main(args):
     # `value` below is the warm protocol (after the secondary measurements), as in rounds 1 and 2. -----------
     headline_cold = None
     s_el = 8 if dtype == torch.float64 else 4
-    if not sharded_mode and not args.headline_first:
+    if args.full and not sharded_mode and not args.headline_first:
         e_cold = _timed_steps(step, args.steps, args.warmup, barrier) / args.steps
         headline_cold = {"ms_per_step": e_cold * 1e3, "GBps": algorithmic_bytes(rows, d, s_el) / e_cold / 1e9,
                          "frac_of_8TBps": algorithmic_bytes(rows, d, s_el) / e_cold / 1e9 / HBM_PEAK_GBPS,
@@ -719,7 +735,7 @@ def rank_main(args):
                                  "secondary measurements; `value` is the same protocol after them and after extras.prewarm_steps "
                                  "untimed launches of the same step" % (args.warmup, args.steps)}
     extras_early = None
-    if not sharded_mode and not args.no_extras and not args.headline_first:
+    if args.full and not sharded_mode and not args.no_extras and not args.headline_first:
         extras_early = extra_measurements(dev)          # see the module docstring: order of the run
         torch.cuda.empty_cache()
 
@@ -731,49 +747,65 @@ def rank_main(args):
     # the same buffers (an optimiser loop) lives in that steady state, so the W + K protocol steps are preceded by
     # untimed launches of the same step; the line reports their number (extras.prewarm_steps) and, beside the value,
     # the same protocol as the first GPU work of the process (extras.headline_cold).  --prewarm 0 switches them off.
+    # A plain one-GPU run has no secondary measurements in front of the headline: it keeps launching the same step for
+    # --prewarm-seconds, which brings the GPU out of its idle power state as they did.
     prewarm = int(os.environ.get("CGPS_BENCH_PREWARM_STEPS", "2000" if sharded_mode else str(args.prewarm)))
-    if sharded_mode or prewarm > 0:
+    warm_s = 0.0 if (args.full or sharded_mode) else max(args.prewarm_seconds, 0.0)
+    if sharded_mode or prewarm > 0 or warm_s > 0:
         for _ in range(prewarm):
             step()
         barrier()
+        t_w = time.perf_counter()
+        while time.perf_counter() - t_w < warm_s:
+            for _ in range(100):
+                step()
+            barrier()
+            prewarm += 100
 
     # ---- timed region: W warm-up steps, then exactly K steps ----------------------------------
-    region_ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    region_ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if args.full else None
     elapsed = _timed_steps(step, args.steps, args.warmup, barrier, region_ev)
-    region_avg_s = region_ev[0].elapsed_time(region_ev[1]) / max(args.steps - 1, 1) / 1e3     # launch period inside the timed region (steps 2..K)
+    res = out.cpu()                                 # what the last timed step computed
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- the same K steps again with HIP events bracketing the dominant kernel of each step, on
-    # the stream it is launched on (kept out of the region above: an event record between two
-    # dependent kernels is itself a ~2 us barrier packet and would inflate ms_per_step) ----------
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for a, c in evs:      # force creation of the underlying hipEvent_t
-        a.record(stream)
-        c.record(stream)
-    barrier()
-    t1 = time.perf_counter()
-    for a, c in evs:
-        lib.cgps_profile_next_call(ctypes.c_void_p(a.cuda_event), ctypes.c_void_p(c.cuda_event))
-        step()
-    barrier()
-    elapsed_with_events = time.perf_counter() - t1
-    kernel_ms = sorted(a.elapsed_time(c) for a, c in evs)
-    # ONE estimator for roofline.achieved: HIP events around each launch of the dominant kernel (an upper
-    # bound of its duration: kernel + the two event packets); min <= avg by construction.  The launch period
-    # inside the timed region (events around steps 2..K, divided by K-1) and rocprofv3's own figure from the
-    # committed profile of this command are side fields.
-    kernel_avg_s = sum(kernel_ms) / len(kernel_ms) / 1e3
+    if args.full:
+        region_avg_s = region_ev[0].elapsed_time(region_ev[1]) / max(args.steps - 1, 1) / 1e3     # launch period inside the timed region (steps 2..K)
+        # ---- the same K steps again with HIP events bracketing the dominant kernel of each step, on
+        # the stream it is launched on (kept out of the region above: an event record between two
+        # dependent kernels is itself a ~2 us barrier packet and would inflate ms_per_step) ----------
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for a, c in evs:      # force creation of the underlying hipEvent_t
+            a.record(stream)
+            c.record(stream)
+        barrier()
+        t1 = time.perf_counter()
+        for a, c in evs:
+            lib.cgps_profile_next_call(ctypes.c_void_p(a.cuda_event), ctypes.c_void_p(c.cuda_event))
+            step()
+        barrier()
+        elapsed_with_events = time.perf_counter() - t1
+        kernel_ms = sorted(a.elapsed_time(c) for a, c in evs)
+        # ONE estimator for roofline.achieved: HIP events around each launch of the dominant kernel (an upper
+        # bound of its duration: kernel + the two event packets); min <= avg by construction.  The launch period
+        # inside the timed region (events around steps 2..K, divided by K-1) and rocprofv3's own figure from the
+        # committed profile of this command are side fields.
+        kernel_avg_s = sum(kernel_ms) / len(kernel_ms) / 1e3
 
     # ---- correctness of what was timed (closed form) ---------------------------------------
-    res = out.cpu()
     rel_ld = abs(float(res[1]) - logdet_true) / abs(logdet_true)
     rel_m = abs(float(res[0]) - mahal_true) / abs(mahal_true)
     tol = 1e-5
     assert int(info.item()) == 0, "library reported a non-positive-definite block"
     assert rel_ld < tol and rel_m < tol * 10, ("result mismatch", rel_ld, rel_m)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        # what mahal_and_det returns to its caller: (mahal, logdet), fp64 scalars
+        np.save(os.path.join(args.dump_outputs, "mahal.npy"), np.array(float(res[0]), dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "logdet.npy"), np.array(float(res[1]), dtype=np.float64))
 
     s = s_el
     t_step = elapsed / args.steps
@@ -793,19 +825,20 @@ def rank_main(args):
         use_dist = False
         if rank != 0:
             return
-        k1 = max(3, min(10, args.steps))
-        try:
-            step1, info1, m1, ld1 = whole_system_step(n_total)
-            e1 = _timed_steps(step1, k1, 2, torch.cuda.synchronize) / k1
-            r1 = out.cpu()
-            scaling_extras["single_gpu_same_system"] = {
-                "rows": n_total, "ms_per_step": e1 * 1e3, "GBps": b_total / e1 / 1e9,
-                "logdet_rel_err": abs(float(r1[1]) - ld1) / abs(ld1), "steps": k1}
-            scaling_extras["speedup_vs_single_gpu"] = e1 / t_step
-            del step1
-        except Exception as e:
-            scaling_extras["single_gpu_same_system"] = {"error": repr(e)[:200]}
-        torch.cuda.empty_cache()
+        if args.full:
+            k1 = max(3, min(10, args.steps))
+            try:
+                step1, info1, m1, ld1 = whole_system_step(n_total)
+                e1 = _timed_steps(step1, k1, 2, torch.cuda.synchronize) / k1
+                r1 = out.cpu()
+                scaling_extras["single_gpu_same_system"] = {
+                    "rows": n_total, "ms_per_step": e1 * 1e3, "GBps": b_total / e1 / 1e9,
+                    "logdet_rel_err": abs(float(r1[1]) - ld1) / abs(ld1), "steps": k1}
+                scaling_extras["speedup_vs_single_gpu"] = e1 / t_step
+                del step1
+            except Exception as e:
+                scaling_extras["single_gpu_same_system"] = {"error": repr(e)[:200]}
+            torch.cuda.empty_cache()
     elif sharded_mode:
         scaling_extras = {"sub_shards_per_rank": plan.sub_shards, "records_per_rank": plan.records_per_rank}
 
@@ -827,53 +860,55 @@ def rank_main(args):
                    else "single GPU",
                    "algo": "levelwise" if args.levelwise else "tile-fused"},
         "roofline_frac_whole_op": b_total / t_step / 1e9 / (HBM_PEAK_GBPS * world),
-        "roofline": {"bound": "hbm", "achieved": b_kernel / kernel_avg_s / 1e9, "peak": HBM_PEAK_GBPS,
-                     "unit": "GB/s", "frac": b_kernel / kernel_avg_s / 1e9 / HBM_PEAK_GBPS, "traffic": None,
-                     "kernel": "first-pass reduction kernel (streams Rs, Os, x once)",
-                     "kernel_avg_us": kernel_avg_s * 1e6, "kernel_min_us": kernel_ms[0] * 1e3,
-                     "kernel_max_us": kernel_ms[-1] * 1e3,
-                     "estimator": "HIP events around each launch of the dominant kernel, on its stream, K launches",
-                     "launch_period_us_in_timed_region": region_avg_s * 1e6 if args.steps >= 2 else None,
-                     "algorithmic_bytes_per_launch": b_kernel,
-                     "ms_per_step_with_event_hooks": elapsed_with_events / args.steps * 1e3},
+        "roofline": None,
         "check": {"logdet_rel_err": rel_ld, "mahal_rel_err": rel_m},
     }
     if scaling_extras is not None:
         line["extras"] = scaling_extras
-    # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process;
-    # the number comes from the committed rocprofv3 --pmc passes of this same command
-    # (profiles/<round>_pmc_traffic.json: 2 x FETCH_SIZE + WRITE_SIZE, calibrated as the guide says).
-    # The file names the kernel sources it was measured on; when they have changed since, the figure
-    # is reported as stale instead of being passed off as current.
-    try:
-        rl = line["roofline"]
-        if rows == 1 << 20 and d == 4 and dtype == torch.float64 and not args.levelwise and not sharded_mode:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)))
-            rl["traffic"] = pmc["hbm_bytes_per_launch"]
-            rl["traffic_source"] = "profiles/" + PMC_TRAFFIC_FILE
-            rl["traffic_stale"] = pmc.get("kernel_source_sha16") != kernel_source_sha16()
-            # the same kernel's average duration in the committed rocprofv3 --kernel-trace --stats
-            # summary of this command
-            import csv
-            prof = "profiles/" + KERNEL_STATS_FILE
-            for r in csv.DictReader(open(os.path.join(ROOT, prof))):
-                if "chunk_reduce" in r["Name"] or "stream_reduce" in r["Name"]:
-                    rl["kernel_avg_us_rocprofv3"] = float(r["AverageNs"]) / 1e3
-                    rl["kernel_avg_us_rocprofv3_source"] = prof
-                    break
-        elif sharded_mode and d == 4 and dtype == torch.float64:
-            # per-shard figure: the shard kernels of one rank, measured on one GPU with the sharded code path
-            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_TRAFFIC_SHARD_FILE)))
-            ent = pmc.get("rows_per_rank", {}).get(str(rows))
-            if ent is not None:
-                rl["traffic"] = ent["hbm_bytes_per_step"]
-                rl["traffic_source"] = "profiles/" + PMC_TRAFFIC_SHARD_FILE + " (one rank's shard kernels, measured on one GPU)"
+    if args.full:
+        line["roofline"] = {"bound": "hbm", "achieved": b_kernel / kernel_avg_s / 1e9, "peak": HBM_PEAK_GBPS,
+                            "unit": "GB/s", "frac": b_kernel / kernel_avg_s / 1e9 / HBM_PEAK_GBPS, "traffic": None,
+                            "kernel": "first-pass reduction kernel (streams Rs, Os, x once)",
+                            "kernel_avg_us": kernel_avg_s * 1e6, "kernel_min_us": kernel_ms[0] * 1e3,
+                            "kernel_max_us": kernel_ms[-1] * 1e3,
+                            "estimator": "HIP events around each launch of the dominant kernel, on its stream, K launches",
+                            "launch_period_us_in_timed_region": region_avg_s * 1e6 if args.steps >= 2 else None,
+                            "algorithmic_bytes_per_launch": b_kernel,
+                            "ms_per_step_with_event_hooks": elapsed_with_events / args.steps * 1e3}
+        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process;
+        # the number comes from the committed rocprofv3 --pmc passes of this same command
+        # (profiles/<round>_pmc_traffic.json: 2 x FETCH_SIZE + WRITE_SIZE, calibrated as the guide says).
+        # The file names the kernel sources it was measured on; when they have changed since, the figure
+        # is reported as stale instead of being passed off as current.
+        try:
+            rl = line["roofline"]
+            if rows == 1 << 20 and d == 4 and dtype == torch.float64 and not args.levelwise and not sharded_mode:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_TRAFFIC_FILE)))
+                rl["traffic"] = pmc["hbm_bytes_per_launch"]
+                rl["traffic_source"] = "profiles/" + PMC_TRAFFIC_FILE
                 rl["traffic_stale"] = pmc.get("kernel_source_sha16") != kernel_source_sha16()
-            else:
-                rl["traffic_note"] = "no PMC pass committed for %d rows per rank (see %s)" % (rows, PMC_TRAFFIC_SHARD_FILE)
-    except Exception as e:
-        line["roofline"]["traffic_note"] = "no committed PMC figure: " + repr(e)[:120]
-    if not sharded_mode and not args.no_extras:
+                # the same kernel's average duration in the committed rocprofv3 --kernel-trace --stats
+                # summary of this command
+                import csv
+                prof = "profiles/" + KERNEL_STATS_FILE
+                for r in csv.DictReader(open(os.path.join(ROOT, prof))):
+                    if "chunk_reduce" in r["Name"] or "stream_reduce" in r["Name"]:
+                        rl["kernel_avg_us_rocprofv3"] = float(r["AverageNs"]) / 1e3
+                        rl["kernel_avg_us_rocprofv3_source"] = prof
+                        break
+            elif sharded_mode and d == 4 and dtype == torch.float64:
+                # per-shard figure: the shard kernels of one rank, measured on one GPU with the sharded code path
+                pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_TRAFFIC_SHARD_FILE)))
+                ent = pmc.get("rows_per_rank", {}).get(str(rows))
+                if ent is not None:
+                    rl["traffic"] = ent["hbm_bytes_per_step"]
+                    rl["traffic_source"] = "profiles/" + PMC_TRAFFIC_SHARD_FILE + " (one rank's shard kernels, measured on one GPU)"
+                    rl["traffic_stale"] = pmc.get("kernel_source_sha16") != kernel_source_sha16()
+                else:
+                    rl["traffic_note"] = "no PMC pass committed for %d rows per rank (see %s)" % (rows, PMC_TRAFFIC_SHARD_FILE)
+        except Exception as e:
+            line["roofline"]["traffic_note"] = "no committed PMC figure: " + repr(e)[:120]
+    if args.full and not sharded_mode and not args.no_extras:
         line["extras"] = extras_early if extras_early is not None else extra_measurements(dev)
         line["extras"]["order"] = ("cold W+K steps, secondary measurements, then the headline" if extras_early is not None
                                    else "headline first")
@@ -881,7 +916,7 @@ def rank_main(args):
         line.setdefault("extras", {})["headline_cold"] = headline_cold
     if not sharded_mode:
         line.setdefault("extras", {})["prewarm_steps"] = prewarm
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         if world > 1 or sharded_mode:
             # bounded sample (the full 2^24-row system is ~25 s per run on the host cores): the 2^20-row system of
             # the same generator -- the oracle's time is linear in the rows, its GB/s is what carries over

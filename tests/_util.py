@@ -18,6 +18,17 @@ def golden_cr_cases():
     return sorted(out, key=lambda t: (t[1], t[0]))
 
 
+def load_golden(path):
+    """{name: array} of a golden npz, with the arrays of golden/parts/<same name> if that exists (a fixture that
+    would exceed 1 MiB keeps part of its arrays there; tests/golden/make_golden.py)."""
+    out = dict(np.load(path))
+    part = os.path.join(GOLDEN, "parts", os.path.basename(path))
+    if os.path.exists(part):
+        for k, a in np.load(part).items():
+            out.setdefault(k, a)
+    return out
+
+
 def level_sizes(n):
     ms = []
     while n > 1:

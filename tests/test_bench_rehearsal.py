@@ -17,7 +17,8 @@ def test_plain_command_runs_two_ranks_and_prints_one_complete_line(sub_shards):
     env = dict(os.environ, CGPS_BENCH_REHEARSAL_GLOO="1", CGPS_BENCH_PREWARM_STEPS="10")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", str(1 << 22), "--steps", "5", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", str(1 << 22), "--steps", "5", "--warmup", "2",
+           "--full"]
     if sub_shards:
         cmd += ["--sub-shards", str(sub_shards)]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)

@@ -35,7 +35,7 @@ def _catnp(lst, d):
 def test_against_reference_golden(d, n, path, where):
     """Everything the reference computes for this system, recomputed by the HIP path.
     where="cpu" feeds CPU tensors like the reference's own tests do."""
-    g = np.load(path)
+    g = _util.load_golden(path)
     dev = "cuda" if where == "gpu" else "cpu"
     Rs, Os, v = (torch.from_numpy(g[k]).to(dev) for k in ("Rs", "Os", "v"))
     dec = cr.decompose(Rs, Os)
@@ -70,7 +70,7 @@ def test_against_reference_golden(d, n, path, where):
 
 def test_plain_tuple_factor_is_accepted():
     """A decomp built by someone else (plain tuple of per-level lists, e.g. the oracle's) works too."""
-    g = np.load(CASES[-1][2])
+    g = _util.load_golden(CASES[-1][2])
     Rs, Os, v = (torch.from_numpy(g[k]) for k in ("Rs", "Os", "v"))
     dec = O.decompose(Rs, Os)
     np.testing.assert_allclose(_np(cr.solve(dec, v)), g["solve"], **T64)

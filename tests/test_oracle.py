@@ -27,7 +27,7 @@ def _cat(lst, d):
 
 @pytest.mark.parametrize("d,n,path", CASES, ids=IDS)
 def test_oracle_matches_reference_golden(d, n, path):
-    g = np.load(path)
+    g = _util.load_golden(path)
     Rs, Os, v = (torch.from_numpy(g[k]) for k in ("Rs", "Os", "v"))
     ms, Ds, Fs, Gs = dec = O.decompose(Rs, Os)
     assert ms.dtype == torch.int64 and ms.tolist() == g["ms"].tolist() == _util.level_sizes(n)
@@ -57,7 +57,7 @@ def test_oracle_matches_reference_golden(d, n, path):
 def test_oracle_matches_dense_algebra(d, n, path):
     """The reference's own dense oracle: L = chol(T J T^T) with T the recursive
     even/odd permutation; halfsolve == L^-1 T v, backhalfsolve == (L^T T)^-1 v."""
-    g = np.load(path)
+    g = _util.load_golden(path)
     Rs, Os, v = g["Rs"], g["Os"], g["v"]
     J = O.dense_from_blocks(Rs, Os)
     perm = O.crr_order(n)

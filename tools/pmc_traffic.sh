@@ -7,6 +7,6 @@ OUT=$1; mkdir -p ${GRAFT_REPO_ROOT:-/root/repo}/$OUT
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace -d $R/$OUT/$c -o p --output-format csv -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $R/$OUT/$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace -d $R/$OUT/$c -o p --output-format csv -- python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras > $R/$OUT/$c.log 2>&1
 done
 echo traffic passes done

@@ -50,7 +50,7 @@ def kernel_source_sha16():
 doc = {
     "round": rnd,
     "command": "bash tools/pmc_traffic.sh OUT  (= rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python3 "
-               "bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras ; same with --pmc WRITE_SIZE: separate passes); "
+               "bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras ; same with --pmc WRITE_SIZE: separate passes); "
                "python tools/pmc_traffic_json.py OUT %d" % rnd,
     "workload": "N=2^20 d=4 fp64 mahal_and_det, ONE launch (stage 1 + record stages inside the launch)",
     "kernel": kernel.split("(")[0].replace("void ", ""),

@@ -29,7 +29,7 @@ def per_step(d, counter):
 
 doc = {"round": rnd,
        "command": "CGPS_BENCH_FORCE_SHARDED=1 CGPS_BENCH_PREWARM_STEPS=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv "
-                  "-- python3 bench.py --rows <rows per rank> --steps 10 --warmup 2 --no-cpu-baseline ; the same with --pmc "
+                  "-- python3 bench.py --rows <rows per rank> --steps 10 --warmup 2 --full --no-cpu-baseline ; the same with --pmc "
                   "WRITE_SIZE (separate passes); python tools/pmc_traffic_shards_json.py OUT %d" % rnd,
        "what": "one rank's kernels of a sharded step (shard reduction with the record stages inside + finish kernel), d = 4 fp64",
        "rows_per_rank": {}}
