@@ -136,10 +136,15 @@ __device__ __forceinline__ bool gap_terms(T dt, const T (&G)[D][D], bool want_ri
   return ok;
 }
 
+// cut (nullptr: one series): cut[g] != 0 marks the gap between rows g and g+1 as the boundary between two
+// independent series (cgps_peg_precision_seg).  Such a gap is never evaluated -- it may be zero or negative --
+// its coupling block is 0 and it adds nothing to either diagonal block; with cut == nullptr the arithmetic is
+// the one-series kernel's, unchanged.
 template <typename T, int D>
 __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __restrict__ ts, const T* __restrict__ Gg,
                                                                     int64_t N, T* __restrict__ Rs, T* __restrict__ Os,
-                                                                    int* __restrict__ info) {
+                                                                    int* __restrict__ info,
+                                                                    const unsigned char* __restrict__ cut = nullptr) {
   constexpr int DD = D * D;
   const int64_t i = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
   if (i >= N) return;
@@ -154,7 +159,14 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
 #pragma unroll
     for (int b = 0; b < D; ++b) R[a][b] = (a == b) ? T(1) : T(0);
   bool ok = true;
-  if (i + 1 < N) {                                 // the gap after this row
+  if (i + 1 < N && cut != nullptr && cut[i]) {    // the gap after this row ends a series: no coupling
+    T z[D][D];
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = 0; b < D; ++b) z[a][b] = T(0);
+    store_block<T, D>(Os + i * DD, z);
+  } else if (i + 1 < N) {                          // the gap after this row
     T c1[D][D], c2[D][D], bb[D][D];
     ok = gap_terms<T, D>(ts[i + 1] - ts[i], G, false, true, c1, c2, bb) && ok;
 #pragma unroll
@@ -163,7 +175,7 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
       for (int b = 0; b < D; ++b) { R[a][b] += c2[a][b]; bb[a][b] = -bb[a][b]; }
     store_block<T, D>(Os + i * DD, bb);
   }
-  if (i >= 1) {                                    // the gap before it
+  if (i >= 1 && !(cut != nullptr && cut[i - 1])) { // the gap before it (unless it starts a series)
     T c1[D][D], c2[D][D], bb[D][D];
     ok = gap_terms<T, D>(ts[i] - ts[i - 1], G, true, false, c1, c2, bb) && ok;
 #pragma unroll
@@ -380,7 +392,8 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __r
 //   Gbar += -1/2 tau Abar ;        taubar = -1/2 <Abar, G>
 // Gbar is summed over the lanes of a workgroup in a fixed order and written per workgroup
 // (gG_partial[block][d][d]: the caller adds the few partial sums -- deterministic, no atomics);
-// gtau[i] = d loss / d (t_{i+1} - t_i).
+// gtau[i] = d loss / d (t_{i+1} - t_i).  With a cut mask (see peg_precision_kernel) a gap between two series
+// gets gtau = 0 and adds nothing to Gbar.
 
 // (E, L) <- (exp(A), L_exp(A, dA)); A and dA are destroyed
 template <typename T, int D>
@@ -436,7 +449,7 @@ __device__ __forceinline__ void mat_exp_frechet(T (&E)[D][D], T (&L)[D][D], T (&
 template <typename T, int D>
 __global__ __launch_bounds__(LEG_THREADS) void peg_precision_adjoint_kernel(
     const T* __restrict__ ts, const T* __restrict__ Gg, int64_t N, const T* __restrict__ gRs, const T* __restrict__ gOs,
-    T* __restrict__ gG_partial, T* __restrict__ gtau) {
+    T* __restrict__ gG_partial, T* __restrict__ gtau, const unsigned char* __restrict__ cut = nullptr) {
   constexpr int DD = D * D;
   __shared__ T red[DD];
   const int64_t i = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;      // the gap between rows i and i + 1
@@ -445,7 +458,9 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_adjoint_kernel(
   for (int a = 0; a < D; ++a)
 #pragma unroll
     for (int b = 0; b < D; ++b) Gbar[a][b] = T(0);
-  if (i + 1 < N) {
+  if (i + 1 < N && cut != nullptr && cut[i]) {   // a gap between two series: evaluated nowhere, contributes nothing
+    if (gtau != nullptr) gtau[i] = T(0);
+  } else if (i + 1 < N) {
     T G[D][D];
 #pragma unroll
     for (int a = 0; a < D; ++a)

@@ -39,6 +39,37 @@ int cgps_peg_precision_adjoint(const void* ts, const void* G, int64_t N, int d, 
   });
 }
 
+int cgps_peg_precision_seg(const void* ts, const void* G, const unsigned char* cut, int64_t N, int d, int dtype, void* Rs,
+                           void* Os, int* info, void* stream) {
+  if (bad_common(N, d) || !ts || !G || (N > 1 && (!Os || !cut)) || !Rs || !info)
+    return fail(CGPS_ERR_ARG, "cgps_peg_precision_seg: null pointer or N < 1");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    hipStream_t st = (hipStream_t)stream;
+    (void)hipMemsetAsync(info, 0, sizeof(int), st);
+    const int64_t nb = (N + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+    hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEG_THREADS), 0, st,
+                       (const T*)ts, (const T*)G, N, (T*)Rs, (T*)Os, info, cut);
+    return check_launch("peg_precision_seg");
+  });
+}
+
+int cgps_peg_precision_adjoint_seg(const void* ts, const void* G, const unsigned char* cut, int64_t N, int d, int dtype,
+                                   const void* gRs, const void* gOs, void* gG_partial, void* gtau, void* stream) {
+  if (bad_common(N, d) || N < 2 || !ts || !G || !cut || !gRs || !gOs || !gG_partial)
+    return fail(CGPS_ERR_ARG, "cgps_peg_precision_adjoint_seg: null pointer or N < 2");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int64_t nb = (N - 1 + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+    hipLaunchKernelGGL((cgps::peg_precision_adjoint_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEG_THREADS), 0,
+                       (hipStream_t)stream, (const T*)ts, (const T*)G, N, (const T*)gRs, (const T*)gOs, (T*)gG_partial,
+                       (T*)gtau, cut);
+    return check_launch("peg_precision_adjoint_seg");
+  });
+}
+
 int cgps_leg_intercast(const void* ts, int64_t n, const void* target_ts, int64_t p, const void* G, int d, int dtype,
                        const void* ip_mean, const void* ip_cov_diag, const void* ip_cov_offdiag, void* out_mean,
                        void* out_cov, void* stream) {

@@ -4,6 +4,7 @@
 #include "cgps_host.h"
 #include "cgps_tile.h"
 #include "cgps_boundary.h"
+#include "cgps_tile_leg_batch.h"
 
 using namespace cgps_host;
 
@@ -106,6 +107,21 @@ int cgps_leg_mahal_logdet_pair(const void* ts, const void* G, const void* A, con
     if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair (twice cgps_mahal_logdet's, each rounded up to 256 bytes)");
     if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_mahal_logdet_pair: not built for this block size (d = 8, fp64 d = 6) or CGPS_NO_FOLD=1");
     return check_launch("LEG tile reduction (pair)");
+  });
+}
+
+int cgps_leg_loglik_batch(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* A, const void* v,
+                          const void* q, int d, int dtype, int64_t max_rows, double* out4, int* info2, void* stream) {
+  if (B < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !out4 || !info2)))
+    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch: null pointer or B < 0");
+  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch: B = %lld series, at most 2^31 - 1", (long long)B);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int rc = cgps::run_leg_batch<T, D>((const T*)ts, offsets, B, (const T*)G, (const T*)A, (const T*)v, (const T*)q,
+                                             max_rows, out4, info2, (hipStream_t)stream);
+    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch: not built for this block size (d = 8, fp64 d = 6)");
+    return check_launch("LEG batched reduction");
   });
 }
 

@@ -1,0 +1,150 @@
+// Batched LEG log-likelihood reductions: many independent series in ONE launch (cgps_leg_loglik_batch).
+// Included from cgps_mahal.hip after cgps_tile.h (the chunk walk, the in-LDS reduction and the in-register
+// assembly of cgps_tile_leg.h are reused as they are).
+//
+// Series b is rows [offsets[b], offsets[b+1]) of the concatenated ts / v / q.  Its two systems
+//     K_b = PEG precision(ts_b, G) + blockdiag(A)        (posterior precision, right-hand side v_b)
+//     S_b = PEG precision(ts_b, G)                        (prior precision, no right-hand side)
+// do not couple to any other series, so each is reduced by ONE workgroup on its own: no records leave the
+// workgroup, no arrival counters, no inter-workgroup hand-off.  Grid (B, 2): blockIdx.x = series,
+// blockIdx.y = 0 for K_b, 1 for S_b (the gridDim.y = 2 layout of cgps_leg_mahal_logdet_pair).
+//   streaming: NT lanes, C = ceil(n_b / NT) rows each; a lane assembles its rows in registers from ts and G
+//              (leg_row / leg_gap) and eliminates them left to right (eliminate_forward), exactly as
+//              chunk_reduce_kernel<.., SRC = 1> does for one long series;
+//   in LDS:    the lanes' kept rows are reduced by tile_cr (NW = 256 threads, the extra waves are role waves);
+//   last row:  thread 0 factors the one row left and adds its pivots;
+//   results:   per-thread partial sums are added in a fixed order (block_sum2), so the values do not depend on
+//              anything but the series itself.  The K workgroup also sums q over the series' rows.
+// out4[b] = {v^T K^-1 v, log|K|, log|S|, sum of q}; info2[2b] / info2[2b+1]: 0 or 1 + a local row near a block of
+// K_b / S_b that was not positive definite (a zero-length gap included); a failed system's entries are NaN.
+// A series with more than max_rows rows is skipped (nothing written: the caller reduces it with another call).
+#pragma once
+
+namespace cgps {
+
+constexpr int LEG_BATCH_THREADS = 256;
+
+template <typename T, int D>
+constexpr int leg_batch_lanes() { return TileCfg<T, D>::NG1; }       // 256, or 128 for 7 x 7 fp64 (LDS)
+
+template <typename T, int D, int NT, int NW>
+__global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ ts, const int64_t* __restrict__ offsets,
+                                                          const T* __restrict__ Gg, const T* __restrict__ Ag,
+                                                          const T* __restrict__ vg, const T* __restrict__ qg,
+                                                          int64_t max_rows, double* __restrict__ out4,
+                                                          int* __restrict__ info2) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  StageSmem<T, D, NT, NW> sm(smem);
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const bool prior = blockIdx.y == 1;
+  const int64_t off = offsets[b];
+  const int64_t n = offsets[b + 1] - off;
+  if (n < 1 || n > max_rows) return;                           // workgroup-uniform
+  const T* __restrict__ tsb = ts + off;
+  const T* __restrict__ vb = (prior || vg == nullptr) ? nullptr : vg + off * D;
+  const T* __restrict__ Ab = prior ? nullptr : Ag;
+  if (tid == 0) *sm.sfail = 0x7fffffff;
+
+  const int64_t C = (n + NT - 1) / NT;                         // rows per lane
+  int64_t r0 = (int64_t)tid * C, rE = r0 + C;
+  if (tid >= NT) r0 = n;                                       // threads past the lanes hold no rows
+  if (rE > n) rE = n;
+  const int L = r0 < n ? (int)(rE - r0) : 0;
+  PivotLog pl;
+  double mah = 0.0;
+  bool fail = false;
+  T Rc[D][D], yc[D], Cc[D][D], dRa[D][D], dya[D], cR[D][D], cB[D][D];
+  set_zero<T, D>(dRa);
+  set_zero<T, D>(dya);
+  set_zero<T, D>(Rc);
+  set_zero<T, D>(yc);
+  set_zero<T, D>(Cc);
+  if (r0 < n) {
+    if (r0 >= 1) {
+      T tl[D][D];
+      if (!leg_gap<T, D>(tsb, Gg, r0 - 1, cR, tl, cB)) fail = true;
+    } else {
+      set_zero<T, D>(cR);
+      set_zero<T, D>(cB);
+    }
+    leg_row<T, D>(tsb, Gg, Ab, vb, r0, n, cR, cB, Rc, Cc, yc, fail);
+  }
+#pragma unroll 1
+  for (int j = 0; j < L - 1; ++j) {
+    T Rn[D][D], On[D][D], yn[D];
+    leg_row<T, D>(tsb, Gg, Ab, vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
+    eliminate_forward<T, D>(Rc, yc, Cc, dRa, dya, On, Rn, yn, pl, mah, fail);
+  }
+  const bool fail_stream = fail;
+  const int n_real = (int)((n + C - 1) / C);                   // lanes that hold rows (<= NT)
+  // row 0 of the series has no left neighbour: lane 0's Cc is zero, so its updates for "the row left of the
+  // tile" are zero as well and the tile's boundary row is the series' last row
+  reduce_tile_and_emit<T, D, NW>(sm.t, Rc, yc, Cc, dRa, dya, n_real, sm.xch, (T*)nullptr, pl, mah, fail);
+  if (tid == 0) {                                              // the one row left: the series' last
+    T A[D][D], x[D];
+    Chol<T, D> c;
+    LdsTile<T, D>::load_blk(sm.t.R, n_real - 1, A);
+    pl.mul(chol_lower<T, D>(A, c, fail));
+    load_vec<T, D>(sm.t.y + (n_real - 1) * D, x);
+    fwd_subst<T, D>(c, x);
+#pragma unroll
+    for (int i = 0; i < D; ++i) mah += (double)x[i] * (double)x[i];
+  }
+  const int fcode = fail_code(fail_stream, fail, r0 < n ? r0 : n - 1);
+  if (fcode) atomicMin(sm.sfail, fcode);
+  double logp = pl.value();
+  block_sum2<NW>(mah, logp, sm.red);                           // contains a barrier (NW > 64)
+  double qs = 0.0, unused = 0.0;
+  if (!prior && qg != nullptr) {
+    for (int64_t i = tid; i < n; i += NW) qs += (double)qg[off + i];
+  }
+  __syncthreads();                                             // sm.red is reused
+  block_sum2<NW>(qs, unused, sm.red);
+  if (tid == 0) {
+    const int f = *sm.sfail;
+    const bool ok = f == 0x7fffffff;
+    const double poison = __builtin_nan("");
+    double* o = out4 + 4 * b;
+    if (prior) {
+      o[2] = ok ? logp : poison;
+    } else {
+      o[0] = ok ? mah : poison;
+      o[1] = ok ? logp : poison;
+      o[3] = qs;
+    }
+    info2[2 * b + (prior ? 1 : 0)] = ok ? 0 : (f & ~FAIL_LATE);
+  }
+}
+
+template <typename T, int D>
+constexpr bool leg_batch_supported() { return leg_source_supported<T, D>(); }
+
+template <typename T, int D>
+size_t leg_batch_lds_bytes() { return stage_lds_bytes<T, D>(leg_batch_lanes<T, D>(), LEG_BATCH_THREADS); }
+
+// -2: not built for this (d, dtype)
+template <typename T, int D>
+int run_leg_batch(const T* ts, const int64_t* offsets, int64_t B, const T* G, const T* A, const T* v, const T* q,
+                  int64_t max_rows, double* out4, int* info2, hipStream_t st) {
+  if constexpr (!leg_batch_supported<T, D>()) {
+    return -2;
+  } else {
+    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
+    const size_t lds = leg_batch_lds_bytes<T, D>();
+    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
+    std::call_once(once[dev], [lds] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    if (B == 0) return 0;
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets, G, A, v, q,
+                       max_rows, out4, info2);
+    return 0;
+  }
+}
+
+}  // namespace cgps

@@ -223,6 +223,239 @@ def leg_loglik_reductions(ts, G, A, v):
     return out[0], out[1], out[3]
 
 
+# ---- many independent series at once ----------------------------------------------------------
+BATCH_MAX_ROWS = 4096
+"""Series longer than this are reduced by ``cgps_leg_mahal_logdet_pair`` (several workgroups per series) instead
+of the one workgroup per series of ``cgps_leg_loglik_batch``; their values go into their slots all the same."""
+
+
+def _batch_layout(ts, xs, lengths):
+    """(ts [R], xs [R, obs], lengths as a list of ints) of either input layout; raises ValueError before
+    anything is launched when the lengths do not describe the rows."""
+    if lengths is None:
+        if ts.dim() != 2 or xs.dim() != 3 or tuple(xs.shape[:2]) != tuple(ts.shape):
+            raise ValueError("dense layout wants ts[B, n] and xs[B, n, obs_dim], got %s and %s"
+                             % (tuple(ts.shape), tuple(xs.shape)))
+        B, n = ts.shape
+        if B > 0 and n < 1:
+            raise ValueError("series of length 0")
+        return ts.reshape(B * n), xs.reshape(B * n, xs.shape[-1]), [int(n)] * B
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda or lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("lengths must be host data: a list or a 1-d CPU integer tensor")
+        lengths = lengths.tolist()
+    lengths = [int(n) for n in lengths]
+    if ts.dim() != 1 or xs.dim() != 2:
+        raise ValueError("ragged layout wants ts[sum(lengths)] and xs[sum(lengths), obs_dim], got %s and %s"
+                         % (tuple(ts.shape), tuple(xs.shape)))
+    bad = [b for b, n in enumerate(lengths) if n < 1]
+    if bad:
+        raise ValueError("series %d has length %d (every series needs at least one row)" % (bad[0], lengths[bad[0]]))
+    total = sum(lengths)
+    if total != ts.shape[0] or total != xs.shape[0]:
+        raise ValueError("lengths sum to %d rows, ts has %d and xs %d" % (total, ts.shape[0], xs.shape[0]))
+    return ts, xs, lengths
+
+
+def batch_supported(ts, G):
+    """The batched kernel (cgps_leg_loglik_batch) exists for this case: GPU tensors and the block sizes of
+    ``fused_supported`` (d <= 7, not fp64 d = 6), with or without a gradient."""
+    d = G.shape[0]
+    return (G.is_cuda and ts.is_cuda and G.dtype in (torch.float32, torch.float64) and 1 <= d <= 7 and
+            not (d == 6 and G.dtype == torch.float64))
+
+
+class _BatchPlan:
+    """What the lengths fix on the host: device offsets, per-row lengths for repeat_interleave, the series-cut mask
+    of the concatenated assembly, and the series handed to the one-series kernel."""
+
+    def __init__(self, lengths, device):
+        self.lengths = lengths
+        self.B, self.R = len(lengths), sum(lengths)
+        off = [0]
+        for n in lengths:
+            off.append(off[-1] + n)
+        self.starts = off
+        self.offsets = torch.tensor(off, dtype=torch.int64).to(device, non_blocking=True)
+        self.lens = torch.tensor(lengths, dtype=torch.int64).to(device, non_blocking=True)
+        cut = torch.zeros(max(self.R - 1, 0), dtype=torch.uint8)
+        if self.B > 1:
+            cut[torch.tensor(off[1:-1]) - 1] = 1
+        self.cut = cut.to(device, non_blocking=True)
+        self.long = [b for b, n in enumerate(lengths) if n > BATCH_MAX_ROWS]
+
+    def per_row(self, g):
+        return g.repeat_interleave(self.lens, output_size=self.R)
+
+
+def _leg_pair_raw(ts, G, A, v):
+    """cgps_leg_mahal_logdet_pair of one series: (out4 fp64, info2), nothing read on the host."""
+    from . import _hip
+    n, d, dt = ts.shape[0], G.shape[0], G.dtype
+    nbytes = 2 * ((_hip._workspace_bytes(int(n), int(d), _hip.dtype_code(dt), _hip.OP_MAHAL_LOGDET) + 255) // 256 * 256)
+    key = (G.device, torch.cuda.current_stream().cuda_stream)
+    ws = _pair_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _pair_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
+    out = torch.empty(4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A), _hip.ptr(v), n, d, _hip.dtype_code(dt),
+                                                     _hip.ptr(ws), ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    return out, info
+
+
+def leg_loglik_batch_reductions(ts, G, A, v, q, plan):
+    """The per-series reductions of a batch, no autograd graph: [B, 4] fp64 rows (v^T K^-1 v, log|K|, log|Sigma^-1|,
+    sum q) and [B, 2] info words (cgps_leg_loglik_batch; series longer than BATCH_MAX_ROWS through
+    cgps_leg_mahal_logdet_pair on the same stream).  ts, A, v, q in G's dtype, contiguous."""
+    from . import _hip
+    d, dt = G.shape[0], G.dtype
+    out = torch.empty(plan.B, 4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(plan.B, 2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_loglik_batch(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, _hip.ptr(G), _hip.ptr(A),
+                                                _hip.ptr(v), _hip.ptr(q), d, _hip.dtype_code(dt), BATCH_MAX_ROWS,
+                                                _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    for b in plan.long:
+        s, e = plan.starts[b], plan.starts[b + 1]
+        o4, i2 = _leg_pair_raw(ts[s:e], G, A, v[s:e])
+        out[b, :3] = o4[[0, 1, 3]]
+        out[b, 3] = q[s:e].to(torch.float64).sum()
+        info[b] = i2
+    return out, info
+
+
+def _raise_batch_not_pd(info):
+    bad = info.cpu()
+    rows = torch.nonzero(bad.amax(1)).flatten().tolist()
+    if rows:
+        b = rows[0]
+        code = int(bad[b, 0]) or int(bad[b, 1])
+        raise cr.NotPSDError("LEG batch: series %d: a block near its row %d is not positive definite "
+                             "(or a time gap has zero length)" % (b, code - 1))
+
+
+def _peg_precision_seg(ts, G, cut):
+    """Blocks of the block-diagonal PEG precision of concatenated series (cgps_peg_precision_seg).  No autograd graph."""
+    from . import _hip
+    n, d = ts.shape[0], G.shape[0]
+    Rs = torch.empty(n, d, d, dtype=G.dtype, device=G.device)
+    Os = torch.empty(max(n - 1, 0), d, d, dtype=G.dtype, device=G.device)
+    info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_peg_precision_seg(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), n, d, _hip.dtype_code(G.dtype),
+                                                 _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
+    return Rs, Os
+
+
+def _peg_precision_adjoint_seg(ts, G, cut, gRs, gOs, want_ts):
+    """(d loss / d G, d loss / d ts or None) through cgps_peg_precision_adjoint_seg."""
+    from . import _hip
+    n, d = ts.shape[0], G.shape[0]
+    if n < 2:
+        return torch.zeros_like(G), (torch.zeros_like(ts) if want_ts else None)
+    part = torch.empty((n - 1 + 63) // 64, d, d, dtype=G.dtype, device=G.device)
+    gtau = torch.empty(n - 1, dtype=G.dtype, device=G.device) if want_ts else None
+    _hip.check(_hip.lib().cgps_peg_precision_adjoint_seg(
+        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), n, d, _hip.dtype_code(G.dtype), _hip.ptr(gRs.contiguous()),
+        _hip.ptr(gOs.contiguous()), _hip.ptr(part), _hip.ptr(gtau), _hip.stream_ptr()))
+    gts = None
+    if want_ts:
+        z = gtau.new_zeros(1)
+        gts = torch.cat([z, gtau]) - torch.cat([gtau, z])
+    return part.sum(0), gts
+
+
+class _LegBatchFn(torch.autograd.Function):
+    """Forward: the batched reductions (one launch).  Backward: the concatenated system of all series, which is
+    block-diagonal (zero coupling between series): series-aware assembly, decompose_solve + inverse_blocks of K and
+    of Sigma^-1, block gradients weighted per row by the series' upstream gradients, series-aware adjoint."""
+
+    @staticmethod
+    def forward(ctx, ts, G, A, v, q, plan):
+        ctx.plan = plan
+        ctx.save_for_backward(ts, G, A, v)
+        out, info = leg_loglik_batch_reductions(ts.detach(), G.detach(), A.detach(), v.detach(), q.detach(), plan)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            _raise_batch_not_pd(info)
+        return out.to(G.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        ts, G, A, v = ctx.saved_tensors
+        plan = ctx.plan
+        need_ts, need_G, need_A, need_v, need_q = ctx.needs_input_grad[:5]
+        gts = gG = gA = gv = gq = None
+        gout = gout.to(G.dtype)
+        if need_q:
+            gq = plan.per_row(gout[:, 3])
+        if need_ts or need_G or need_A or need_v:
+            Rs, Os = _peg_precision_seg(ts, G, plan.cut)
+            gm, gl = plan.per_row(gout[:, 0]), plan.per_row(gout[:, 1])
+            dec, w = cr.decompose_solve(Rs + A, Os, v)
+            if need_v:
+                gv = 2 * gm.unsqueeze(-1) * w
+            if need_ts or need_G or need_A:
+                Sd, So = cr.inverse_blocks(dec)
+                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
+                if need_A:
+                    gA = gR.sum(0)
+                if need_ts or need_G:
+                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
+                    if plan.R > 1:           # (one row: its block is I whatever G and ts are)
+                        gs = plan.per_row(gout[:, 2])
+                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
+                        gR = gR + gs.view(-1, 1, 1) * Sd0
+                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
+                    gG, gts = _peg_precision_adjoint_seg(ts, G, plan.cut, gR, gO, need_ts)
+                    if not need_G:
+                        gG = None
+        return gts, gG, gA, gv, gq, None
+
+
+def _log_likelihood_per_series(m, ts, xs, lengths):
+    """One ``log_likelihood`` per series: d = 8, fp64 d = 6 and CPU tensors (no batched kernel there)."""
+    outs, s = [], 0
+    for b, n in enumerate(lengths):
+        try:
+            outs.append(log_likelihood(m, ts[s:s + n], xs[s:s + n]))
+        except cr.NotPSDError as e:
+            raise cr.NotPSDError("LEG batch: series %d: %s" % (b, e)) from None
+        s += n
+    return torch.stack(outs)
+
+
+def log_likelihood_batch(m, ts, xs, lengths=None):
+    """log p(xs_b | ts_b) of the LEG model for B independent series (models.py:301-372 for each), as a [B] tensor of
+    the model's dtype; ``out.sum()`` is what a training step over the batch minimises.
+
+    ``lengths=None``: the dense layout of the reference's dataset, ts[B, n] and xs[B, n, obs_dim].  Otherwise the
+    ragged layout: ts[sum(lengths)], xs[sum(lengths), obs_dim], series b being rows offsets[b]:offsets[b+1];
+    ``lengths`` is host data (a list or a CPU integer tensor, every length >= 1).  The time stamps of different
+    series are independent.  Differentiable in N, R, B, Lambda (through ``m``), xs and ts, for any upstream
+    gradient and any subset of trainable parameters.  On the GPU one launch for every series up to
+    BATCH_MAX_ROWS rows (cgps_leg_loglik_batch) and a backward through the concatenated, decoupled system;
+    d = 8, fp64 d = 6 and CPU tensors take one ``log_likelihood`` per series.  With
+    ``cr.CHECK_POSITIVE_DEFINITE`` a series that is not positive definite raises ``NotPSDError`` naming it; without
+    it its slot is NaN and no other slot is affected."""
+    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    G = m.G
+    dt = G.dtype
+    if not lengths:
+        return torch.empty(0, dtype=dt, device=ts.device)
+    if not batch_supported(ts, G):
+        return _log_likelihood_per_series(m, ts, xs, lengths)
+    plan = _BatchPlan(lengths, G.device)
+    LLT = m.LLT
+    Li = m.inv_of(LLT)
+    xl = xs @ Li
+    v = (xl @ m.B).to(dt).contiguous()
+    q = (xl * xs).sum(-1).to(dt).contiguous()
+    A = (m.B.T @ Li @ m.B).to(dt).contiguous()
+    red = _LegBatchFn.apply(ts.to(dt).contiguous(), G.contiguous(), A, v, q, plan)
+    llt_det = torch.log(2 * math.pi * LLT[0, 0]) if LLT.shape[0] == 1 else torch.logdet(2 * math.pi * LLT)
+    n = plan.lens.to(dt)
+    return -0.5 * ((red[:, 3] - red[:, 0]) + (n * llt_det + red[:, 1] - red[:, 2]))
+
+
 def posterior_precision(m, ts):
     Rs, Os = peg_precision(ts, m.G)
     BtLB = m.B.T @ m.LLT_inv @ m.B

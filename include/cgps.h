@@ -180,6 +180,36 @@ int cgps_leg_mahal_logdet_pair(const void* ts, const void* G, const void* A, con
 int cgps_peg_precision_adjoint(const void* ts, const void* G, int64_t N, int d, int dtype,
                                const void* gRs, const void* gOs, void* gG_partial, void* gtau, void* stream);
 
+/* Many independent LEG series in ONE launch (the batch dimension of the reference's time_series_dataset,
+ * data_utils.py:61-75, which LEGFamily.training_step squeezes away, models.py:374-381).  Series b is rows
+ * offsets[b] .. offsets[b+1]-1 of the concatenated ts[sum n_b], v[sum n_b][d] (NULL: zeros) and q[sum n_b]
+ * (NULL: zeros); offsets[B+1] is int64 DEVICE memory.  Per series, in fp64:
+ *   out4[b][0..1] = {v_b^T K_b^-1 v_b, log|K_b|},  K_b = PEG precision(ts_b, G) + blockdiag(A)    (info2[2b])
+ *   out4[b][2]    = log|PEG precision(ts_b, G)|                                                  (info2[2b+1])
+ *   out4[b][3]    = sum of q over the series' rows (summed in a fixed order)
+ * i.e. the two reductions of models.py:349-367 and the observation term for each series alone.  info: 0 or
+ * 1 + a row of the series (local index) near a block that is not positive definite (a zero-length gap
+ * included); that system's entries are NaN, every other series is unaffected.  The time stamps of different
+ * series are independent (they may overlap or decrease from one series to the next).  One workgroup per
+ * series and system; a series of more than max_rows rows is skipped (nothing written).  No workspace.
+ * CGPS_ERR_UNSUPPORTED for d = 8 and fp64 d = 6, as cgps_leg_mahal_logdet. */
+int cgps_leg_loglik_batch(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* A,
+                          const void* v, const void* q, int d, int dtype, int64_t max_rows, double* out4,
+                          int* info2, void* stream);
+
+/* cgps_peg_precision of several series concatenated (models.py:181-239 for each): cut[N-1] (device bytes),
+ * cut[g] != 0 when rows g and g+1 belong to different series.  Such a gap is never evaluated, its coupling
+ * block Os[g] is 0 and it adds nothing to Rs[g] or Rs[g+1]: the blocks of a block-diagonal system of
+ * independent series.  Otherwise as cgps_peg_precision (which this leaves unchanged). */
+int cgps_peg_precision_seg(const void* ts, const void* G, const unsigned char* cut, int64_t N, int d, int dtype,
+                           void* Rs, void* Os, int* info, void* stream);
+
+/* Adjoint of cgps_peg_precision_seg: as cgps_peg_precision_adjoint; a gap between two series contributes
+ * nothing to gG_partial and gets gtau = 0. */
+int cgps_peg_precision_adjoint_seg(const void* ts, const void* G, const unsigned char* cut, int64_t N, int d,
+                                   int dtype, const void* gRs, const void* gOs, void* gG_partial, void* gtau,
+                                   void* stream);
+
 /* Prediction glue of LEG models, the step AFTER the path (reference models.py:455-514 intercast with
  * forecast :394-408, interpolate :410-452 and gaussian_stitch model_utils.py:64-107, which the reference
  * runs as a Python loop over the targets): posterior mean and covariance of the latent at p target
