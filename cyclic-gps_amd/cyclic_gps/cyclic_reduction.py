@@ -135,7 +135,7 @@ def _packed(decomp):
 # factorisation
 # ----------------------------------------------------------------------------
 def decompose_step(Rs, Os):
-    """One reduction level -> (n, D, F, G), (Rs', Os')   (reference :203-259)."""
+    """One reduction level -> (n, D, F, G), (Rs', Os')   (reference :203-259).  No autograd graph."""
     _check_blocks(Rs, Os)
     n, d = Rs.shape[0], Rs.shape[1]
     if n < 2:
@@ -162,7 +162,8 @@ def decompose(Rs, Os):
 
     The factor tensors themselves are plain (non-differentiable) device buffers; when Rs / Os
     require grad the returned decomp remembers them, and det(decomp) / solve(decomp, y) /
-    mahal(decomp, y) differentiate with respect to them analytically (see _DetFn, _SolveFn)."""
+    mahal(decomp, y) differentiate with respect to them analytically (see _DetFn, _SolveFn).
+    halfsolve, backhalfsolve and inverse_blocks of the factor build no autograd graph."""
     dec = _decompose_raw(Rs.detach(), Os.detach())
     if _needs_grad(Rs, Os):
         dec.inputs = (Rs, Os)
@@ -194,9 +195,13 @@ def decompose_solve(Rs, Os, y):
     (reference models.py:288-292: decompose, then solve), with the forward substitution of y riding along in the
     first pass of the factorisation -- the forward sweep never reads 7/8 of the factor (cgps_decompose_solve).
     An addition to the reference's surface (its callers that factor and solve together can switch to it);
-    y: [N, d].  No autograd graph: with a gradient wanted, call decompose and solve."""
+    y: [N, d].  When Rs, Os or y require grad (and grad mode is on) it returns (decompose(Rs, Os), solve(decomp, y)),
+    so x is differentiable in all three; otherwise one fused call that builds no autograd graph."""
     _check_blocks(Rs, Os)
     N, d = Rs.shape[0], Rs.shape[1]
+    if _needs_grad(Rs, Os, y):
+        dec = decompose(Rs, Os)
+        return dec, solve(dec, y.reshape(N, d)).reshape(y.shape)
     R, O = _stage(Rs.detach()), _stage(Os.detach())
     dev, dt = R.device, R.dtype
     v = _stage(y.detach()).to(dt).reshape(N, d).contiguous()
@@ -240,7 +245,8 @@ def _pair(a, b):
     """sum over the right-hand-side columns of a_c b_c^T per block row: [N, d] or [N, d, ...] -> [N, d, d]"""
     if a.dim() == 2:
         return _outer(a, b)
-    return a.reshape(a.shape[0], a.shape[1], -1) @ b.reshape(b.shape[0], b.shape[1], -1).transpose(-1, -2)
+    m = a.shape[2:].numel()              # explicit: a -1 is ambiguous for zero rows (the off-diagonal terms at N = 1)
+    return a.reshape(a.shape[0], a.shape[1], m) @ b.reshape(b.shape[0], b.shape[1], m).transpose(-1, -2)
 
 
 class _MahalLogdetFn(torch.autograd.Function):
@@ -338,7 +344,8 @@ def _rhs(y, N, d, dt):
 
 
 def halfsolve(decomp, y):
-    """L^-1 (T y) as the per-level list ("CRR layout")   (reference :312-338).  y: [N, d] or [N, d, m]."""
+    """L^-1 (T y) as the per-level list ("CRR layout")   (reference :312-338).  y: [N, d] or [N, d, m].
+    No autograd graph (neither in y nor in the factor's Rs / Os)."""
     xs, _ = _halfsolve(decomp, y, want_mahal=False)
     return xs
 
@@ -360,7 +367,7 @@ def _halfsolve(decomp, y, want_mahal):
 
 
 def backhalfsolve(decomp, ycrr):
-    """T^T L^-T applied to a per-level list -> natural order   (reference :341-377)."""
+    """T^T L^-T applied to a per-level list -> natural order   (reference :341-377).  No autograd graph."""
     Dp, Fp, Gp, N, d, like = _packed(decomp)
     dev, dt = Dp.device, Dp.dtype
     src = ycrr[0]
@@ -425,13 +432,20 @@ def _det_raw(decomp):
 
 
 def mahal(decomp, y):
-    """y^T J^-1 y = ||L^-1 T y||^2   (reference :461-467)."""
+    """y^T J^-1 y = ||L^-1 T y||^2   (reference :461-467); y: [N, d] or [N, d, m] (summed over the columns).
+    Differentiable in y and in the Rs / Os the factor came from: with a gradient wanted it is
+    sum(y * solve(decomp, y)), accumulated in fp64, through _SolveFn; otherwise one halfsolve that reduces the norm."""
+    Rs, Os = _decomp_inputs(decomp)
+    if _needs_grad(Rs, Os, y):
+        dt = _packed(decomp)[0].dtype
+        w = solve(decomp, y)
+        return (y.to(torch.float64) * w.to(torch.float64)).sum().to(dt)
     _, m = _halfsolve(decomp, y, want_mahal=True)
     return _back(m.to(_packed(decomp)[0].dtype), y)[0]
 
 
 def inverse_blocks(decomp):
-    """Diagonal and lower off-diagonal blocks of J^-1   (reference :470-503)."""
+    """Diagonal and lower off-diagonal blocks of J^-1   (reference :470-503).  No autograd graph."""
     Dp, Fp, Gp, N, d, like = _packed(decomp)
     dev, dt = Dp.device, Dp.dtype
     Sd = torch.empty((N, d, d), dtype=dt, device=dev)

@@ -163,7 +163,8 @@ def peg_precision(ts, G):
 
 def fused_supported(ts, G):
     """The assembly-in-registers form (cgps_leg_mahal_logdet) exists for this case: GPU tensors, no gradient wanted, a
-    block size whose first pass runs one lane per row."""
+    block size whose first pass runs one lane per row.  Looks at ts and G only: ``log_likelihood`` also keeps the fused
+    kernels off when B, Lambda or xs need a gradient."""
     d = G.shape[0]
     return (G.is_cuda and ts.is_cuda and G.dtype in (torch.float32, torch.float64) and 1 <= d <= 7 and
             not (d == 6 and G.dtype == torch.float64) and
@@ -467,28 +468,34 @@ def compute_v(m, xs):
 
 
 def log_likelihood(m, ts, xs):
-    """log p(xs | ts) of the LEG model (models.py:301-372)."""
+    """log p(xs | ts) of the LEG model (models.py:301-372).  Differentiable in N, R, B, Lambda (through ``m``), xs and
+    ts, for any subset of trainable parameters.  The fused reductions (no autograd graph) are taken only when none of
+    ts, G, B^T (LL^T)^-1 B and v needs a gradient; otherwise the blocks go through ``peg_precision`` and
+    ``cr.mahal_and_det``."""
     LLT = m.LLT
     Li = m.inv_of(LLT)
     xl = xs @ Li
     v = (xl @ m.B).contiguous()
+    A = m.B.T @ Li @ m.B
     G = m.G
     n = xs.shape[0]
-    if fused_supported(ts, G) and LLT.shape[0] == 1:
+    # fused_supported looks at ts and G only; B, Lambda and xs reach the reductions through A and v
+    fused = fused_supported(ts, G) and not (torch.is_grad_enabled() and (A.requires_grad or v.requires_grad))
+    if fused and LLT.shape[0] == 1:
         # the two reductions (prior precision: log-det only; posterior precision: mahal + log-det) never see their blocks
         # in memory, and run side by side in one launch: they share nothing but ts and G.  The scalar terms around them
         # are one product, one log and one weighted sum (N ~ 500 is launch-bound: every small launch is ~2.5 us)
-        k_mahal, k_det, sig_inv_det = leg_loglik_reductions(ts, G, m.B.T @ Li @ m.B, v)
+        k_mahal, k_det, sig_inv_det = leg_loglik_reductions(ts, G, A, v)
         terms = torch.stack([torch.dot(xl.reshape(-1), xs.reshape(-1)), torch.log(LLT[0, 0]), k_mahal, k_det, sig_inv_det])
         return torch.dot(terms, _ll_weights(n, terms.dtype, terms.device)) - 0.5 * n * math.log(2 * math.pi)
     llt_mahal = (xl * xs).sum()
     llt_det = (torch.log(2 * math.pi * LLT[0, 0]) if LLT.shape[0] == 1 else torch.logdet(2 * math.pi * LLT)) * n
-    if fused_supported(ts, G):
-        k_mahal, k_det, sig_inv_det = leg_loglik_reductions(ts, G, m.B.T @ Li @ m.B, v)
+    if fused:
+        k_mahal, k_det, sig_inv_det = leg_loglik_reductions(ts, G, A, v)
         return -0.5 * ((llt_mahal - k_mahal) + (llt_det + k_det - sig_inv_det))
     Rs, Os = peg_precision(ts, G)
     _, sig_inv_det = cr.mahal_and_det(Rs, Os, torch.zeros_like(v))       # = det(decompose(Rs, Os)), fused
-    K_Rs = Rs + (m.B.T @ Li @ m.B).unsqueeze(0)
+    K_Rs = Rs + A.unsqueeze(0)
     k_mahal, k_det = cr.mahal_and_det(Rs=K_Rs, Os=Os, x=v)
     return -0.5 * ((llt_mahal - k_mahal) + (llt_det + k_det - sig_inv_det))
 
@@ -576,7 +583,8 @@ class GraphedValueAndGrad:
 
 
 def insample_posterior(m, ts, xs):
-    """Posterior mean [N,d] and (diag, lower off-diag) covariance blocks (models.py:282-298)."""
+    """Posterior mean [N,d] and (diag, lower off-diag) covariance blocks (models.py:282-298).  The mean is
+    differentiable; the covariance blocks (``cr.inverse_blocks``) carry no autograd graph."""
     K_Rs, K_Os = posterior_precision(m, ts)
     v = compute_v(m, xs)
     if K_Rs.is_cuda and not (torch.is_grad_enabled() and (K_Rs.requires_grad or K_Os.requires_grad or v.requires_grad)):
