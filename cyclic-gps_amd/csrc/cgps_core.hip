@@ -2,7 +2,6 @@
 // One translation unit of libcgps (include/cgps.h); host code only decides sizes/offsets and
 // enqueues kernels on the caller's stream: nothing here allocates, copies to the host or synchronises.
 #include "cgps_host.h"
-#include "cgps_tile_sizes.h"
 
 using namespace cgps_host;
 
@@ -42,47 +41,16 @@ int cgps_workspace_bytes(int64_t N, int d, int dtype, int op, size_t* bytes) {
   if (d > 8) return fail(CGPS_ERR_UNSUPPORTED, "block size d=%d outside 1..8", d);
   if (dtype != CGPS_F32 && dtype != CGPS_F64) return fail(CGPS_ERR_UNSUPPORTED, "dtype %d not supported", dtype);
   const size_t s = dtype == CGPS_F32 ? 4 : 8;
-  const int64_t capA = N / 2 + 1;
   switch (op) {
-    case CGPS_OP_MAHAL_LOGDET_LEVELWISE:
-      *bytes = level_ws(N, d, s, true, true).total;
-      return CGPS_OK;
-    case CGPS_OP_MAHAL_LOGDET: {
-      size_t a = level_ws(N, d, s, true, true).total;
-      size_t b = cgps::tile_ws_bytes(N, d, s);
-      *bytes = a > b ? a : b;
-      return CGPS_OK;
-    }
-    case CGPS_OP_DECOMPOSE:
-      *bytes = level_ws(N, d, s, true, false).total;
-      return CGPS_OK;
-    case CGPS_OP_HALFSOLVE:
-      *bytes = level_ws(N, d, s, false, true).total;
-      return CGPS_OK;
-    case CGPS_OP_BACKSOLVE:
-    case CGPS_OP_SOLVE: {
-      LevelWs w = level_ws(N, d, s, false, true);
-      size_t back = w.partial_bytes + 2 * align_up((size_t)d * s * capA);
-      size_t crr = (op == CGPS_OP_SOLVE) ? align_up((size_t)N * d * s) : 0;
-      size_t m = w.total > back ? w.total : back;
-      *bytes = crr + m;
-      return CGPS_OK;
-    }
-    case CGPS_OP_DECOMPOSE_SOLVE: {
-      size_t a = 0, b = 0, c = 0;
-      (void)cgps_workspace_bytes(N, d, dtype, CGPS_OP_DECOMPOSE, &a);
-      (void)cgps_workspace_bytes(N, d, dtype, CGPS_OP_HALFSOLVE, &b);
-      (void)cgps_workspace_bytes(N, d, dtype, CGPS_OP_BACKSOLVE, &c);
-      const size_t m = a > b ? (a > c ? a : c) : (b > c ? b : c);
-      *bytes = align_up(m) + decompose_solve_tail_bytes(N, d, s);
-      return CGPS_OK;
-    }
-    case CGPS_OP_LOGDET_FACTOR:
-      *bytes = align_up((size_t)(1024 + 2) * 16);
-      return CGPS_OK;
-    case CGPS_OP_INVERSE_BLOCKS:
-      *bytes = 2 * align_up((size_t)2 * d * d * s * capA);
-      return CGPS_OK;
+    case CGPS_OP_MAHAL_LOGDET_LEVELWISE: *bytes = level_ws(N, d, s, true, true).total; return CGPS_OK;
+    case CGPS_OP_MAHAL_LOGDET: *bytes = mahal_logdet_ws_bytes(N, d, s); return CGPS_OK;
+    case CGPS_OP_DECOMPOSE: *bytes = decompose_ws(N, d, s).total; return CGPS_OK;
+    case CGPS_OP_HALFSOLVE: *bytes = halfsolve_ws(N, d, s).total; return CGPS_OK;
+    case CGPS_OP_BACKSOLVE: *bytes = sweeps_ws_bytes(N, d, s); return CGPS_OK;
+    case CGPS_OP_SOLVE: *bytes = solve_ws(N, d, s).total; return CGPS_OK;
+    case CGPS_OP_DECOMPOSE_SOLVE: *bytes = decompose_solve_ws(N, d, s).total; return CGPS_OK;
+    case CGPS_OP_LOGDET_FACTOR: *bytes = logdet_factor_ws().total; return CGPS_OK;
+    case CGPS_OP_INVERSE_BLOCKS: *bytes = inverse_ws(N, d, s).total; return CGPS_OK;
     default:
       return fail(CGPS_ERR_ARG, "cgps_workspace_bytes: unknown op %d", op);
   }
@@ -120,14 +88,15 @@ int cgps_decompose_step(const void* Rs, const void* Os, int64_t n, int d, int dt
 int cgps_logdet_factor(const void* Dp, int64_t N, int d, int dtype, void* ws, size_t ws_bytes, double* out,
                        void* stream) {
   if (bad_common(N, d) || !Dp || !ws || !out) return fail(CGPS_ERR_ARG, "cgps_logdet_factor: null pointer or N < 1");
-  if (ws_bytes < (size_t)(1024 + 2) * 16) return fail(CGPS_ERR_ARG, "workspace too small");
+  const LogdetFactorWs w = logdet_factor_ws();
+  if (ws_bytes < w.total) return fail(CGPS_ERR_ARG, "workspace too small: %zu < %zu", ws_bytes, w.total);
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
     hipStream_t st = (hipStream_t)stream;
-    double* partial = (double*)ws;
+    double* partial = at<double>((char*)ws, w.partial);
     int64_t nb = (N * D + 255) / 256;
-    if (nb > 1024) nb = 1024;
+    if (nb > cgps::LOGDET_MAX_BLOCKS) nb = cgps::LOGDET_MAX_BLOCKS;
     hipLaunchKernelGGL((cgps::logdiag_kernel<T, D>), dim3((unsigned)nb), dim3(256), 0, st, (const T*)Dp, N, partial);
     double* tmp = partial + 2 * nb;
     hipLaunchKernelGGL(cgps::sum_partials_kernel, dim3(1), dim3(256), 0, st, partial, nb, tmp);

@@ -24,22 +24,12 @@ namespace cgps {
 #ifndef CGPS_DECOMP_QUAD
 #define CGPS_DECOMP_QUAD 1     // 4 x 4 / 8 x 8 blocks: four lanes per elimination (0: role split, for A/B builds)
 #endif
-constexpr int DECL_LP = 8;
-constexpr int DECL_TS = 1 << DECL_LP;     // 256 rows per tile
-constexpr int DECL_NT = 256;             // four waves
-constexpr int DECL_MAXLEV = DECL_LP + 1;
-
-struct DecompLevelsL {
-  int64_t offD[DECL_MAXLEV], offF[DECL_MAXLEV], offG[DECL_MAXLEV];
-  int nlev;
-};
+constexpr int DECL_NT = 256;             // four waves (tile shape and DecompLevelsL: cgps_plan.h)
 
 // Blocks whose 256-row tile does not fit the LDS (fp64 d = 6, 7, 8) take tiles of 2^6 rows, six levels per launch,
-// for EVERY pass of their factorisation (cgps_decompose.hip: run_decompose_lds_only) -- 2^20 rows in four launches
+// for EVERY pass of their factorisation (plan_decompose in cgps_plan.h) -- 2^20 rows in four launches
 // instead of one per level; two to four such tiles share a CU.
-template <typename T, int D> constexpr int decomp_lds_lp() {
-  return (((size_t)DECL_TS * 2 * D * D + D * D) * sizeof(T) + 4096 <= 160 * 1024) ? DECL_LP : 6;
-}
+template <typename T, int D> constexpr int decomp_lds_lp() { return decomp_lds_lp(D, sizeof(T)); }
 template <typename T, int D, int LP = DECL_LP>
 constexpr size_t decomp_lds_tile_bytes() {
   return (((size_t)(1 << LP) * 2 * D * D + D * D) * sizeof(T) + 15 & ~(size_t)15) + 256;

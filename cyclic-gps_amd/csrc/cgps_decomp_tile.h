@@ -32,17 +32,7 @@
 
 namespace cgps {
 
-constexpr int DEC_LP = 3;               // levels per pass over many tiles
-constexpr int DEC_TS = 128;             // rows per tile: two per lane
-constexpr int DEC_TS_LOG2 = 7;          // levels per pass over few tiles (one survivor per tile)
-constexpr int DEC_NT = 64;              // one wave
-constexpr int DEC_MAXLEV = 8;           // the last pass takes a system of <= DEC_TS rows to the end: log2(128) + 1
-constexpr int64_t DEC_FEW_TILES = 512;  // below this a pass is latency-bound: run all levels of a tile
-
-struct DecompLevels {
-  int64_t offD[DEC_MAXLEV], offF[DEC_MAXLEV], offG[DEC_MAXLEV];
-  int nlev;
-};
+constexpr int DEC_NT = 64;              // one wave (tile shape and DecompLevels: cgps_plan.h)
 
 // a block / the lower triangle of a symmetric block as held by lane `src` (every lane of the wave
 // executes this; lanes whose src is out of range get something they must not use)

@@ -1,6 +1,6 @@
 // Host-side plumbing shared by the translation units of libcgps (one .hip file per group of
 // entry points, so that the library builds in parallel): error string, dtype / block-size
-// dispatch, level layout, workspace carve-up, per-device one-time setup.
+// dispatch, per-device one-time setup.  Sizes, offsets and pass lists: cgps_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 
 #include "../../include/cgps.h"
 #include "cgps_level.h"
+#include "cgps_plan.h"
 
 namespace cgps_host {
 
@@ -75,72 +76,19 @@ inline int device_cus(int dev) {
   return cus > 0 ? cus : 256;
 }
 
-// ---- level layout of the packed factor ----------------------------------------------------------
-struct Layout {
-  int nlevels;
-  int64_t ms[CGPS_MAX_LEVELS], offD[CGPS_MAX_LEVELS + 1], offF[CGPS_MAX_LEVELS + 1], offG[CGPS_MAX_LEVELS + 1];
-};
-
-inline void make_layout(int64_t N, Layout& L) {
-  int l = 0;
-  int64_t m = N, oD = 0, oF = 0, oG = 0;
-  for (;;) {
-    L.ms[l] = m;
-    L.offD[l] = oD; L.offF[l] = oF; L.offG[l] = oG;
-    oD += (m + 1) / 2; oF += m / 2; oG += (m - 1) / 2;
-    ++l;
-    if (m == 1) break;
-    m /= 2;
-  }
-  L.nlevels = l;
-  L.offD[l] = oD; L.offF[l] = oF; L.offG[l] = oG;
-}
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int64_t level_blocks(int64_t m) { return ((m + 1) / 2 + cgps::LEVEL_THREADS - 1) / cgps::LEVEL_THREADS; }
-
-// workspace carve-up shared by the level-wise paths
-struct LevelWs {
-  size_t partial_off, partial_bytes;  // [total blocks][2] doubles
-  size_t a_off, b_off;                // ping-pong level buffers
-  int64_t capA, capB;                 // rows
-  size_t total;
-};
-
-inline LevelWs level_ws(int64_t N, int d, size_t s, bool with_mats, bool with_vec, int nrhs = 1) {
-  LevelWs w{};
-  Layout L;
-  make_layout(N, L);
-  int64_t nb = 0;
-  for (int l = 0; l < L.nlevels; ++l) nb += level_blocks(L.ms[l]);
-  w.partial_off = 0;
-  w.partial_bytes = align_up((size_t)(nb + 1) * 16);
-  w.capA = N / 2 + 1;
-  w.capB = N / 4 + 1;
-  size_t per_row = (with_mats ? 2 * (size_t)d * d : 0) + (with_vec ? (size_t)d * nrhs : 0);
-  w.a_off = w.partial_bytes;
-  w.b_off = w.a_off + align_up(per_row * s * w.capA);
-  w.total = w.b_off + align_up(per_row * s * w.capB);
-  return w;
-}
-
+// ---- workspace regions -> pointers (the layout itself: cgps_plan.h) ----------------------------------------------
 template <typename T>
 struct LevelBuf {
   T *R, *O, *y;
 };
+// ping-pong buffer i of a level-wise workspace: R [cap][d][d], O [cap][d][d], then y
 template <typename T>
-LevelBuf<T> carve(char* base, int64_t cap, int d, bool with_mats, bool with_vec) {
+LevelBuf<T> carve(char* ws, const LevelWs& w, int i, int d, bool with_mats, bool with_vec) {
   LevelBuf<T> b{nullptr, nullptr, nullptr};
-  T* p = reinterpret_cast<T*>(base);
-  if (with_mats) { b.R = p; p += cap * d * d; b.O = p; p += cap * d * d; }
+  T* p = at<T>(ws, w.buf[i]);
+  if (with_mats) { b.R = p; p += w.cap[i] * d * d; b.O = p; p += w.cap[i] * d * d; }
   if (with_vec) b.y = p;
   return b;
-}
-
-// cgps_decompose_solve keeps the right-hand side of the rows that survive its first pass, and what each tile owes the
-// previous one, behind the workspace of the ops it runs one after the other
-inline size_t decompose_solve_tail_bytes(int64_t N, int d, size_t s) {
-  return align_up((size_t)(N / 8 + 16) * d * s) + align_up((size_t)(N / 128 + 2) * d * s);
 }
 
 inline bool bad_common(int64_t N, int d) { return N < 1 || d < 1; }
@@ -162,8 +110,8 @@ int run_levelwise(const T* Rs, const T* Os, const T* x, int64_t N, T* Dp, T* Fp,
   if (ws_bytes < w.total) return fail(CGPS_ERR_ARG, "workspace too small: %zu < %zu", ws_bytes, w.total);
   Layout L;
   make_layout(N, L);
-  double* partial = reinterpret_cast<double*>(ws + w.partial_off);
-  LevelBuf<T> bufs[2] = {carve<T>(ws + w.a_off, w.capA, D, true, rhs), carve<T>(ws + w.b_off, w.capB, D, true, rhs)};
+  double* partial = at<double>(ws, w.partial);
+  LevelBuf<T> bufs[2] = {carve<T>(ws, w, 0, D, true, rhs), carve<T>(ws, w, 1, D, true, rhs)};
   (void)hipMemsetAsync(info, 0, sizeof(int), st);
   const T *R = Rs, *O = Os, *y = x;
   int64_t pb = 0;

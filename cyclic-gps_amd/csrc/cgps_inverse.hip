@@ -24,21 +24,11 @@ inline bool inverse_lds_enabled() {         // CGPS_NO_LDS_INVERSE=1: large bloc
   static const bool on = [] { const char* e = getenv("CGPS_NO_LDS_INVERSE"); return !(e && e[0] == '1'); }();
   return on;
 }
-constexpr int64_t INV_FUSED_MIN_ROWS = 1024;   // a fused inverse pass must produce at least this many rows
 template <typename T, int D>
 int run_inverse(const T* Dp, const T* Fp, const T* Gp, int64_t N, T* Sd, T* So, char* ws, size_t ws_bytes,
                 hipStream_t st) {
-  const int64_t cap = N / 2 + 1;
-  const size_t one = align_up((size_t)2 * D * D * sizeof(T) * cap);
-  if (ws_bytes < 2 * one) return fail(CGPS_ERR_ARG, "workspace too small: %zu < %zu", ws_bytes, 2 * one);
-  Layout L;
-  make_layout(N, L);
-  T* bufs[2] = {reinterpret_cast<T*>(ws), reinterpret_cast<T*>(ws + one)};
-  const T *Sdc = nullptr, *Soc = nullptr;
-  // The coarse levels one launch each (latency-bound, little data); once a level that is a
-  // multiple of INV_LP above level 0 is reached and the rows get many, INV_LP levels per launch
-  // (cgps_inverse_tile.h): those passes read 1/8 of what they write instead of ping-ponging every
-  // level's Sigma through HBM.
+  const size_t need = inverse_ws(N, D, sizeof(T)).total;
+  if (ws_bytes < need) return fail(CGPS_ERR_ARG, "workspace too small: %zu < %zu", ws_bytes, need);
   // blocks up to CGPS_INV_FUSED_MAX_BLOCK bytes keep the tile's Sigma in registers, larger ones in LDS
   // 8 x 8 blocks: four lanes per row (cgps_inverse_quad.h); fp64 d = 8 one lane per row spills in either form
   const bool IN_QUAD = D == 8 && inverse_quad_enabled();
@@ -66,21 +56,25 @@ int run_inverse(const T* Dp, const T* Fp, const T* Gp, int64_t N, T* Sd, T* So, 
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, tile_kernel, tile_threads, lds);
     return device_cus(dev) * (nb > 0 ? nb : 1);
   });
-  int p = 0;
-  int l_start = L.nlevels - 1;
-  if constexpr (cgps::inverse_deep_supported<T, D>()) {
-    // the coarse end in ONE launch (inverse_deep_kernel): from the single row of the coarsest level down
-    // to the finest level of at most INVD_TS rows at which the three-levels-per-launch passes can take
-    // over (a multiple of INV_LP), or to level 0 of a small system
-    if (inverse_deep_enabled()) {
-      constexpr int INVD_TS_ = 1 << cgps::invd_tsl<T, D>();
-      int lf = -1;
-      for (int l = 0; l < L.nlevels; ++l)
-        if (L.ms[l] <= INVD_TS_ && (l % cgps::INV_LP == 0 || !FUSED)) { lf = l; break; }
-      if (lf < 0)
-        for (int l = 0; l < L.nlevels; ++l)
-          if (L.ms[l] <= INVD_TS_) { lf = l; break; }
-      if (lf >= 0 && L.nlevels - lf <= cgps::INVD_MAXLEV) {
+  // the passes, coarse to fine (plan_inverse in cgps_plan.h): the coarse end in ONE launch where the block size has
+  // that kernel, INV_LP levels per launch once the rows get many, one launch per level in between
+  bool deep = false;
+  if constexpr (cgps::inverse_deep_supported<T, D>()) deep = inverse_deep_enabled();
+  InvPlan P;
+  plan_inverse(N, D, sizeof(T), FUSED, IN_QUAD || !IN_LDS || inverse_lds_enabled(), deep, P);
+  Layout L;
+  make_layout(N, L);
+  T* bufs[2] = {at<T>(ws, P.ws.buf[0]), at<T>(ws, P.ws.buf[1])};
+  const int64_t so_off = P.ws.cap * D * D;               // a buffer's off-diagonal blocks come after cap diagonal ones
+  const T *Sdc = nullptr, *Soc = nullptr;
+  for (int p = 0; p < P.np; ++p) {
+    const InvPass& q = P.pass[p];
+    T* od = q.out < 0 ? Sd : bufs[q.out];
+    T* oo = q.out < 0 ? So : bufs[q.out] + so_off;
+    const int l = q.first;
+    if (q.kind == InvKind::Deep) {
+      if constexpr (cgps::inverse_deep_supported<T, D>()) {
+        constexpr int INVD_TS_ = 1 << cgps::invd_tsl<T, D>();
         static PerDevice<int> attr;
         attr.get([](int) {
           (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cgps::inverse_deep_kernel<T, D>),
@@ -88,46 +82,23 @@ int run_inverse(const T* Dp, const T* Fp, const T* Gp, int64_t N, T* Sd, T* So, 
           return 1;
         });
         cgps::InverseDeepLevels dl;
-        dl.nlev = L.nlevels - lf;
-        for (int j = 0; j < cgps::INVD_MAXLEV; ++j) {
-          const int l = lf + j < L.nlevels ? lf + j : L.nlevels - 1;
-          dl.offD[j] = L.offD[l]; dl.offF[j] = L.offF[l]; dl.offG[j] = L.offG[l];
-        }
-        T* od = (lf == 0) ? Sd : bufs[p];
-        T* oo = (lf == 0) ? So : bufs[p] + cap * D * D;
+        dl.nlev = q.nlev;
+        fill_window(L, l, dl);
         const size_t lds_deep = cgps::inverse_deep_lds_bytes<T, D>();
         hipLaunchKernelGGL((cgps::inverse_deep_kernel<T, D>), dim3(1), dim3(INVD_TS_ / 2), lds_deep, st, Dp, Fp, Gp, dl,
-                           (int)L.ms[lf], od, oo);
-        Sdc = od; Soc = oo; p ^= 1;
-        l_start = lf - 1;
+                           (int)q.rows, od, oo);
       }
-    }
-  }
-  for (int l = l_start; l >= 0;) {
-    const int have = l + 1;                               // Sdc / Soc hold Sigma of this level
-    if (FUSED && (IN_QUAD || !IN_LDS || inverse_lds_enabled()) && Sdc != nullptr && have % cgps::INV_LP == 0 && L.ms[have] >= 1 &&
-        L.ms[have - cgps::INV_LP] >= INV_FUSED_MIN_ROWS) {
-      const int lf = have - cgps::INV_LP;
-      const int64_t n = L.ms[lf], tiles = (n + cgps::INV_TS - 1) / cgps::INV_TS;
+    } else if (q.kind == InvKind::Tile) {
+      const int64_t tiles = (q.rows + cgps::INV_TS - 1) / cgps::INV_TS;
       cgps::InverseLevels lv;
-      for (int t = 0; t < cgps::INV_LP; ++t) {
-        lv.offD[t] = L.offD[lf + t]; lv.offF[t] = L.offF[lf + t]; lv.offG[t] = L.offG[lf + t];
-      }
-      T* od = (lf == 0) ? Sd : bufs[p];
-      T* oo = (lf == 0) ? So : bufs[p] + cap * D * D;
+      fill_window(L, l, lv);
       const int64_t grid = tiles < grid_cap ? tiles : grid_cap;
-      hipLaunchKernelGGL(tile_kernel, dim3((unsigned)grid), dim3(tile_threads), lds, st, Dp, Fp, Gp, lv, Sdc, Soc, n, od, oo);
-      Sdc = od; Soc = oo; p ^= 1;
-      l = lf - 1;
-      continue;
+      hipLaunchKernelGGL(tile_kernel, dim3((unsigned)grid), dim3(tile_threads), lds, st, Dp, Fp, Gp, lv, Sdc, Soc, q.rows, od, oo);
+    } else {
+      hipLaunchKernelGGL((cgps::inverse_level_kernel<T, D>), dim3((unsigned)level_blocks(q.rows)), dim3(cgps::LEVEL_THREADS), 0, st,
+                         Dp + L.offD[l] * D * D, Fp + L.offF[l] * D * D, Gp + L.offG[l] * D * D, Sdc, Soc, q.rows, od, oo);
     }
-    const int64_t n = L.ms[l], nb = level_blocks(n);
-    T* od = (l == 0) ? Sd : bufs[p];
-    T* oo = (l == 0) ? So : bufs[p] + cap * D * D;
-    hipLaunchKernelGGL((cgps::inverse_level_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEVEL_THREADS), 0, st,
-                       Dp + L.offD[l] * D * D, Fp + L.offF[l] * D * D, Gp + L.offG[l] * D * D, Sdc, Soc, n, od, oo);
-    Sdc = od; Soc = oo; p ^= 1;
-    --l;
+    Sdc = od; Soc = oo;
   }
   return check_launch("inverse_blocks");
 }

@@ -22,19 +22,13 @@
 
 namespace cgps {
 
-constexpr int INV_LP = 3;
-constexpr int INV_TS = 128;
-constexpr int INV_NT = 64;
+constexpr int INV_NT = 64;              // (tile shape and the level windows: cgps_plan.h)
 // fp64 d = 4 needs ~335 registers: one wave per SIMD.  Forcing two (256 registers) spills 83 of
 // them to scratch and the big pass goes from 138 to 255 us; at one wave the chain of a tile
 // (input load -> three dependent levels -> stores) is what bounds the pass.
 #ifndef INV_MIN_WAVES
 #define INV_MIN_WAVES 1
 #endif
-
-struct InverseLevels {
-  int64_t offD[INV_LP], offF[INV_LP], offG[INV_LP];   // packed-array offsets of levels L, L+1, L+2
-};
 
 template <typename T, int D>
 __device__ __forceinline__ void set_identity(T (&A)[D][D]) {
@@ -645,14 +639,9 @@ __global__ __launch_bounds__(INV_NT, 1) void inverse_tile_lds_kernel(const T* __
 // new couplings (inverse_even_row): disjoint slots per elimination, one barrier per level.
 // Blocks <= 256 bytes (the tile is 512 rows x 2 blocks of <= 128 bytes, or 256 rows x 2 larger blocks), one workgroup.
 // rows of the finest level this kernel takes: 512 for blocks <= 128 bytes, 256 up to 256 bytes
-template <typename T, int D> constexpr int invd_tsl() { return (size_t)D * D * sizeof(T) <= 128 ? 9 : 8; }
-constexpr int INVD_MAXLEV = 10;
-struct InverseDeepLevels {
-  int64_t offD[INVD_MAXLEV], offF[INVD_MAXLEV], offG[INVD_MAXLEV];   // packed-array offsets of the kernel's levels, finest first
-  int nlev;
-};
+template <typename T, int D> constexpr int invd_tsl() { return invd_tsl(D, sizeof(T)); }
 // (larger blocks spill in this kernel -- 376 B per lane at fp64 d = 5 -- and gain nothing: they stay one launch per coarse level)
-template <typename T, int D> constexpr bool inverse_deep_supported() { return (size_t)D * D * sizeof(T) <= 128; }
+template <typename T, int D> constexpr bool inverse_deep_supported() { return deep_block(D, sizeof(T)); }
 template <typename T, int D> constexpr size_t inverse_deep_lds_bytes() { return ((size_t)2 << invd_tsl<T, D>()) * D * D * sizeof(T); }
 
 // n: rows of the finest level (<= INVD_TS); output in natural order: Sd_out[n], So_out[n - 1]

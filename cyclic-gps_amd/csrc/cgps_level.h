@@ -9,10 +9,9 @@
 // cross-lane traffic).
 #pragma once
 #include "cgps_math.h"
+#include "cgps_plan.h"
 
 namespace cgps {
-
-constexpr int LEVEL_THREADS = 128;
 
 // One cyclic-reduction level (reference decompose_step, cyclic_reduction.py:203-259,
 // fused with the per-level pieces of mahal_and_det :412-427 when RHS).

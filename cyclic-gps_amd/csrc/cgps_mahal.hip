@@ -33,7 +33,7 @@ int cgps_mahal_logdet(const void* Rs, const void* Os, const void* x, int64_t N, 
 int cgps_record_elems(int d, int dtype, int64_t* elems) {
   if (!elems || d < 1) return fail(CGPS_ERR_ARG, "cgps_record_elems: bad argument");
   if (d > 8 || (dtype != CGPS_F32 && dtype != CGPS_F64)) return fail(CGPS_ERR_UNSUPPORTED, "unsupported d / dtype");
-  *elems = ((3 * d * d + 2 * d + 3) / 4) * 4;
+  *elems = cgps::record_stride(d);
   return CGPS_OK;
 }
 

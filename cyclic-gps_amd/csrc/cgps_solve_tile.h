@@ -20,15 +20,10 @@
 // sweep: the x of the previous tile's last row).
 #pragma once
 #include "cgps_math.h"
+#include "cgps_plan.h"
 
 namespace cgps {
 
-constexpr int SOLVE_LP = 10;            // levels per pass
-constexpr int SOLVE_TS = 1 << SOLVE_LP; // rows per tile
-constexpr int SOLVE_NT = 512;           // threads per workgroup (= eliminations of a tile's level 0)
-constexpr int SOLVE_MAXLEV = SOLVE_LP + 1;
-constexpr int SOLVE_LP_WIDE = 3;                  // levels per pass while the system is large ...
-constexpr int64_t SOLVE_WIDE_ROWS = 1 << 20;      // ... i.e. has at least this many rows (2^18 .. 2^20 measured alike)
 template <typename T, int D> constexpr size_t solve_lds_bytes() {
   return (size_t)SOLVE_TS * D * sizeof(T) + 2 * (SOLVE_NT / 64) * sizeof(double) + (size_t)(2 + SOLVE_MAXLEV) * D * sizeof(T);
 }
@@ -36,13 +31,6 @@ template <typename T, int D> constexpr size_t solve_lds_bytes() {
 // Blocks of <= 128 bytes: hold the forward sweep to 64 registers (it needs 65 otherwise), i.e. four
 // resident workgroups per CU; larger blocks need more registers than that anyway.
 template <typename T, int D> constexpr int solve_min_waves() { return (size_t)D * D * sizeof(T) <= 128 ? 8 : 1; }
-
-// offsets (in blocks) of the levels one pass covers, and their sizes
-struct PassLevels {
-  int64_t offD[SOLVE_MAXLEV], offF[SOLVE_MAXLEV], offG[SOLVE_MAXLEV], m[SOLVE_MAXLEV];
-  int nlev;       // levels this pass runs
-  int64_t endD, endF, endG;   // one past the last block of this pass's levels in Dp / Fp / Gp
-};
 
 // A single-tile (top) pass is a chain of ~2 nlev dependent phases; touching its small,
 // contiguous slice of the factor once up front turns every later load into an L2 hit.
@@ -225,7 +213,7 @@ __global__ __launch_bounds__(SOLVE_NT, (solve_min_waves<T, D>())) void halfsolve
 // its right-hand-side entry in the backward sweep) before anything else: ONE round trip for the
 // whole pass; after it the levels only touch LDS (two barriers each).  Six blocks in registers:
 // for blocks of at most 128 bytes (fp64 d <= 4, fp32 d <= 5), one workgroup per CU.
-template <typename T, int D> constexpr bool solve_deep_supported() { return (size_t)D * D * sizeof(T) <= 128; }
+template <typename T, int D> constexpr bool solve_deep_supported() { return deep_block(D, sizeof(T)); }
 
 struct DeepOwner {
   int j, k;           // the deep elimination (level >= 1) this lane owns, j = -1: none

@@ -15,7 +15,6 @@
 
 namespace cgps {
 
-template <int MC> constexpr int solve_m_tile_log2() { return MC <= 2 ? 9 : (MC <= 4 ? 8 : 7); }
 // Eight columns: the 128-row tile has 64 threads' worth of eliminations, ONE wave per workgroup, and the LDS tile lets
 // four or five of them share a CU -- barely more than a wave per SIMD, every latency of a level exposed (2.7 TB/s).
 // The panel's columns are therefore split over CS = 2 waves of the workgroup: wave c takes columns [4c, 4c + 4) of
@@ -402,7 +401,6 @@ __global__ __launch_bounds__((1 << solve_m_tile_log2<MC>()) / 2 * solve_m_col_sp
 // of both -- and, in the backward sweep, its two right-hand-side panels -- before anything else, and the levels then only
 // touch LDS.  Tiles of 2^TSLD rows, 2^TSLD / 2 lanes per column split: 256 threads, one wave per SIMD (seven blocks
 // and two panels in registers); blocks of at most 128 bytes, as for the single-column form.
-template <int MC> constexpr int solve_m_deep_tile_log2() { return MC >= 8 ? 8 : 9; }
 template <typename T, int D, int MC>
 constexpr size_t solve_m_deep_lds_bytes() {
   return ((size_t)(1 << solve_m_deep_tile_log2<MC>()) + 2 + SOLVE_MAXLEV) * D * MC * sizeof(T) + 64 * sizeof(double);

@@ -41,7 +41,7 @@
 #include <type_traits>
 
 #include "cgps_level.h"
-#include "cgps_tile_sizes.h"
+#include "cgps_plan.h"
 #include "cgps_leg.h"
 
 namespace cgps {
@@ -487,7 +487,7 @@ template <typename T, int D> constexpr int record_rcmax() { return (D == 8 || (s
 template <typename T, int D>
 struct RecordLayout {
   static constexpr int DD = D * D;
-  static constexpr int STRIDE = ((3 * DD + 2 * D + 3) / 4) * 4;   // elements, 16/32-byte aligned
+  static constexpr int STRIDE = record_stride(D);   // elements, 16/32-byte aligned
   static constexpr int RS = 0, CS = DD, DRA = 2 * DD, YS = 3 * DD, DYA = 3 * DD + D;
 };
 
@@ -1252,9 +1252,7 @@ static __global__ __launch_bounds__(256) void sum_partials4_kernel(const double*
 
 // ---- host side ------------------------------------------------------------------------------
 // does the 256-row LDS tile of the record stages fit the 160 KB of LDS?  (fp64 d <= 5, fp32 d <= 8)
-template <typename T, int D> constexpr bool tile_fits_256() {
-  return ((size_t)256 * (2 * D * D + D) + D * D) * sizeof(T) + 4096 <= 160 * 1024;
-}
+template <typename T, int D> constexpr bool tile_fits_256() { return tile_fits_256(D, sizeof(T)); }
 // The fused pipeline is built for every block size 1 <= d <= 8 in both precisions.  (Above fp64
 // d=4 / fp32 d=5 the one-lane-per-row code spills registers; it still reads the inputs once
 // instead of three times, which is what counts for an HBM-bound path.)  The factor-emitting
@@ -1446,17 +1444,16 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
                           const T* Oleft = nullptr, T* shard_record = nullptr, double* shard_partial = nullptr) {
   using Cfg = TileCfg<T, D>;
   using RL = RecordLayout<T, D>;
-  if (ws_bytes < tile_ws_bytes(N, D, sizeof(T))) return -1;
-  if (Cfg::ROWS1 != tile_rows1(D, sizeof(T))) return -1;   // the two definitions of ROWS1 must agree
+  static_assert(Cfg::ROWS1 == tile_rows1(D, sizeof(T)), "the workspace is sized for other stage-1 tiles than the kernels take");
+  const cgps_host::TileWs w = cgps_host::tile_ws(N, D, sizeof(T));
+  if (ws_bytes < w.total) return -1;
   const int clong = (Cfg::LPR > 1 || !fold_final_enabled()) ? 0 : long_chunk_rows_per_lane(N, Cfg::NG1, Cfg::C, (int)(D * D * sizeof(T)));
   const int csel = clong > 0 ? clong : ((Cfg::LPR > 1 || Cfg::ALWAYS_WIDE) ? Cfg::C : stage1_rows_per_lane(N, Cfg::C, Cfg::NT1));
   const int64_t rows_per_tile = (int64_t)csel * Cfg::NG1;
   const int64_t tiles = (N + rows_per_tile - 1) / rows_per_tile;
-  const int64_t tiles_cap = tile_cap(N, D, sizeof(T));
-  double* partial = reinterpret_cast<double*>(ws);
-  const size_t pbytes = ((size_t)(2 * tiles_cap + 8) * PARTIAL_STRIDE * sizeof(double) + 255) & ~(size_t)255;
-  T* recA = reinterpret_cast<T*>(ws + pbytes);
-  T* recB = recA + (size_t)(tiles_cap + 2) * RL::STRIDE;
+  double* partial = cgps_host::at<double>(ws, w.partial);
+  T* recA = cgps_host::at<T>(ws, w.recA);
+  T* recB = cgps_host::at<T>(ws, w.recB);
   const size_t lds1 = stage_lds_bytes<T, D>(Cfg::NG1, Cfg::NT1), lds3 = stage_lds_bytes<T, D>(Cfg::NTILE3, Cfg::NT3);
   tile_set_attributes<T, D>();
   if (ev_start) (void)hipEventRecord(ev_start, st);
@@ -1615,22 +1612,21 @@ int run_tile_leg(const T* ts, const T* G, const T* A, const T* v, int64_t N, cha
     return -2;
   } else {
     using Cfg = TileCfg<T, D>;
-    using RL = RecordLayout<T, D>;
     if (!fold_final_enabled()) return -2;
-    const size_t ws1 = (tile_ws_bytes(N, D, sizeof(T)) + 255) & ~(size_t)255;
-    if (ws_bytes < (pair ? 2 * ws1 : ws1)) return -1;
+    // one pipeline, or two of them a fixed stride apart (the pair form)
+    const cgps_host::TilePairWs pw = cgps_host::tile_pair_ws(N, D, sizeof(T));
+    const cgps_host::TileWs& w = pw.one;
+    if (ws_bytes < (pair ? pw.total : pw.stride)) return -1;
     const int64_t per_round = (int64_t)STAGE1_SMALL_TILES * Cfg::NG1;
     const int64_t c = (N + per_round - 1) / per_round;
     if (c > (1 << 20)) return -2;
     const int64_t rows_per_tile = c * Cfg::NG1;
     const int64_t tiles = (N + rows_per_tile - 1) / rows_per_tile;
-    const int64_t tiles_cap = tile_cap(N, D, sizeof(T));
-    double* partial = reinterpret_cast<double*>(ws);
-    const size_t pbytes = ((size_t)(2 * tiles_cap + 8) * PARTIAL_STRIDE * sizeof(double) + 255) & ~(size_t)255;
-    T* recA = reinterpret_cast<T*>(ws + pbytes);
-    T* recB = recA + (size_t)(tiles_cap + 2) * RL::STRIDE;
+    double* partial = cgps_host::at<double>(ws, w.partial);
+    T* recA = cgps_host::at<T>(ws, w.recA);
+    T* recB = cgps_host::at<T>(ws, w.recB);
     tile_set_attributes<T, D>();
-    const FoldArgs fa{fold_slot_for(ws), recB, out2, info, nullptr, nullptr, (int)c, pair ? fold_slot_for(ws + ws1) : 0, ws1};
+    const FoldArgs fa{fold_slot_for(ws), recB, out2, info, nullptr, nullptr, (int)c, pair ? fold_slot_for(ws + pw.stride) : 0, pw.stride};
     const dim3 grid((unsigned)tiles, pair ? 2u : 1u);
     if constexpr (Cfg::ALWAYS_WIDE) {
       const size_t ldsw = stage_lds_bytes<T, D>(Cfg::NG1, 2 * Cfg::NT1);

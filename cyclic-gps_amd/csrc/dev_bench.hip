@@ -273,7 +273,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&O2, N * D * D * sizeof(T)));
     CK(hipMalloc(&y2, N * D * sizeof(T)));
     hipLaunchKernelGGL((gen_kernel<T, D>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s2, R2, O2, y2, N);
-    const size_t wsb = tile_ws_bytes(N, D, sizeof(T));
+    const size_t wsb = cgps_host::tile_ws(N, D, sizeof(T)).total;
     char* ws;
     double* out2;
     int* info;

@@ -130,15 +130,25 @@ def _workspace_bytes(N, d, dtc, op, nrhs=1):
     return b.value
 
 
-_ws_cache = {}
+_ws_cache, _pair_ws_cache = {}, {}
+
+
+def _scratch(cache, nbytes, device):
+    key = (device, torch.cuda.current_stream().cuda_stream)
+    cur = cache.get(key)
+    if cur is None or cur.numel() < nbytes:
+        cur = cache[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return cur
 
 
 def workspace(N, d, dt, op, device, nrhs=1):
     """A cached scratch tensor of the size the library asks for (torch owns the memory)."""
     nbytes = _workspace_bytes(int(N), int(d), dtype_code(dt), int(op), int(nrhs))
-    key = (device, torch.cuda.current_stream().cuda_stream)
-    cur = _ws_cache.get(key)
-    if cur is None or cur.numel() < nbytes:
-        cur = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-        _ws_cache[key] = cur
-    return cur, nbytes
+    return _scratch(_ws_cache, nbytes, device), nbytes
+
+
+def pair_workspace(N, d, dt, device):
+    """The same for cgps_leg_mahal_logdet_pair: two fused pipelines, each rounded up to 256 bytes (tile_pair_ws in
+    csrc/cgps_plan.h is the layout run_tile_leg cuts up; include/cgps.h states the size)."""
+    nbytes = 2 * ((_workspace_bytes(int(N), int(d), dtype_code(dt), OP_MAHAL_LOGDET) + 255) // 256 * 256)
+    return _scratch(_pair_ws_cache, nbytes, device)

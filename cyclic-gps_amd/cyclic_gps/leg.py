@@ -195,9 +195,6 @@ def leg_mahal_and_det(ts, G, A=None, v=None):
     return out[0], out[1]
 
 
-_pair_ws = {}
-
-
 def leg_loglik_reductions(ts, G, A, v):
     """The two reductions of a LEG log-likelihood in ONE launch (cgps_leg_mahal_logdet_pair): returns
     (v^T K^-1 v, log|K|, log|Sigma^-1|) with K = PEG precision(ts, G) + blockdiag(A), Sigma^-1 the PEG precision itself
@@ -206,15 +203,7 @@ def leg_loglik_reductions(ts, G, A, v):
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
     ts = ts.to(dt).contiguous()
     G, A, v = G.contiguous(), A.to(dt).contiguous(), v.to(dt).contiguous()
-    nbytes = 2 * ((_hip._workspace_bytes(int(n), int(d), _hip.dtype_code(dt), _hip.OP_MAHAL_LOGDET) + 255) // 256 * 256)
-    key = (G.device, torch.cuda.current_stream().cuda_stream)
-    ws = _pair_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _pair_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
-    out = torch.empty(4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A), _hip.ptr(v), n, d, _hip.dtype_code(dt),
-                                                     _hip.ptr(ws), ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    out, info = _leg_pair_raw(ts, G, A, v)
     if cr.CHECK_POSITIVE_DEFINITE:
         bad = info.tolist()
         if bad[0] or bad[1]:
@@ -293,11 +282,7 @@ def _leg_pair_raw(ts, G, A, v):
     """cgps_leg_mahal_logdet_pair of one series: (out4 fp64, info2), nothing read on the host."""
     from . import _hip
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
-    nbytes = 2 * ((_hip._workspace_bytes(int(n), int(d), _hip.dtype_code(dt), _hip.OP_MAHAL_LOGDET) + 255) // 256 * 256)
-    key = (G.device, torch.cuda.current_stream().cuda_stream)
-    ws = _pair_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _pair_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
+    ws = _hip.pair_workspace(n, d, dt, G.device)
     out = torch.empty(4, dtype=torch.float64, device=G.device)
     info = torch.zeros(2, dtype=torch.int32, device=G.device)
     _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A), _hip.ptr(v), n, d, _hip.dtype_code(dt),
