@@ -395,6 +395,40 @@ inline void plan_panel_sweep(const Layout& L, SolvePasses& P, int mc, bool deep_
   make_passes(L, P, cgps::SOLVE_LP_WIDE, 1 << tsl, tsl, 0, deep_block ? 1 << tsld : 0, tsld, panel_deep_tiles(mc, deep_enabled));
 }
 
+// ---- cgps_sample (cgps_sample_tile.h): the backward panel sweep with ALL column chunks of a pass in one launch ------
+// Chunk c (columns [c mc, c mc + mc)) has its own slice of the two coarse-solution buffers: backward pass p > 0 writes
+// its [rows[p]][d][mc] solution into slice c of buf[p & 1] and pass p - 1 reads it there, so buf[b] is sized for the
+// largest pass of its parity (exactly, from the plan) times the chunks of a launch.  At most SAMPLE_CHUNK_GROUP chunks
+// (1024 columns) go into one launch, and the workspace never holds more than that many slices: more samples than that
+// run group after group on the same slices (launches = passes x groups).  With the three-level first pass of a system
+// of >= 2^20 rows a slice pair is (1/8 + 1/64) of the chunk's output, so the workspace stays below a fifth of x.
+constexpr int64_t SAMPLE_CHUNK_GROUP = 128;
+struct SampleWs {
+  Region buf[2];
+  size_t slice[2];                    // bytes from one chunk's slice of buf[b] to the next
+  int mc;                             // panel width
+  int64_t chunks, group;              // column chunks of the call; chunks per launch
+  size_t total;
+};
+inline SampleWs sample_ws(int64_t N, int d, size_t s, int64_t nrhs) {
+  SampleWs w{};
+  w.mc = cgps::panel_width(nrhs > 8 ? 8 : (int)nrhs);
+  w.chunks = (nrhs + w.mc - 1) / w.mc;
+  w.group = w.chunks < SAMPLE_CHUNK_GROUP ? w.chunks : SAMPLE_CHUNK_GROUP;
+  Layout L;
+  make_layout(N, L);
+  SolvePasses P;
+  plan_panel_sweep(L, P, w.mc, false, false);
+  int64_t cap[2] = {0, 0};
+  for (int p = 1; p < P.np; ++p)
+    if (P.rows[p] > cap[p & 1]) cap[p & 1] = P.rows[p];
+  for (int b = 0; b < 2; ++b) w.slice[b] = align_up((size_t)cap[b] * d * w.mc * s);
+  w.buf[0] = {0, w.slice[0] * (size_t)w.group};
+  w.buf[1] = {w.buf[0].end(), w.slice[1] * (size_t)w.group};
+  w.total = max_bytes(w.buf[1].end(), 256);
+  return w;
+}
+
 // ---- passes of the factorisation ---------------------------------------------------------------------------------
 // A pass reads the caller's Rs / Os (in < 0) or what the previous pass left in buf[in] of decompose_ws(), and writes
 // into buf[out] (out < 0: nothing, the pass runs to the end): one launch per level writes the next level's rows

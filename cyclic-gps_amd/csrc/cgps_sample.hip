@@ -1,0 +1,113 @@
+// cgps_sample.hip -- counter-based standard normals and samples from N(mean, J^-1) off a stored factor
+// One translation unit of libcgps (include/cgps.h); host code only decides sizes/offsets and
+// enqueues kernels on the caller's stream: nothing here allocates, copies to the host or synchronises.
+#include "cgps_host.h"
+#include "cgps_sample_tile.h"
+
+using namespace cgps_host;
+
+namespace cgps {
+// out [rows][cols]: one lane per (row, column group)
+template <typename T>
+__global__ __launch_bounds__(256) void normal_fill_kernel(T* __restrict__ out, int64_t rows, int64_t cols, int64_t groups,
+                                                          uint64_t seed, uint32_t stream) {
+  constexpr int GC = RngGroup<T>::COLS;
+  const int64_t items = rows * groups, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += step) {
+    const int64_t r = it / groups, g = it - r * groups;
+    T z[GC];
+    normal_group(seed, stream, (uint64_t)r, (uint32_t)g, z);
+    T* p = out + r * cols + g * GC;
+#pragma unroll
+    for (int u = 0; u < GC; ++u)
+      if (g * GC + u < cols) p[u] = z[u];
+  }
+}
+}  // namespace cgps
+
+namespace {
+template <typename T>
+int run_normal_fill(T* out, int64_t rows, int64_t cols, uint64_t seed, uint32_t stream_id, hipStream_t st) {
+  constexpr int GC = cgps::RngGroup<T>::COLS;
+  const int64_t groups = (cols + GC - 1) / GC;
+  if (groups > (int64_t)1 << 32) return fail(CGPS_ERR_ARG, "cgps_normal_fill: more than 2^32 column groups");
+  const int64_t blocks = (rows * groups + 255) / 256, cap = (int64_t)1 << 20;
+  hipLaunchKernelGGL((cgps::normal_fill_kernel<T>), dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, st, out, rows,
+                     cols, groups, seed, stream_id);
+  return check_launch("normal fill");
+}
+
+template <typename T, int D, int MC>
+int run_sample(const T* Dp, const T* Fp, const T* Gp, int64_t N, int64_t nrhs, const T* mean, uint64_t seed, uint32_t stream_id,
+               T* x, char* ws, size_t ws_bytes, hipStream_t st) {
+  constexpr int TSL = cgps::solve_m_tile_log2<MC>(), NT = (1 << TSL) / 2, CS = cgps::solve_m_col_splits<MC>();
+  const SampleWs w = sample_ws(N, D, sizeof(T), nrhs);
+  if (ws_bytes < w.total) return fail(CGPS_ERR_ARG, "workspace too small: %zu < %zu", ws_bytes, w.total);
+  const size_t lds = cgps::solve_m_lds_bytes<T, D, MC>();
+  static PerDevice<int> done;
+  done.get([&](int) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cgps::sample_tile_m_kernel<T, D, MC>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return 1;
+  });
+  Layout L;
+  make_layout(N, L);
+  SolvePasses P;                    // the one regular kernel form for every pass (no latency-bound variants)
+  plan_panel_sweep(L, P, MC, false, false);
+  T* bufs[2] = {at<T>(ws, w.buf[0]), at<T>(ws, w.buf[1])};
+  const size_t slice[2] = {w.slice[0] / sizeof(T), w.slice[1] / sizeof(T)};
+  for (int64_t c = 0; c < w.chunks; c += w.group) {        // one group unless nrhs > 8 SAMPLE_CHUNK_GROUP
+    const int64_t gc = w.chunks - c < w.group ? w.chunks - c : w.group, col0 = c * MC;
+    const T* xc = nullptr;
+    size_t xc_stride = 0;
+    for (int p = P.np - 1; p >= 0; --p) {
+      const bool last = p == 0;
+      T* X = last ? x + col0 : bufs[P.buf(p)];
+      const size_t stride = last ? (size_t)MC : slice[P.buf(p)];
+      hipLaunchKernelGGL((cgps::sample_tile_m_kernel<T, D, MC>), dim3((unsigned)P.tiles[p], (unsigned)gc), dim3(NT * CS), lds, st,
+                         Dp, Fp, Gp, P.lv[p], seed, stream_id, col0, nrhs, xc, xc_stride, P.rows[p], X, stride,
+                         last ? nrhs : (int64_t)MC, last ? mean : nullptr);
+      xc = X;
+      xc_stride = stride;
+    }
+  }
+  return check_launch("sample");
+}
+}  // namespace
+
+extern "C" {
+
+int cgps_normal_fill(void* out, int64_t rows, int64_t cols, int dtype, uint64_t seed, uint32_t stream_id, void* stream) {
+  if (!out || rows < 1 || cols < 1) return fail(CGPS_ERR_ARG, "cgps_normal_fill: null pointer, rows < 1 or cols < 1");
+  if (dtype == CGPS_F32) return run_normal_fill<float>((float*)out, rows, cols, seed, stream_id, (hipStream_t)stream);
+  if (dtype == CGPS_F64) return run_normal_fill<double>((double*)out, rows, cols, seed, stream_id, (hipStream_t)stream);
+  return fail(CGPS_ERR_UNSUPPORTED, "dtype %d not supported", dtype);
+}
+
+int cgps_sample_workspace_bytes(int64_t N, int d, int dtype, int64_t nrhs, size_t* bytes) {
+  if (bad_common(N, d) || !bytes || nrhs < 1) return fail(CGPS_ERR_ARG, "cgps_sample_workspace_bytes: bad argument");
+  if (d > 8) return fail(CGPS_ERR_UNSUPPORTED, "block size d=%d outside 1..8", d);
+  if (dtype != CGPS_F32 && dtype != CGPS_F64) return fail(CGPS_ERR_UNSUPPORTED, "dtype %d not supported", dtype);
+  *bytes = sample_ws(N, d, dtype == CGPS_F32 ? 4 : 8, nrhs).total;
+  return CGPS_OK;
+}
+
+int cgps_sample(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype, int64_t nrhs, const void* mean,
+                uint64_t seed, uint32_t stream_id, void* x, void* ws, size_t ws_bytes, void* stream) {
+  if (bad_common(N, d) || nrhs < 1 || !Dp || !Fp || !Gp || !x || !ws)
+    return fail(CGPS_ERR_ARG, "cgps_sample: null pointer, N < 1 or nrhs < 1");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    switch (cgps::panel_width(nrhs > 8 ? 8 : (int)nrhs)) {
+      case 2: return run_sample<T, D, 2>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)mean, seed, stream_id, (T*)x,
+                                         (char*)ws, ws_bytes, (hipStream_t)stream);
+      case 4: return run_sample<T, D, 4>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)mean, seed, stream_id, (T*)x,
+                                         (char*)ws, ws_bytes, (hipStream_t)stream);
+      default: return run_sample<T, D, 8>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)mean, seed, stream_id, (T*)x,
+                                          (char*)ws, ws_bytes, (hipStream_t)stream);
+    }
+  });
+}
+
+}  // extern "C"

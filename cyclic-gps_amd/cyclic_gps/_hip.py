@@ -38,6 +38,9 @@ _SIGNATURES = {
     "cgps_halfsolve": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _sz, _vp, _vp]),
     "cgps_backsolve": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "cgps_solve": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "cgps_normal_fill": (_int, [_vp, _i64, _i64, _int, ctypes.c_uint64, ctypes.c_uint32, _vp]),
+    "cgps_sample_workspace_bytes": (_int, [_i64, _int, _int, _i64, ctypes.POINTER(_sz)]),
+    "cgps_sample": (_int, [_vp, _vp, _vp, _i64, _int, _int, _i64, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _sz, _vp]),
     "cgps_logdet_factor": (_int, [_vp, _i64, _int, _int, _vp, _sz, _vp, _vp]),
     "cgps_inverse_blocks": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "cgps_mahal_logdet_adjoint": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
@@ -144,6 +147,19 @@ def _scratch(cache, nbytes, device):
 def workspace(N, d, dt, op, device, nrhs=1):
     """A cached scratch tensor of the size the library asks for (torch owns the memory)."""
     nbytes = _workspace_bytes(int(N), int(d), dtype_code(dt), int(op), int(nrhs))
+    return _scratch(_ws_cache, nbytes, device), nbytes
+
+
+@functools.lru_cache(maxsize=512)
+def _sample_workspace_bytes(N, d, dtc, nrhs):
+    b = _sz(0)
+    check(lib().cgps_sample_workspace_bytes(N, d, dtc, nrhs, ctypes.byref(b)))
+    return b.value
+
+
+def sample_workspace(N, d, dt, nrhs, device):
+    """The same for cgps_sample (its own carve-up: sample_ws in csrc/cgps_plan.h)."""
+    nbytes = _sample_workspace_bytes(int(N), int(d), dtype_code(dt), int(nrhs))
     return _scratch(_ws_cache, nbytes, device), nbytes
 
 

@@ -458,6 +458,41 @@ def inverse_blocks(decomp):
 
 
 # ----------------------------------------------------------------------------
+# sampling (an addition to the reference's surface; its LEGFamily.sample_from_prior, models.py:243-252, is a stub)
+# ----------------------------------------------------------------------------
+def standard_normal(rows, cols, seed, stream=0, dtype=torch.float64, device=None):
+    """[rows, cols] standard normals, element (r, s) a pure function of (seed, stream, r, s): Philox4x32-10 and
+    Box-Muller as csrc/cgps_rng.h specifies them (cgps_normal_fill).  The first c columns of a wider array are bitwise
+    those of a c-column array; `stream` separates independent arrays drawn under one seed."""
+    dev = _device() if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _hip.CgpsError("standard_normal fills device memory: the generator is a HIP kernel (no CPU fallback)")
+    rows, cols = int(rows), int(cols)
+    out = torch.empty((rows, cols), dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.lib().cgps_normal_fill(_hip.ptr(out), rows, cols, _hip.dtype_code(dtype),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, _hip.stream_ptr()))
+    return out
+
+
+def sample(decomp, num_samples, seed, mean=None, stream=0):
+    """num_samples draws from N(mean, J^-1) off the factor of J: x[:, :, s] = mean + backhalfsolve(decomp, eps)[:, :, s]
+    with eps = standard_normal(N d, num_samples, seed, stream) in CRR layout -- one call (cgps_sample) that makes the
+    noise in registers inside the backward sweep and never writes it.  Returns [N, d, num_samples]; sample s depends on
+    (seed, stream, s) only, not on num_samples.  mean: [N, d] or None (zero).  No autograd graph."""
+    Dp, Fp, Gp, N, d, like = _packed(decomp)
+    dev, dt = Dp.device, Dp.dtype
+    S = int(num_samples)
+    mu = None if mean is None else _stage(mean.detach(), dt).reshape(N, d).contiguous()
+    x = torch.empty((N, d, S), dtype=dt, device=dev)
+    ws, nbytes = _hip.sample_workspace(N, d, dt, S, dev)
+    _hip.check(_hip.lib().cgps_sample(
+        _hip.ptr(Dp), _hip.ptr(Fp), _hip.ptr(Gp), N, d, _hip.dtype_code(dt), S, _hip.ptr(mu),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, _hip.ptr(x), _hip.ptr(ws), nbytes, _hip.stream_ptr()))
+    return _back(x, like)
+
+
+# ----------------------------------------------------------------------------
 # banded products with the block upper-bidiagonal U (diagonal F, super-diagonal G).
 # Thin device-side helpers of the reference surface (:15-200); they run as batched
 # products wherever their inputs live and are not on the fused hot path.

@@ -580,6 +580,37 @@ def insample_posterior(m, ts, xs):
     return mean, cr.inverse_blocks(dec)
 
 
+# ---- drawing from the process -----------------------------------------------------------------------
+def sample_observations(m, z, seed, stream=1):
+    """Observations of latent paths z [n, rank, S]: x = B z + Lambda eps' [n, obs, S], eps' =
+    ``cr.standard_normal(n obs, S, seed, stream)`` (the observation model of models.py:254-280).  Its default noise
+    stream is 1; the latent draws of ``cr.sample`` use stream 0 of the same seed."""
+    n, S = z.shape[0], z.shape[2]
+    obs = m.B.shape[0]
+    eps = cr.standard_normal(n * obs, S, seed, stream=stream, dtype=z.dtype, device=z.device if z.is_cuda else None)
+    eps = eps.to(z.device).reshape(n, obs, S)                # (CPU inputs: generated on the GPU, like every result)
+    return torch.baddbmm(torch.matmul(m.Lambda.to(z.dtype), eps), m.B.to(z.dtype).expand(n, -1, -1), z)
+
+
+def sample_from_prior(m, ts, num_samples, seed):
+    """num_samples draws of the LEG process at times ts: (z [n, rank, S] latent paths, x [n, obs, S] observations).
+    The finished form of the reference's LEGFamily.sample_from_prior stub (models.py:243-252): the prior precision
+    (``peg_precision``), its factor, ``cr.sample`` for z, ``sample_observations`` for x.  No autograd graph."""
+    with torch.no_grad():
+        Rs, Os = peg_precision(ts, m.G)
+        z = cr.sample(cr.decompose(Rs, Os), num_samples, seed)
+        return z, sample_observations(m, z, seed)
+
+
+def sample_from_posterior(m, ts, xs, num_samples, seed):
+    """num_samples latent paths z [n, rank, S] from the posterior given xs at ts: factor and posterior mean together
+    (``cr.decompose_solve``), then ``cr.sample`` with that mean -- two library calls.  No autograd graph."""
+    with torch.no_grad():
+        K_Rs, K_Os = posterior_precision(m, ts)
+        dec, mean = cr.decompose_solve(K_Rs, K_Os, compute_v(m, xs))
+        return cr.sample(dec, num_samples, seed, mean=mean)
+
+
 # ---- the config-5 workload -----------------------------------------------------------------
 def co2_like_series(rows=770, seed=0, dtype=torch.float64):
     """Mauna-Loa-shaped monthly series (decimal date, ppm): quadratic trend + annual and

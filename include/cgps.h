@@ -133,6 +133,25 @@ int cgps_logdet_factor(const void* Dp, int64_t N, int d, int dtype,
 int cgps_inverse_blocks(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype,
                         void* Sd, void* So, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- sampling (an addition to the reference's surface: LEGFamily.sample_from_prior, models.py:243-252, is a stub) ----
+ * Counter-based standard normals: out[rows][cols], element (r, s) a pure function of (seed, stream_id, r, s) --
+ * Philox4x32-10 and Box-Muller, specified in csrc/cgps_rng.h.  Column s of row r does not depend on cols: the first
+ * c columns of a wider array are bitwise those of a c-column array.  stream_id: a caller-chosen word that separates
+ * independent arrays drawn under one seed. */
+int cgps_normal_fill(void* out, int64_t rows, int64_t cols, int dtype, uint64_t seed, uint32_t stream_id, void* stream);
+
+/* Samples from N(mean, J^-1) off a stored factor: x[:, :, s] = mean + H^T eps[:, :, s], H = L^-1 T (cgps_halfsolve),
+ * H^T = cgps_backsolve, J^-1 = H^T H.  eps[N][d][nrhs] is BY DEFINITION what
+ * cgps_normal_fill(rows = N d in CRR order, cols = nrhs, seed, stream_id) writes, but it is never in memory: the lane
+ * that eliminates a block row makes its panel of eps in registers (csrc/cgps_sample_tile.h), and the last pass adds
+ * mean[N][d] (NULL: zero) in its store to x[N][d][nrhs].  Sample s therefore depends on (seed, stream_id, s) alone,
+ * not on nrhs.  Launches: one per pass of the sweep for up to 1024 samples (all eight-column chunks of a pass in one
+ * launch), each further 1024 samples the same passes again on the same workspace.  1 <= d <= 8, any N, nrhs >= 1.
+ * Workspace: cgps_sample_workspace_bytes(). */
+int cgps_sample_workspace_bytes(int64_t N, int d, int dtype, int64_t nrhs, size_t* bytes);
+int cgps_sample(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype, int64_t nrhs,
+                const void* mean, uint64_t seed, uint32_t stream_id, void* x, void* ws, size_t ws_bytes, void* stream);
+
 /* Adjoint of mahal_and_det in the blocks (what autograd computes through cyclic_reduction.py:380-438
  * for LEGFamily.training_step, models.py:374-381).  Given Sd/So = inverse_blocks(decomp),
  * w[N][d] = solve(decomp, x) and the two upstream gradients gm, gl (DEVICE scalars of the blocks'
