@@ -19,6 +19,8 @@ namespace cgps_host {
 // defined once, in cgps_core.hip
 extern thread_local char g_err[512];
 extern thread_local hipEvent_t g_prof_start, g_prof_stop;
+// cgps_leg_obs.hip: zero the arrival counters of that translation unit's fused launches (cgps_reset_counters)
+hipError_t leg_obs_reset_counters(hipStream_t st);
 
 inline int fail(int code, const char* fmt, ...) {
   va_list ap;

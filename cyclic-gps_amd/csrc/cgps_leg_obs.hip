@@ -1,0 +1,32 @@
+// cgps_leg_obs.hip -- the fused LEG reductions for series with missing observations: every row names the entry of
+// a table of diagonal terms it adds (chunk_reduce_kernel<.., SRC = 2>, cgps_tile.h).  A translation unit of its own:
+// these are the heaviest stage-1 instantiations of the library and compile next to cgps_mahal.hip, not after it.
+#include "cgps_host.h"
+#include "cgps_tile.h"
+
+using namespace cgps_host;
+
+namespace cgps_host {
+hipError_t leg_obs_reset_counters(hipStream_t st) { return cgps::fold_reset_counters(st); }
+}  // namespace cgps_host
+
+extern "C" {
+
+int cgps_leg_mahal_logdet_pair_obs(const void* ts, const void* G, const void* A_table, int P, const unsigned char* pattern,
+                                   const void* v, int64_t N, int d, int dtype, void* ws, size_t ws_bytes, double* out4,
+                                   int* info2, void* stream) {
+  if (bad_common(N, d) || !ts || !G || !A_table || !pattern || !ws || !out4 || !info2)
+    return fail(CGPS_ERR_ARG, "cgps_leg_mahal_logdet_pair_obs: null pointer or N < 1");
+  if (P < 1 || P > 256) return fail(CGPS_ERR_ARG, "cgps_leg_mahal_logdet_pair_obs: P = %d table entries, outside 1..256", P);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int rc = cgps::run_tile_leg<T, D, 2>((const T*)ts, (const T*)G, (const T*)A_table, (const T*)v, N, (char*)ws, ws_bytes,
+                                               out4, info2, (hipStream_t)stream, true, pattern, P);
+    if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_obs (that of cgps_leg_mahal_logdet_pair)");
+    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_mahal_logdet_pair_obs: not built for this block size (d = 8, fp64 d = 6) or CGPS_NO_FOLD=1");
+    return check_launch("LEG tile reduction (pair, per-row observation pattern)");
+  });
+}
+
+}  // extern "C"

@@ -158,7 +158,8 @@ int cgps_boundary_recursions(const void* records, size_t record_stride_bytes, in
 }
 
 int cgps_reset_counters(void* stream) {
-  if (cgps::fold_reset_counters((hipStream_t)stream) != hipSuccess) return check_launch("cgps_reset_counters");
+  if (cgps::fold_reset_counters((hipStream_t)stream) != hipSuccess || leg_obs_reset_counters((hipStream_t)stream) != hipSuccess)
+    return check_launch("cgps_reset_counters");
   return CGPS_OK;
 }
 

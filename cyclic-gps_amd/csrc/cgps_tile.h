@@ -463,7 +463,7 @@ __device__ __forceinline__ typename Vec16<T>::type load16_coh(const T* p) {
 // Arrival counters of the folded final stage.  They live in the library's own device data (zero
 // when the code object is loaded, touched by nothing else) rather than in the caller's
 // workspace, whose contents are arbitrary before a call and which other entry points use as
-// scratch (one copy per translation unit that launches the fused pipeline: cgps_mahal.hip).  A counter is incremented with a wrapping atomic (atomicInc: old >= limit ? 0 : old + 1),
+// scratch (one copy per translation unit that launches the fused pipeline: cgps_mahal.hip, cgps_leg_obs.hip).  A counter is incremented with a wrapping atomic (atomicInc: old >= limit ? 0 : old + 1),
 // so the arrival that completes the count also puts it back to 0: no per-call memset, no reset
 // store, and a replayed graph launch finds it clean.  The host maps each workspace it has seen to
 // one slot (fold_slot_for): two launches may be in flight at the same time only with different
@@ -715,8 +715,10 @@ struct FoldArgs {
   void* shard_record;              // ... or one shard of a larger system (non-null): its single record
   double* shard_partial;           //     and its {sum of squares, sum of log pivots, fail, 0}
   int rows_per_lane;               // chunk_reduce_kernel<.., C = 0, ..>: rows per lane given at run time (a multiple of 4)
-  int pair_slot;                   // SRC = 1, gridDim.y = 2: counters and workspace offset (bytes) of the second system
+  int pair_slot;                   // SRC >= 1, gridDim.y = 2: counters and workspace offset (bytes) of the second system
   size_t pair_ws_stride;
+  const unsigned char* obs_pattern; // SRC = 2: [N] table entry of each row's diagonal term, and the table's length
+  int obs_entries;
 };
 template <typename T, int D, int NTILE, int NT, bool FINAL, bool INL = false>
 __device__ __forceinline__ void record_reduce_body(char* smem, unsigned tile_index, const T* __restrict__ rin, int64_t n,
@@ -809,6 +811,8 @@ __device__ __forceinline__ void fold_record_stages(char* smem, int* last_flag, T
 // but the last round's tail of a multi-round grid ever had the memory system to itself anyway.
 // SRC = 1: the rows are those of a LEG model, assembled in registers (cgps_tile_leg.h): Rg = time stamps [N], Og = the
 // generator G [d][d], Oleft = the block A added to every diagonal block (or nullptr), yg = right-hand side (or nullptr).
+// SRC = 2: the same, but Oleft = a table of fold.obs_entries blocks and row r adds entry fold.obs_pattern[r] of it
+// (rows that observe different channels, or nothing: leg_obs_block in cgps_tile_leg.h).  Nothing else differs.
 template <typename T, int D, int CT, int NT, int NW = NT, bool FOLD = false, int SRC = 0>
 __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void chunk_reduce_kernel(const T* __restrict__ Rg, const T* __restrict__ Og,
                                                           const T* __restrict__ yg, int64_t N,
@@ -824,7 +828,7 @@ __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void 
   CGPS_KSTAMP(0);
   if (tid == 0) *sm.sfail = 0x7fffffff;
   const int C = CT > 0 ? CT : fold.rows_per_lane;
-  if constexpr (SRC == 1) {
+  if constexpr (SRC >= 1) {
     // a pair launch (gridDim.y = 2: the two reductions of a LEG log-likelihood, models.py:349-367, side by side):
     // blockIdx.y = 1 is the prior precision itself -- no diagonal term, no right-hand side -- with its own records,
     // partial results, counters and outputs (out2 + 2, info + 1)
@@ -878,8 +882,8 @@ __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void 
   constexpr int RG = stage1_row_group<T, D>();
   constexpr bool GROUPED = SRC == 0 && RG > 1 && CT % RG == 0 && !YSTAGE;
   const bool grouped = GROUPED && whole_chunk_and_next && r0 < N;   // every row of the chunk, and O[last row], exist
-  T cR[D][D], cB[D][D];                          // SRC = 1: what the gap before the next row leaves it (cgps_tile_leg.h)
-  if constexpr (SRC == 1) {
+  T cR[D][D], cB[D][D];                          // SRC >= 1: what the gap before the next row leaves it (cgps_tile_leg.h)
+  if constexpr (SRC >= 1) {
     if (r0 < N) {
       if (r0 >= 1) {
         T tl[D][D];
@@ -888,7 +892,10 @@ __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void 
         set_zero<T, D>(cR);
         set_zero<T, D>(cB);
       }
-      leg_row<T, D>(Rg, Og, Oleft, yg, r0, N, cR, cB, Rc, Cc, yc, fail);
+      if constexpr (SRC == 2)
+        leg_row<T, D>(Rg, Og, leg_obs_block<T, D>(Oleft, fold.obs_pattern, fold.obs_entries, r0), yg, r0, N, cR, cB, Rc, Cc, yc, fail);
+      else
+        leg_row<T, D>(Rg, Og, Oleft, yg, r0, N, cR, cB, Rc, Cc, yc, fail);
     }
   } else
   if (r0 < N) {
@@ -951,8 +958,11 @@ __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void 
   for (int j = 0; j < L - 1; ++j) {
     const int64_t rn = r0 + j + 1;
     T Rn[D][D], On[D][D], yn[D];
-    if constexpr (SRC == 1) {
-      leg_row<T, D>(Rg, Og, Oleft, yg, rn, N, cR, cB, Rn, On, yn, fail);
+    if constexpr (SRC >= 1) {
+      if constexpr (SRC == 2)
+        leg_row<T, D>(Rg, Og, leg_obs_block<T, D>(Oleft, fold.obs_pattern, fold.obs_entries, rn), yg, rn, N, cR, cB, Rn, On, yn, fail);
+      else
+        leg_row<T, D>(Rg, Og, Oleft, yg, rn, N, cR, cB, Rn, On, yn, fail);
       eliminate_forward<T, D>(Rc, yc, Cc, dRa, dya, On, Rn, yn, pl, mah, fail);
       continue;
     }
@@ -1605,9 +1615,11 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
 // Built for the block sizes whose stage 1 runs one lane per row (every d <= 7 but fp64 d = 6).
 // returns 0 on success, -1 when the workspace is too small, -2 when this (dtype, d) is not built
 template <typename T, int D> constexpr bool leg_source_supported() { return TileCfg<T, D>::LPR == 1; }
-template <typename T, int D>
+// SRC = 2: A is a table of `entries` blocks and row r adds entry min(pattern[r], entries - 1) of it (pattern: N device
+// bytes).  Its kernels are instantiated by the translation unit that calls it (cgps_leg_obs.hip).
+template <typename T, int D, int SRC = 1>
 int run_tile_leg(const T* ts, const T* G, const T* A, const T* v, int64_t N, char* ws, size_t ws_bytes, double* out2,
-                 int* info, hipStream_t st, bool pair = false) {
+                 int* info, hipStream_t st, bool pair = false, const unsigned char* pattern = nullptr, int entries = 0) {
   if constexpr (!leg_source_supported<T, D>()) {
     return -2;
   } else {
@@ -1625,18 +1637,25 @@ int run_tile_leg(const T* ts, const T* G, const T* A, const T* v, int64_t N, cha
     double* partial = cgps_host::at<double>(ws, w.partial);
     T* recA = cgps_host::at<T>(ws, w.recA);
     T* recB = cgps_host::at<T>(ws, w.recB);
-    tile_set_attributes<T, D>();
-    const FoldArgs fa{fold_slot_for(ws), recB, out2, info, nullptr, nullptr, (int)c, pair ? fold_slot_for(ws + pw.stride) : 0, pw.stride};
-    const dim3 grid((unsigned)tiles, pair ? 2u : 1u);
-    if constexpr (Cfg::ALWAYS_WIDE) {
-      const size_t ldsw = stage_lds_bytes<T, D>(Cfg::NG1, 2 * Cfg::NT1);
-      hipLaunchKernelGGL((chunk_reduce_kernel<T, D, 0, Cfg::NT1, 2 * Cfg::NT1, true, 1>), grid, dim3(2 * Cfg::NT1), ldsw, st, ts,
-                         G, v, N, A, recA, partial, fa);
-    } else {
-      const size_t lds1 = stage_lds_bytes<T, D>(Cfg::NG1, Cfg::NT1);
-      hipLaunchKernelGGL((chunk_reduce_kernel<T, D, 0, Cfg::NT1, Cfg::NT1, true, 1>), grid, dim3(Cfg::NT1), lds1, st, ts, G, v,
-                         N, A, recA, partial, fa);
+    constexpr int NW = Cfg::ALWAYS_WIDE ? 2 * Cfg::NT1 : Cfg::NT1;
+    const size_t lds = stage_lds_bytes<T, D>(Cfg::NG1, NW);
+    if constexpr (SRC == 1) {
+      tile_set_attributes<T, D>();
+    } else {                       // (tile_set_attributes names, and so would instantiate here, every SRC = 0 / 1 kernel)
+      static std::once_flag once[TILE_MAX_DEVICES];
+      int dev = 0;
+      (void)hipGetDevice(&dev);
+      if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
+      std::call_once(once[dev], [lds] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&chunk_reduce_kernel<T, D, 0, Cfg::NT1, NW, true, SRC>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      });
     }
+    const FoldArgs fa{fold_slot_for(ws), recB, out2, info, nullptr, nullptr, (int)c, pair ? fold_slot_for(ws + pw.stride) : 0, pw.stride,
+                      pattern, entries};
+    const dim3 grid((unsigned)tiles, pair ? 2u : 1u);
+    hipLaunchKernelGGL((chunk_reduce_kernel<T, D, 0, Cfg::NT1, NW, true, SRC>), grid, dim3(NW), lds, st, ts, G, v, N, A, recA,
+                       partial, fa);
     return 0;
   }
 }

@@ -75,3 +75,15 @@ __device__ __forceinline__ void leg_row(const T* __restrict__ ts, const T* __res
       for (int j = 0; j < D; ++j) R[i][j] += tl[i][j];
   }
 }
+
+// The diagonal term of row r when rows differ in what they observe (chunk_reduce_kernel<.., SRC = 2>): entry pattern[r]
+// of a table of `entries` D x D blocks.  The index is clamped, so no byte value reads outside the table; a null table
+// (the prior-precision half of a pair launch) adds nothing and reads no pattern.  The address differs from lane to
+// lane, so leg_row reads the block with vector loads (the one block of SRC = 1 arrives through the scalar cache).
+template <typename T, int D>
+__device__ __forceinline__ const T* leg_obs_block(const T* __restrict__ table, const unsigned char* __restrict__ pattern,
+                                                  int entries, int64_t r) {
+  if (table == nullptr) return nullptr;
+  const int p = (int)pattern[r];
+  return table + (size_t)(p < entries - 1 ? p : entries - 1) * (D * D);
+}

@@ -290,6 +290,33 @@ def _leg_pair_raw(ts, G, A, v):
     return out, info
 
 
+def leg_loglik_reductions_obs(ts, G, A_table, pattern, v):
+    """``leg_loglik_reductions`` of a series whose rows observe different channels, still ONE launch
+    (cgps_leg_mahal_logdet_pair_obs): K = PEG precision(ts, G) + blockdiag(A_table[pattern[i]]).  A_table [P, d, d] with
+    1 <= P <= 256, pattern uint8 [N] on the device (a byte >= P takes the last entry), v [N, d].  No autograd graph."""
+    from . import _hip
+    n, d, dt = ts.shape[0], G.shape[0], G.dtype
+    if pattern.dtype != torch.uint8 or pattern.shape != (n,) or not pattern.is_cuda:
+        raise ValueError("pattern must be a uint8 device tensor of shape [%d], got %s %s" % (n, pattern.dtype, tuple(pattern.shape)))
+    if A_table.dim() != 3 or tuple(A_table.shape[1:]) != (d, d):
+        raise ValueError("A_table must be [P, %d, %d], got %s" % (d, d, tuple(A_table.shape)))
+    ts = ts.to(dt).contiguous()
+    G, A_table, pattern, v = G.contiguous(), A_table.to(dt).contiguous(), pattern.contiguous(), v.to(dt).contiguous()
+    ws = _hip.pair_workspace(n, d, dt, G.device)
+    out = torch.empty(4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_obs(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A_table), A_table.shape[0],
+                                                         _hip.ptr(pattern), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
+                                                         ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = info.tolist()
+        if bad[0] or bad[1]:
+            raise cr.NotPSDError("LEG system: a block near row %d is not positive definite (or a time gap has zero length)"
+                                 % ((bad[0] or bad[1]) - 1))
+    out = out.to(dt)
+    return out[0], out[1], out[3]
+
+
 def leg_loglik_batch_reductions(ts, G, A, v, q, plan):
     """The per-series reductions of a batch, no autograd graph: [B, 4] fp64 rows (v^T K^-1 v, log|K|, log|Sigma^-1|,
     sum q) and [B, 2] info words (cgps_leg_loglik_batch; series longer than BATCH_MAX_ROWS through
@@ -442,6 +469,102 @@ def log_likelihood_batch(m, ts, xs, lengths=None):
     return -0.5 * ((red[:, 3] - red[:, 0]) + (n * llt_det + red[:, 1] - red[:, 2]))
 
 
+# ---- missing observations ------------------------------------------------------------------------------------------
+# A row that observes the channels S only contributes B^T Li B to its diagonal block of the posterior precision, with
+# Li = (LLT[S, S])^-1 embedded in zeros (zero when S is empty); everything after the assembly -- factor, solve, selected
+# inverse, sampler -- is unchanged.  All 2^obs patterns form one small batched table; a row names its entry by the
+# code sum_c observed[i, c] 2^c, computed on the device: nothing here reads a device value on the host.
+MAX_PATTERN_OBS = 8
+
+_pattern_masks = {}
+
+
+def _pattern_mask_table(obs, dtype, device):
+    """[2^obs, obs]: row p holds the bits of p (bit c = channel c observed), built once per (obs, dtype, device)."""
+    key = (obs, dtype, device)
+    t = _pattern_masks.get(key)
+    if t is None:
+        codes = torch.arange(1 << obs, device=device)
+        t = _pattern_masks[key] = ((codes.unsqueeze(1) >> torch.arange(obs, device=device)) & 1).to(dtype)
+    return t
+
+
+def _observed_2d(observed, obs):
+    if not isinstance(observed, torch.Tensor) or observed.dtype != torch.bool:
+        raise ValueError("observed must be a bool tensor")
+    if observed.dim() == 1:
+        return observed.unsqueeze(-1).expand(-1, obs)
+    if observed.dim() != 2 or observed.shape[1] != obs:
+        raise ValueError("observed must be [n] or [n, %d] (one flag per row or per observed channel), got %s"
+                         % (obs, tuple(observed.shape)))
+    return observed
+
+
+def observation_tables(m, observed):
+    """What rows with missing observations need, for every pattern at once: ``(pattern, A_table, Li_table, c_table)``.
+
+    ``observed``: bool [n, obs_dim], or [n] for whole rows.  With M = diag(mask of pattern p), S its observed channels
+    and LLT = Lambda Lambda^T + 1e-9 I:  W = M LLT M + (I - M),  Li_table[p] = W^-1 - (I - M)  (= (LLT[S, S])^-1 embedded
+    in zeros),  A_table[p] = B^T Li_table[p] B,  c_table[p] = |S| log 2 pi + log|W|  (log|W| = log|LLT[S, S]|);
+    pattern[i] = sum_c observed[i, c] 2^c as uint8.  P = 2^obs_dim entries, obs_dim <= 8.  Batched torch ops,
+    differentiable in B and Lambda, nothing read on the host."""
+    obs = m.B.shape[0]
+    if obs > MAX_PATTERN_OBS:
+        raise ValueError("observation patterns are tabulated for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, obs))
+    observed = _observed_2d(observed, obs)
+    dt, dev = m.B.dtype, m.B.device
+    Mt = _pattern_mask_table(obs, dt, dev)
+    LLT = m.LLT
+    if obs == 1:                                        # a single output: no factorisation call, the scalar log
+        W = Mt * LLT[0, 0] + (1 - Mt)                   # [2, 1]
+        Li_table = (1.0 / W - (1 - Mt)).unsqueeze(-1)
+        logdet_W = torch.log(W[:, 0])
+    else:
+        unobs = torch.diag_embed(1 - Mt)
+        W = Mt.unsqueeze(2) * LLT * Mt.unsqueeze(1) + unobs
+        Li_table = torch.linalg.inv_ex(W)[0] - unobs    # the inverse's backward is matmul only (see LLT_inv); no host check
+        logdet_W = torch.logdet(W)
+    A_table = m.B.T @ Li_table @ m.B
+    c_table = Mt.sum(1) * math.log(2 * math.pi) + logdet_W
+    weights = 1 << torch.arange(obs, device=observed.device)
+    pattern = (observed * weights).sum(1).to(torch.uint8)
+    return pattern, A_table, Li_table, c_table
+
+
+def _observed_operands(m, ts, xs, observed):
+    """(pattern, row index into the tables, A_table, c_table, x~ Li per row, x~) with x~ = xs where observed, 0 elsewhere
+    (whatever the unobserved entries hold, NaN included)."""
+    if xs.dim() != 2 or xs.shape[1] != m.B.shape[0]:
+        raise ValueError("xs must be [n, %d], got %s" % (m.B.shape[0], tuple(xs.shape)))
+    observed = _observed_2d(observed, xs.shape[1])
+    if not (observed.shape[0] == xs.shape[0] == ts.shape[0]):
+        raise ValueError("observed has %d rows, xs has %d, ts has %d" % (observed.shape[0], xs.shape[0], ts.shape[0]))
+    pattern, A_table, Li_table, c_table = observation_tables(m, observed)
+    xz = torch.where(observed, xs, torch.zeros((), dtype=xs.dtype, device=xs.device))
+    idx = pattern.long()
+    xl = (xz.unsqueeze(1) @ Li_table[idx]).squeeze(1)           # x~^T Li(m_i): Li is symmetric
+    return pattern, idx, A_table, c_table, xl, xz
+
+
+def merge_targets(ts, xs, target_ts, check=True):
+    """Insert the times ``target_ts`` [k] into the series as wholly unobserved rows: ``(ts_all [n + k], xs_all
+    [n + k, obs], observed_all bool [n + k], target_index int64 [k])``, ts_all sorted (a stable sort on the device),
+    target_index[j] the row of target j.  With ``observed=observed_all``, ``insample_posterior`` and
+    ``sample_from_posterior`` then give posterior blocks, neighbouring cross-covariances and joint paths at times that
+    have no data.  A target at an observation time makes a zero-length gap: ``check=True`` reads one flag on the host
+    and raises ValueError; with ``check=False`` nothing is read (graph capture) and the singular gap surfaces as
+    NotPSDError or NaN like any other."""
+    n, k = ts.shape[0], target_ts.shape[0]
+    ts_all, perm = torch.sort(torch.cat([ts, target_ts.to(dtype=ts.dtype, device=ts.device)]), stable=True)
+    xs_all = torch.cat([xs, xs.new_zeros(k, xs.shape[1])])[perm]
+    observed_all = perm < n
+    where = torch.empty_like(perm)
+    where[perm] = torch.arange(n + k, device=perm.device)
+    if check and n + k > 1 and bool((ts_all[1:] == ts_all[:-1]).any()):
+        raise ValueError("a target time coincides with another time of the series (zero-length gap)")
+    return ts_all, xs_all, observed_all, where[n:]
+
+
 def posterior_precision(m, ts):
     Rs, Os = peg_precision(ts, m.G)
     BtLB = m.B.T @ m.LLT_inv @ m.B
@@ -452,11 +575,43 @@ def compute_v(m, xs):
     return (xs @ m.LLT_inv @ m.B).contiguous()
 
 
-def log_likelihood(m, ts, xs):
+def _posterior_system(m, ts, xs, observed):
+    """(K_Rs, K_Os, v) of the posterior N(K^-1 v, K^-1); with ``observed``, row i adds A(m_i) and v_i = B^T Li(m_i) x~_i."""
+    if observed is None:
+        return posterior_precision(m, ts) + (compute_v(m, xs),)
+    _, idx, A_table, _, xl, _ = _observed_operands(m, ts, xs, observed)
+    Rs, Os = peg_precision(ts, m.G)
+    return Rs + A_table[idx], Os, (xl @ m.B).contiguous()
+
+
+def _log_likelihood_observed(m, ts, xs, observed):
+    """``log_likelihood`` with a per-row observation pattern:  -1/2 [sum q_i - v^T K^-1 v + sum c(m_i) + log|K| -
+    log|Sigma^-1|],  K = PEG precision + blockdiag(A(m_i)),  v_i = B^T Li(m_i) x~_i,  q_i = x~_i^T Li(m_i) x~_i."""
+    pattern, idx, A_table, c_table, xl, xz = _observed_operands(m, ts, xs, observed)
+    v = (xl @ m.B).contiguous()
+    G = m.G
+    obs_terms = (xl * xz).sum() + c_table[idx].sum()
+    if fused_supported(ts, G) and not (torch.is_grad_enabled() and (A_table.requires_grad or v.requires_grad)):
+        k_mahal, k_det, sig_inv_det = leg_loglik_reductions_obs(ts, G, A_table, pattern, v)
+    else:
+        Rs, Os = peg_precision(ts, G)
+        _, sig_inv_det = cr.mahal_and_det(Rs, Os, torch.zeros_like(v))
+        k_mahal, k_det = cr.mahal_and_det(Rs=Rs + A_table[idx], Os=Os, x=v)
+    return -0.5 * ((obs_terms - k_mahal) + (k_det - sig_inv_det))
+
+
+def log_likelihood(m, ts, xs, observed=None):
     """log p(xs | ts) of the LEG model (models.py:301-372).  Differentiable in N, R, B, Lambda (through ``m``), xs and
     ts, for any subset of trainable parameters.  The fused reductions (no autograd graph) are taken only when none of
     ts, G, B^T (LL^T)^-1 B and v needs a gradient; otherwise the blocks go through ``peg_precision`` and
-    ``cr.mahal_and_det``."""
+    ``cr.mahal_and_det``.
+
+    ``observed`` (bool [n, obs_dim], or [n] for whole rows; None: everything): the density of the observed entries
+    alone.  Entries of xs that are not observed are ignored whatever they hold; a row that observes nothing is
+    marginalised out, i.e. the result is that of the series without it (``observation_tables``).  The same fused /
+    unfused choice (cgps_leg_mahal_logdet_pair_obs), the same gradients, and nothing read on the host."""
+    if observed is not None:
+        return _log_likelihood_observed(m, ts, xs, observed)
     LLT = m.LLT
     Li = m.inv_of(LLT)
     xl = xs @ Li
@@ -567,11 +722,11 @@ class GraphedValueAndGrad:
         return self.value, self.grads
 
 
-def insample_posterior(m, ts, xs):
+def insample_posterior(m, ts, xs, observed=None):
     """Posterior mean [N,d] and (diag, lower off-diag) covariance blocks (models.py:282-298).  The mean is
-    differentiable; the covariance blocks (``cr.inverse_blocks``) carry no autograd graph."""
-    K_Rs, K_Os = posterior_precision(m, ts)
-    v = compute_v(m, xs)
+    differentiable; the covariance blocks (``cr.inverse_blocks``) carry no autograd graph.  ``observed`` as in
+    ``log_likelihood``: the posterior is given at ALL rows, those that observe nothing included (``merge_targets``)."""
+    K_Rs, K_Os, v = _posterior_system(m, ts, xs, observed)
     if K_Rs.is_cuda and not (torch.is_grad_enabled() and (K_Rs.requires_grad or K_Os.requires_grad or v.requires_grad)):
         dec, mean = cr.decompose_solve(K_Rs, K_Os, v)      # factor and solve together (cgps_decompose_solve)
     else:
@@ -602,12 +757,13 @@ def sample_from_prior(m, ts, num_samples, seed):
         return z, sample_observations(m, z, seed)
 
 
-def sample_from_posterior(m, ts, xs, num_samples, seed):
+def sample_from_posterior(m, ts, xs, num_samples, seed, observed=None):
     """num_samples latent paths z [n, rank, S] from the posterior given xs at ts: factor and posterior mean together
-    (``cr.decompose_solve``), then ``cr.sample`` with that mean -- two library calls.  No autograd graph."""
+    (``cr.decompose_solve``), then ``cr.sample`` with that mean -- two library calls.  No autograd graph.  ``observed``
+    as in ``log_likelihood``: joint paths through every row, observed or not."""
     with torch.no_grad():
-        K_Rs, K_Os = posterior_precision(m, ts)
-        dec, mean = cr.decompose_solve(K_Rs, K_Os, compute_v(m, xs))
+        K_Rs, K_Os, v = _posterior_system(m, ts, xs, observed)
+        dec, mean = cr.decompose_solve(K_Rs, K_Os, v)
         return cr.sample(dec, num_samples, seed, mean=mean)
 
 

@@ -190,6 +190,18 @@ int cgps_leg_mahal_logdet(const void* ts, const void* G, const void* A, const vo
 int cgps_leg_mahal_logdet_pair(const void* ts, const void* G, const void* A, const void* v, int64_t N, int d, int dtype,
                                void* ws, size_t ws_bytes, double* out4, int* info2, void* stream);
 
+/* cgps_leg_mahal_logdet_pair for a series whose rows do not all observe the same channels (or anything at all):
+ * row i adds entry pattern[i] of a table of diagonal terms instead of the one A,
+ *   K = PEG precision(ts, G) + blockdiag(A_table[pattern[i]]).
+ * A_table[P][d][d], 1 <= P <= 256 (an all-zero entry for a row that observes nothing); pattern[N]: DEVICE bytes, a
+ * byte >= P reads entry P - 1 (no byte value reads outside the table); v[N][d] (NULL: zeros) is the caller's
+ * right-hand side, built with the same per-row pattern.  The prior-precision half (out4[2..3]) adds nothing and reads
+ * no pattern.  out4, info2, workspace and error codes: those of cgps_leg_mahal_logdet_pair; null pointers and P
+ * outside 1..256 are CGPS_ERR_ARG before anything is launched. */
+int cgps_leg_mahal_logdet_pair_obs(const void* ts, const void* G, const void* A_table, int P,
+                                   const unsigned char* pattern, const void* v, int64_t N, int d, int dtype,
+                                   void* ws, size_t ws_bytes, double* out4, int* info2, void* stream);
+
 /* Adjoint of cgps_peg_precision in G and in the time gaps (training through the assembly; what
  * autograd computes through models.py:181-239 for LEGFamily.training_step, models.py:374-381).
  * gRs[N][d][d], gOs[N-1][d][d]: d loss / d Rs, d loss / d Os.  One lane per time gap, 64 gaps per
