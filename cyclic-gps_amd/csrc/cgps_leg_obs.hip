@@ -1,8 +1,10 @@
 // cgps_leg_obs.hip -- the fused LEG reductions for series with missing observations: every row names the entry of
-// a table of diagonal terms it adds (chunk_reduce_kernel<.., SRC = 2>, cgps_tile.h).  A translation unit of its own:
-// these are the heaviest stage-1 instantiations of the library and compile next to cgps_mahal.hip, not after it.
+// a table of diagonal terms it adds (chunk_reduce_kernel<.., SRC = 2>, cgps_tile.h; for many series in one launch
+// leg_batch_kernel<.., OBS = true>, cgps_tile_leg_batch.h).  A translation unit of its own: these are the heaviest
+// stage-1 instantiations of the library and compile next to cgps_mahal.hip, not after it.
 #include "cgps_host.h"
 #include "cgps_tile.h"
+#include "cgps_tile_leg_batch.h"
 
 using namespace cgps_host;
 
@@ -26,6 +28,24 @@ int cgps_leg_mahal_logdet_pair_obs(const void* ts, const void* G, const void* A_
     if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_obs (that of cgps_leg_mahal_logdet_pair)");
     if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_mahal_logdet_pair_obs: not built for this block size (d = 8, fp64 d = 6) or CGPS_NO_FOLD=1");
     return check_launch("LEG tile reduction (pair, per-row observation pattern)");
+  });
+}
+
+int cgps_leg_loglik_batch_obs(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* A_table, int P,
+                              const unsigned char* pattern, const void* v, const void* q, int d, int dtype, int64_t max_rows,
+                              double* out4, int* info2, void* stream) {
+  if (B < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !A_table || !pattern || !out4 || !info2)))
+    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_obs: null pointer or B < 0");
+  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_obs: B = %lld series, at most 2^31 - 1", (long long)B);
+  if (P < 1 || P > 256) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_obs: P = %d table entries, outside 1..256", P);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int rc = cgps::run_leg_batch_obs<T, D>((const T*)ts, offsets, B, (const T*)G, (const T*)A_table, P, pattern,
+                                                 (const T*)v, (const T*)q, max_rows, out4, info2, (hipStream_t)stream);
+    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch_obs: not built for this block size (d = 8, fp64 d = 6)");
+    if (B == 0) return (int)CGPS_OK;
+    return check_launch("LEG batched reduction (per-row observation pattern)");
   });
 }
 

@@ -1,6 +1,7 @@
-// Batched LEG log-likelihood reductions: many independent series in ONE launch (cgps_leg_loglik_batch).
-// Included from cgps_mahal.hip after cgps_tile.h (the chunk walk, the in-LDS reduction and the in-register
-// assembly of cgps_tile_leg.h are reused as they are).
+// Batched LEG log-likelihood reductions: many independent series in ONE launch (cgps_leg_loglik_batch, and
+// cgps_leg_loglik_batch_obs for rows that differ in what they observe).
+// Included from cgps_mahal.hip and from cgps_leg_obs.hip, after cgps_tile.h (the chunk walk, the in-LDS reduction and
+// the in-register assembly of cgps_tile_leg.h are reused as they are).
 //
 // Series b is rows [offsets[b], offsets[b+1]) of the concatenated ts / v / q.  Its two systems
 //     K_b = PEG precision(ts_b, G) + blockdiag(A)        (posterior precision, right-hand side v_b)
@@ -18,6 +19,14 @@
 // out4[b] = {v^T K^-1 v, log|K|, log|S|, sum of q}; info2[2b] / info2[2b+1]: 0 or 1 + a local row near a block of
 // K_b / S_b that was not positive definite (a zero-length gap included); a failed system's entries are NaN.
 // A series with more than max_rows rows is skipped (nothing written: the caller reduces it with another call).
+//
+// OBS = true (cgps_leg_loglik_batch_obs): rows differ in what they observe.  Ag is then a table of `entries` blocks and
+// row r of series b adds entry pattern[offsets[b] + r] of it (leg_obs_block in cgps_tile_leg.h: the index is clamped,
+// the block is read with per-lane vector loads straight from global memory -- at most 256 blocks, they stay in cache);
+// `pattern` holds one byte per row of the CONCATENATED batch.  The prior-precision workgroup has a null table and reads
+// neither table nor pattern.  OBS = false reads neither argument, and every difference is an `if constexpr`: its
+// instruction stream is the one it had before the flag existed.  The OBS = true kernels are instantiated by the
+// translation unit that calls run_leg_batch_obs (cgps_leg_obs.hip).
 #pragma once
 
 namespace cgps {
@@ -27,12 +36,13 @@ constexpr int LEG_BATCH_THREADS = 256;
 template <typename T, int D>
 constexpr int leg_batch_lanes() { return TileCfg<T, D>::NG1; }       // 256, or 128 for 7 x 7 fp64 (LDS)
 
-template <typename T, int D, int NT, int NW>
+template <typename T, int D, int NT, int NW, bool OBS = false>
 __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ ts, const int64_t* __restrict__ offsets,
                                                           const T* __restrict__ Gg, const T* __restrict__ Ag,
                                                           const T* __restrict__ vg, const T* __restrict__ qg,
                                                           int64_t max_rows, double* __restrict__ out4,
-                                                          int* __restrict__ info2) {
+                                                          int* __restrict__ info2, int entries,
+                                                          const unsigned char* __restrict__ pattern) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   StageSmem<T, D, NT, NW> sm(smem);
   const int tid = threadIdx.x;
@@ -44,6 +54,7 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
   const T* __restrict__ tsb = ts + off;
   const T* __restrict__ vb = (prior || vg == nullptr) ? nullptr : vg + off * D;
   const T* __restrict__ Ab = prior ? nullptr : Ag;
+  const unsigned char* __restrict__ pb = OBS ? pattern + off : nullptr;       // the series' own bytes: local row + offset
   if (tid == 0) *sm.sfail = 0x7fffffff;
 
   const int64_t C = (n + NT - 1) / NT;                         // rows per lane
@@ -68,12 +79,18 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
       set_zero<T, D>(cR);
       set_zero<T, D>(cB);
     }
-    leg_row<T, D>(tsb, Gg, Ab, vb, r0, n, cR, cB, Rc, Cc, yc, fail);
+    if constexpr (OBS)
+      leg_row<T, D>(tsb, Gg, leg_obs_block<T, D>(Ab, pb, entries, r0), vb, r0, n, cR, cB, Rc, Cc, yc, fail);
+    else
+      leg_row<T, D>(tsb, Gg, Ab, vb, r0, n, cR, cB, Rc, Cc, yc, fail);
   }
 #pragma unroll 1
   for (int j = 0; j < L - 1; ++j) {
     T Rn[D][D], On[D][D], yn[D];
-    leg_row<T, D>(tsb, Gg, Ab, vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
+    if constexpr (OBS)
+      leg_row<T, D>(tsb, Gg, leg_obs_block<T, D>(Ab, pb, entries, r0 + j + 1), vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
+    else
+      leg_row<T, D>(tsb, Gg, Ab, vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
     eliminate_forward<T, D>(Rc, yc, Cc, dRa, dya, On, Rn, yn, pl, mah, fail);
   }
   const bool fail_stream = fail;
@@ -142,7 +159,32 @@ int run_leg_batch(const T* ts, const int64_t* offsets, int64_t B, const T* G, co
     });
     if (B == 0) return 0;
     hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets, G, A, v, q,
-                       max_rows, out4, info2);
+                       max_rows, out4, info2, 0, (const unsigned char*)nullptr);
+    return 0;
+  }
+}
+
+// the per-row pattern form (OBS = true); entries in 1..256 and the non-null table and pattern are the caller's checks
+template <typename T, int D>
+int run_leg_batch_obs(const T* ts, const int64_t* offsets, int64_t B, const T* G, const T* table, int entries,
+                      const unsigned char* pattern, const T* v, const T* q, int64_t max_rows, double* out4, int* info2,
+                      hipStream_t st) {
+  if constexpr (!leg_batch_supported<T, D>()) {
+    return -2;
+  } else {
+    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
+    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
+    const size_t lds = leg_batch_lds_bytes<T, D>();
+    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
+    std::call_once(once[dev], [lds] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, true>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets, G, table,
+                       v, q, max_rows, out4, info2, entries, pattern);
     return 0;
   }
 }

@@ -278,6 +278,41 @@ class _BatchPlan:
         return g.repeat_interleave(self.lens, output_size=self.R)
 
 
+PLAN_CACHE_SIZE = 8
+_plans = {}                 # (lengths, device) -> plan, least recently used first
+_captured_plans = {}        # plans that a stream capture has read: never dropped
+
+
+def _capturing(device):
+    return torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+
+def _cached_batch_plan(lengths, device):
+    """The plan of these lengths, built once: a repeated call -- a training loop over one data set, a graph capture
+    after its warm-up -- then copies nothing from the host.  The PLAN_CACHE_SIZE most recently used plans are kept.
+    A plan handed out while the current stream is being captured is kept for as long as the process lives: the
+    captured kernels hold the addresses of its device tensors and nothing else would own them, whoever made the
+    capture and whatever they kept of its results.  A capture cannot build a plan (that is a copy from the host):
+    RuntimeError unless an ordinary call with the same lengths came first, as ``Graphed``'s warm-up is."""
+    key = (tuple(lengths), str(device))
+    plan = _captured_plans.get(key)
+    if plan is not None:
+        return plan
+    plan = _plans.pop(key, None)                                 # (put back below, as the most recent)
+    if _capturing(device):
+        if plan is None:
+            raise RuntimeError("log_likelihood_batch(observed=) inside a graph capture needs one ordinary call with "
+                               "the same lengths before the capture (leg.Graphed's warm-up is one)")
+        _captured_plans[key] = plan
+        return plan
+    if plan is None:
+        plan = _BatchPlan(lengths, device)
+        while len(_plans) >= PLAN_CACHE_SIZE:
+            _plans.pop(next(iter(_plans)))
+    _plans[key] = plan
+    return plan
+
+
 def _leg_pair_raw(ts, G, A, v):
     """cgps_leg_mahal_logdet_pair of one series: (out4 fp64, info2), nothing read on the host."""
     from . import _hip
@@ -331,6 +366,48 @@ def leg_loglik_batch_reductions(ts, G, A, v, q, plan):
     for b in plan.long:
         s, e = plan.starts[b], plan.starts[b + 1]
         o4, i2 = _leg_pair_raw(ts[s:e], G, A, v[s:e])
+        out[b, :3] = o4[[0, 1, 3]]
+        out[b, 3] = q[s:e].to(torch.float64).sum()
+        info[b] = i2
+    return out, info
+
+
+def _leg_pair_obs_raw(ts, G, A_table, pattern, v):
+    """cgps_leg_mahal_logdet_pair_obs of one series: (out4 fp64, info2), nothing read on the host."""
+    from . import _hip
+    n, d, dt = ts.shape[0], G.shape[0], G.dtype
+    ws = _hip.pair_workspace(n, d, dt, G.device)
+    out = torch.empty(4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_obs(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A_table), A_table.shape[0],
+                                                         _hip.ptr(pattern), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
+                                                         ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    return out, info
+
+
+def leg_loglik_batch_reductions_obs(ts, G, A_table, pattern, v, q, plan):
+    """``leg_loglik_batch_reductions`` of series whose rows observe different channels, still ONE launch
+    (cgps_leg_loglik_batch_obs): K_b = PEG precision(ts_b, G) + blockdiag(A_table[pattern[i]]) over the series' rows.
+    A_table [P, d, d] with 1 <= P <= 256, pattern uint8 [R] on the device, one byte per row of the concatenated batch
+    (a byte >= P takes the last entry); series longer than BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_obs with
+    their slice of the pattern.  ts, A_table, v, q in G's dtype, contiguous.  No autograd graph."""
+    from . import _hip
+    d, dt = G.shape[0], G.dtype
+    if pattern.dtype != torch.uint8 or pattern.shape != (plan.R,) or not pattern.is_cuda:
+        raise ValueError("pattern must be a uint8 device tensor of shape [%d], got %s %s"
+                         % (plan.R, pattern.dtype, tuple(pattern.shape)))
+    if A_table.dim() != 3 or tuple(A_table.shape[1:]) != (d, d):
+        raise ValueError("A_table must be [P, %d, %d], got %s" % (d, d, tuple(A_table.shape)))
+    pattern = pattern.contiguous()
+    out = torch.empty(plan.B, 4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(plan.B, 2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_loglik_batch_obs(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, _hip.ptr(G),
+                                                    _hip.ptr(A_table), A_table.shape[0], _hip.ptr(pattern), _hip.ptr(v),
+                                                    _hip.ptr(q), d, _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out),
+                                                    _hip.ptr(info), _hip.stream_ptr()))
+    for b in plan.long:
+        s, e = plan.starts[b], plan.starts[b + 1]
+        o4, i2 = _leg_pair_obs_raw(ts[s:e], G, A_table, pattern[s:e], v[s:e])
         out[b, :3] = o4[[0, 1, 3]]
         out[b, 3] = q[s:e].to(torch.float64).sum()
         info[b] = i2
@@ -424,19 +501,92 @@ class _LegBatchFn(torch.autograd.Function):
         return gts, gG, gA, gv, gq, None
 
 
-def _log_likelihood_per_series(m, ts, xs, lengths):
+class _LegBatchObsFn(torch.autograd.Function):
+    """``_LegBatchFn`` with a per-row observation pattern.  Forward: cgps_leg_loglik_batch_obs (one launch).  Backward:
+    the same concatenated, decoupled system with Rs + A_table[idx] as K's diagonal; the gradient of A_table is the
+    per-pattern sum of the rows' block gradients, taken as a matrix product with the one-hot matrix of the pattern
+    (no scatter: ``index_add_`` on the GPU adds with atomics, in no fixed order)."""
+
+    @staticmethod
+    def forward(ctx, ts, G, A_table, v, q, pattern, plan):
+        ctx.plan = plan
+        ctx.save_for_backward(ts, G, A_table, v, pattern)
+        out, info = leg_loglik_batch_reductions_obs(ts.detach(), G.detach(), A_table.detach(), pattern, v.detach(),
+                                                    q.detach(), plan)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            _raise_batch_not_pd(info)
+        return out.to(G.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        ts, G, A_table, v, pattern = ctx.saved_tensors
+        plan = ctx.plan
+        need_ts, need_G, need_A, need_v, need_q = ctx.needs_input_grad[:5]
+        gts = gG = gA = gv = gq = None
+        gout = gout.to(G.dtype)
+        if need_q:
+            gq = plan.per_row(gout[:, 3])
+        if need_ts or need_G or need_A or need_v:
+            P, d = A_table.shape[0], G.shape[0]
+            idx = pattern.long().clamp(max=P - 1)                # the kernel's clamp
+            Rs, Os = _peg_precision_seg(ts, G, plan.cut)
+            gm, gl = plan.per_row(gout[:, 0]), plan.per_row(gout[:, 1])
+            dec, w = cr.decompose_solve(Rs + A_table[idx], Os, v)
+            if need_v:
+                gv = 2 * gm.unsqueeze(-1) * w
+            if need_ts or need_G or need_A:
+                Sd, So = cr.inverse_blocks(dec)
+                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
+                if need_A:
+                    codes = torch.arange(P, device=idx.device).unsqueeze(1)
+                    step = max(1024, (1 << 24) // P)             # rows per product: the one-hot matrix stays small
+                    gA = torch.zeros(P, d * d, dtype=G.dtype, device=G.device)
+                    for s in range(0, plan.R, step):             # (one product unless P * R > 2^24)
+                        gA = gA + (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype) @ gR[s:s + step].reshape(-1, d * d)
+                    gA = gA.reshape(P, d, d)
+                if need_ts or need_G:
+                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
+                    if plan.R > 1:           # (one row: its block is I whatever G and ts are)
+                        gs = plan.per_row(gout[:, 2])
+                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
+                        gR = gR + gs.view(-1, 1, 1) * Sd0
+                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
+                    gG, gts = _peg_precision_adjoint_seg(ts, G, plan.cut, gR, gO, need_ts)
+                    if not need_G:
+                        gG = None
+        return gts, gG, gA, gv, gq, None, None
+
+
+def _log_likelihood_per_series(m, ts, xs, lengths, observed=None):
     """One ``log_likelihood`` per series: d = 8, fp64 d = 6 and CPU tensors (no batched kernel there)."""
     outs, s = [], 0
     for b, n in enumerate(lengths):
         try:
-            outs.append(log_likelihood(m, ts[s:s + n], xs[s:s + n]))
+            outs.append(log_likelihood(m, ts[s:s + n], xs[s:s + n], None if observed is None else observed[s:s + n]))
         except cr.NotPSDError as e:
             raise cr.NotPSDError("LEG batch: series %d: %s" % (b, e)) from None
         s += n
     return torch.stack(outs)
 
 
-def log_likelihood_batch(m, ts, xs, lengths=None):
+def _batch_observed(observed, xs_shape, dense):
+    """``observed`` in the layout of the batch's xs, flattened to the rows of the concatenated batch ([R, obs] or [R]);
+    raises ValueError before anything is launched."""
+    if not isinstance(observed, torch.Tensor) or observed.dtype != torch.bool:
+        raise ValueError("observed must be a bool tensor")
+    xs_shape = tuple(xs_shape)
+    if dense:
+        if tuple(observed.shape) not in (xs_shape, xs_shape[:2]):
+            raise ValueError("dense layout wants observed[B, n, obs_dim] or observed[B, n] like xs %s, got %s"
+                             % (xs_shape, tuple(observed.shape)))
+        return observed.reshape((xs_shape[0] * xs_shape[1],) + tuple(observed.shape[2:]))
+    if tuple(observed.shape) not in (xs_shape, xs_shape[:1]):
+        raise ValueError("ragged layout wants observed[sum(lengths), obs_dim] or observed[sum(lengths)] like xs %s, got %s"
+                         % (xs_shape, tuple(observed.shape)))
+    return observed
+
+
+def log_likelihood_batch(m, ts, xs, lengths=None, observed=None):
     """log p(xs_b | ts_b) of the LEG model for B independent series (models.py:301-372 for each), as a [B] tensor of
     the model's dtype; ``out.sum()`` is what a training step over the batch minimises.
 
@@ -448,14 +598,37 @@ def log_likelihood_batch(m, ts, xs, lengths=None):
     BATCH_MAX_ROWS rows (cgps_leg_loglik_batch) and a backward through the concatenated, decoupled system;
     d = 8, fp64 d = 6 and CPU tensors take one ``log_likelihood`` per series.  With
     ``cr.CHECK_POSITIVE_DEFINITE`` a series that is not positive definite raises ``NotPSDError`` naming it; without
-    it its slot is NaN and no other slot is affected."""
+    it its slot is NaN and no other slot is affected.
+
+    ``observed`` (bool, in the layout of xs: [B, n, obs_dim] or [B, n] for whole rows; ragged [sum(lengths), obs_dim]
+    or [sum(lengths)]; None: everything, and exactly the calls above): every slot is the density of that series'
+    observed entries alone, as ``log_likelihood(..., observed=)`` gives it.  Entries of xs that are not observed are
+    ignored whatever they hold (NaN included); a row that observes nothing is marginalised out exactly, so a dense
+    batch of series of unequal true length is the mask whose tail rows are False (the padded time stamps must still
+    increase); a series that observes nothing at all has log-likelihood 0.  Still one launch
+    (cgps_leg_loglik_batch_obs; ``observation_tables`` for the operands), the same gradients, the same fallbacks and
+    errors, and nothing read on the host when ``cr.CHECK_POSITIVE_DEFINITE`` is off."""
+    dense = lengths is None
+    xs_shape = xs.shape
     ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    if observed is not None:
+        observed = _batch_observed(observed, xs_shape, dense)
+        if xs.shape[1] != m.B.shape[0]:
+            raise ValueError("xs must have %d channels, got %s" % (m.B.shape[0], tuple(xs_shape)))
+        observed = _observed_2d(observed, xs.shape[1])
     G = m.G
     dt = G.dtype
     if not lengths:
         return torch.empty(0, dtype=dt, device=ts.device)
     if not batch_supported(ts, G):
-        return _log_likelihood_per_series(m, ts, xs, lengths)
+        return _log_likelihood_per_series(m, ts, xs, lengths, observed)
+    if observed is not None:
+        plan = _cached_batch_plan(lengths, G.device)
+        pattern, idx, A_table, c_table, xl, xz = _observed_operands(m, ts, xs, observed)
+        v = (xl @ m.B).to(dt).contiguous()
+        q = ((xl * xz).sum(-1) + c_table[idx]).to(dt).contiguous()       # the observation constant rides in sum q
+        red = _LegBatchObsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A_table.to(dt).contiguous(), v, q, pattern, plan)
+        return -0.5 * ((red[:, 3] - red[:, 0]) + (red[:, 1] - red[:, 2]))
     plan = _BatchPlan(lengths, G.device)
     LLT = m.LLT
     Li = m.inv_of(LLT)

@@ -228,6 +228,20 @@ int cgps_leg_loglik_batch(const void* ts, const int64_t* offsets, int64_t B, con
                           const void* v, const void* q, int d, int dtype, int64_t max_rows, double* out4,
                           int* info2, void* stream);
 
+/* cgps_leg_loglik_batch for series whose rows do not all observe the same channels (or anything at all: padding,
+ * held-out windows): row i of the CONCATENATED batch adds entry pattern[i] of a table of diagonal terms instead of
+ * the one A,
+ *   K_b = PEG precision(ts_b, G) + blockdiag(A_table[pattern[offsets[b] + r]]),  r = 0 .. n_b - 1.
+ * A_table[P][d][d], 1 <= P <= 256 (an all-zero entry for a row that observes nothing); pattern[sum n_b]: DEVICE bytes,
+ * a byte >= P reads entry P - 1 (no byte value reads outside the table); v and q are the caller's, built with the same
+ * per-row pattern (q carries the rows' observation constants).  The prior-precision system (out4[b][2]) adds nothing,
+ * reads neither table nor pattern, and its value is that of cgps_leg_loglik_batch bit for bit.  out4, info2, max_rows
+ * and error codes: those of cgps_leg_loglik_batch; a null A_table or pattern with B > 0 and P outside 1..256 are
+ * CGPS_ERR_ARG before anything is launched; B = 0 returns CGPS_OK.  No workspace. */
+int cgps_leg_loglik_batch_obs(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* A_table,
+                              int P, const unsigned char* pattern, const void* v, const void* q, int d, int dtype,
+                              int64_t max_rows, double* out4, int* info2, void* stream);
+
 /* cgps_peg_precision of several series concatenated (models.py:181-239 for each): cut[N-1] (device bytes),
  * cut[g] != 0 when rows g and g+1 belong to different series.  Such a gap is never evaluated, its coupling
  * block Os[g] is 0 and it adds nothing to Rs[g] or Rs[g+1]: the blocks of a block-diagonal system of

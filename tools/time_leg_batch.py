@@ -6,6 +6,13 @@ backward of out.sum() with all four matrices trainable, for B in --batches.
 
     python tools/time_leg_batch.py [--batches 1,64,1024] [--reps 20] [--loop-reps 3] [--json out.json]
     python tools/time_leg_batch.py --profile-only --batches 1024     (forward calls only, for rocprofv3 --kernel-trace --stats)
+    python tools/time_leg_batch.py --observed 0.7 [--batches 1,64,1024]
+        every entry observed with probability 0.7 (another mask per series): log_likelihood_batch(observed=mask) against
+        a Python loop of log_likelihood(observed=) and against the fully observed log_likelihood_batch on the same shapes
+        (the batched calls alternate inside every repetition).  The masked call keeps its plan (device offsets, the
+        series-cut mask: about R bytes from the host) between calls, the fully observed call builds it every time;
+        *_obs_us is the call as users get it, *_obs_cold_us the call with the plan cache emptied first, so that both
+        sides build a plan, and *_ratio_to_full is taken from the latter
 """
 import argparse
 import json
@@ -46,8 +53,91 @@ def timed(fn, reps, warmup):
     return float(np.median(times)), float(min(times))
 
 
+def timed_alternating(fns, reps, warmup):
+    """The same for several variants, alternated inside every repetition (other work shares the machine: a drift then
+    hits all of them alike): name -> (median, min) in microseconds."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[k].append(a.elapsed_time(b) * 1e3)
+    return {k: (float(np.median(v)), float(min(v))) for k, v in times.items()}
+
+
 def trainable(m):
     return leg.LEGMatrices(*(t.clone().requires_grad_(True) for t in (m.N, m.R, m.B, m.Lambda)))
+
+
+def observed_row(m, ts, xs, fraction, reps, loop_reps):
+    """The masked batch against its two baselines, forward only and forward + backward."""
+    B = ts.shape[0]
+    obs = torch.rand(xs.shape, generator=torch.Generator().manual_seed(B)) < fraction
+    obs = obs.cuda()
+    with torch.no_grad():
+        ref = torch.stack([leg.log_likelihood(m, ts[b], xs[b], observed=obs[b]) for b in range(B)])
+        out = leg.log_likelihood_batch(m, ts, xs, observed=obs)
+    err = float(((out - ref).abs() / ref.abs().clamp_min(1.0)).max())
+    assert err < 1e-9, err
+    mg = trainable(m)
+
+    def zero():
+        for p in (mg.N, mg.R, mg.B, mg.Lambda):
+            p.grad = None
+
+    def fwd_obs():
+        with torch.no_grad():
+            leg.log_likelihood_batch(m, ts, xs, observed=obs)
+
+    def fwd_obs_cold():
+        leg._plans.clear()
+        fwd_obs()
+
+    def fwd_full():
+        with torch.no_grad():
+            leg.log_likelihood_batch(m, ts, xs)
+
+    def fwd_loop():
+        with torch.no_grad():
+            for b in range(B):
+                leg.log_likelihood(m, ts[b], xs[b], observed=obs[b])
+
+    def fb_obs():
+        zero()
+        leg.log_likelihood_batch(mg, ts, xs, observed=obs).sum().backward()
+
+    def fb_obs_cold():
+        leg._plans.clear()
+        fb_obs()
+
+    def fb_full():
+        zero()
+        leg.log_likelihood_batch(mg, ts, xs).sum().backward()
+
+    def fb_loop():
+        zero()
+        for b in range(B):
+            leg.log_likelihood(mg, ts[b], xs[b], observed=obs[b]).backward()
+
+    row = {"B": B, "rows": ts.shape[1], "d": 5, "dtype": "float64", "observed": fraction, "max_rel_err_vs_loop": err}
+    got = timed_alternating({"fwd_obs": fwd_obs, "fwd_obs_cold": fwd_obs_cold, "fwd_full": fwd_full}, reps, 3)
+    got.update(timed_alternating({"fwdbwd_obs": fb_obs, "fwdbwd_obs_cold": fb_obs_cold, "fwdbwd_full": fb_full}, reps, 3))
+    got["fwd_loop"] = timed(fwd_loop, loop_reps, 1)
+    got["fwdbwd_loop"] = timed(fb_loop, loop_reps, 1)
+    for name, (med, low) in got.items():
+        row[name + "_us"], row[name + "_min_us"] = med, low
+    for k in ("fwd", "fwdbwd"):
+        row[k + "_speedup_vs_loop"] = row[k + "_loop_us"] / row[k + "_obs_us"]
+        row[k + "_ratio_to_full"] = row[k + "_obs_cold_us"] / row[k + "_full_us"]      # a plan built on both sides
+        row[k + "_cached_ratio_to_full"] = row[k + "_obs_us"] / row[k + "_full_us"]
+    return row
 
 
 def main():
@@ -57,10 +147,16 @@ def main():
     ap.add_argument("--loop-reps", type=int, default=3)
     ap.add_argument("--json", default=None)
     ap.add_argument("--profile-only", action="store_true")
+    ap.add_argument("--observed", type=float, default=None, metavar="FRACTION")
     a = ap.parse_args()
     res = []
     for B in [int(x) for x in a.batches.split(",")]:
         m, ts, xs = workload(B)
+        if a.observed is not None:
+            row = observed_row(m, ts, xs, a.observed, a.reps, a.loop_reps if B > 64 else a.reps)
+            print(json.dumps(row), flush=True)
+            res.append(row)
+            continue
         if a.profile_only:
             with torch.no_grad():
                 for _ in range(a.reps):
