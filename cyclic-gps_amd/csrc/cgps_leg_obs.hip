@@ -1,7 +1,9 @@
-// cgps_leg_obs.hip -- the fused LEG reductions for series with missing observations: every row names the entry of
-// a table of diagonal terms it adds (chunk_reduce_kernel<.., SRC = 2>, cgps_tile.h; for many series in one launch
-// leg_batch_kernel<.., OBS = true>, cgps_tile_leg_batch.h).  A translation unit of its own: these are the heaviest
-// stage-1 instantiations of the library and compile next to cgps_mahal.hip, not after it.
+// cgps_leg_obs.hip -- the fused LEG reductions for series whose rows differ in their observation model.  Missing
+// observations: every row names the entry of a table of diagonal terms it adds (chunk_reduce_kernel<.., SRC = 2>,
+// cgps_tile.h; for many series in one launch leg_batch_kernel<.., OBS = true>, cgps_tile_leg_batch.h).  Noise variances
+// of their own: every row adds a weighted sum of a basis shared by all rows (chunk_reduce_kernel<.., SRC = 3>).
+// A translation unit of its own: these are the heaviest stage-1 instantiations of the library and compile next to
+// cgps_mahal.hip, not after it.
 #include "cgps_host.h"
 #include "cgps_tile.h"
 #include "cgps_tile_leg_batch.h"
@@ -28,6 +30,22 @@ int cgps_leg_mahal_logdet_pair_obs(const void* ts, const void* G, const void* A_
     if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_obs (that of cgps_leg_mahal_logdet_pair)");
     if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_mahal_logdet_pair_obs: not built for this block size (d = 8, fp64 d = 6) or CGPS_NO_FOLD=1");
     return check_launch("LEG tile reduction (pair, per-row observation pattern)");
+  });
+}
+
+int cgps_leg_mahal_logdet_pair_w(const void* ts, const void* G, const void* basis, int Kb, const void* weights, const void* v,
+                                 int64_t N, int d, int dtype, void* ws, size_t ws_bytes, double* out4, int* info2, void* stream) {
+  if (bad_common(N, d) || !ts || !G || !basis || !weights || !ws || !out4 || !info2)
+    return fail(CGPS_ERR_ARG, "cgps_leg_mahal_logdet_pair_w: null pointer or N < 1");
+  if (Kb < 1 || Kb > 64) return fail(CGPS_ERR_ARG, "cgps_leg_mahal_logdet_pair_w: Kb = %d basis blocks, outside 1..64", Kb);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int rc = cgps::run_tile_leg<T, D, 3>((const T*)ts, (const T*)G, (const T*)basis, (const T*)v, N, (char*)ws, ws_bytes,
+                                               out4, info2, (hipStream_t)stream, true, (const unsigned char*)weights, Kb);
+    if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_w (that of cgps_leg_mahal_logdet_pair)");
+    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_mahal_logdet_pair_w: not built for this block size (d = 8, fp64 d = 6) or CGPS_NO_FOLD=1");
+    return check_launch("LEG tile reduction (pair, per-row weighted basis)");
   });
 }
 

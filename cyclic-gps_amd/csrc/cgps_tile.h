@@ -718,7 +718,7 @@ struct FoldArgs {
   int pair_slot;                   // SRC >= 1, gridDim.y = 2: counters and workspace offset (bytes) of the second system
   size_t pair_ws_stride;
   const unsigned char* obs_pattern; // SRC = 2: [N] table entry of each row's diagonal term, and the table's length
-  int obs_entries;
+  int obs_entries;                 // (SRC = 3 reads the same two fields as its weights [N][Kb], of type T, and Kb)
 };
 template <typename T, int D, int NTILE, int NT, bool FINAL, bool INL = false>
 __device__ __forceinline__ void record_reduce_body(char* smem, unsigned tile_index, const T* __restrict__ rin, int64_t n,
@@ -813,6 +813,9 @@ __device__ __forceinline__ void fold_record_stages(char* smem, int* last_flag, T
 // generator G [d][d], Oleft = the block A added to every diagonal block (or nullptr), yg = right-hand side (or nullptr).
 // SRC = 2: the same, but Oleft = a table of fold.obs_entries blocks and row r adds entry fold.obs_pattern[r] of it
 // (rows that observe different channels, or nothing: leg_obs_block in cgps_tile_leg.h).  Nothing else differs.
+// SRC = 3: the same as SRC = 1, but Oleft = a basis of Kb = fold.obs_entries blocks and row r adds their sum weighted
+// by the Kb values of T at fold.obs_pattern + r Kb sizeof(T) (rows with noise of their own: leg_add_weighted_basis in
+// cgps_tile_leg.h).  Nothing else differs.
 template <typename T, int D, int CT, int NT, int NW = NT, bool FOLD = false, int SRC = 0>
 __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void chunk_reduce_kernel(const T* __restrict__ Rg, const T* __restrict__ Og,
                                                           const T* __restrict__ yg, int64_t N,
@@ -894,7 +897,10 @@ __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void 
       }
       if constexpr (SRC == 2)
         leg_row<T, D>(Rg, Og, leg_obs_block<T, D>(Oleft, fold.obs_pattern, fold.obs_entries, r0), yg, r0, N, cR, cB, Rc, Cc, yc, fail);
-      else
+      else if constexpr (SRC == 3) {
+        leg_add_weighted_basis<T, D>(Oleft, reinterpret_cast<const T*>(fold.obs_pattern), fold.obs_entries, r0, cR);
+        leg_row<T, D>(Rg, Og, (const T*)nullptr, yg, r0, N, cR, cB, Rc, Cc, yc, fail);
+      } else
         leg_row<T, D>(Rg, Og, Oleft, yg, r0, N, cR, cB, Rc, Cc, yc, fail);
     }
   } else
@@ -961,7 +967,10 @@ __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void 
     if constexpr (SRC >= 1) {
       if constexpr (SRC == 2)
         leg_row<T, D>(Rg, Og, leg_obs_block<T, D>(Oleft, fold.obs_pattern, fold.obs_entries, rn), yg, rn, N, cR, cB, Rn, On, yn, fail);
-      else
+      else if constexpr (SRC == 3) {
+        leg_add_weighted_basis<T, D>(Oleft, reinterpret_cast<const T*>(fold.obs_pattern), fold.obs_entries, rn, cR);
+        leg_row<T, D>(Rg, Og, (const T*)nullptr, yg, rn, N, cR, cB, Rn, On, yn, fail);
+      } else
         leg_row<T, D>(Rg, Og, Oleft, yg, rn, N, cR, cB, Rn, On, yn, fail);
       eliminate_forward<T, D>(Rc, yc, Cc, dRa, dya, On, Rn, yn, pl, mah, fail);
       continue;
@@ -1617,6 +1626,8 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
 template <typename T, int D> constexpr bool leg_source_supported() { return TileCfg<T, D>::LPR == 1; }
 // SRC = 2: A is a table of `entries` blocks and row r adds entry min(pattern[r], entries - 1) of it (pattern: N device
 // bytes).  Its kernels are instantiated by the translation unit that calls it (cgps_leg_obs.hip).
+// SRC = 3: A is a basis of `entries` = Kb blocks and `pattern` points at the rows' weights, [N][Kb] values of T: row r
+// adds sum_k weights[r][k] A[k].  Instantiated by cgps_leg_obs.hip as well.
 template <typename T, int D, int SRC = 1>
 int run_tile_leg(const T* ts, const T* G, const T* A, const T* v, int64_t N, char* ws, size_t ws_bytes, double* out2,
                  int* info, hipStream_t st, bool pair = false, const unsigned char* pattern = nullptr, int entries = 0) {

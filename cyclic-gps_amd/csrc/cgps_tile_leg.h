@@ -87,3 +87,27 @@ __device__ __forceinline__ const T* leg_obs_block(const T* __restrict__ table, c
   const int p = (int)pattern[r];
   return table + (size_t)(p < entries - 1 ? p : entries - 1) * (D * D);
 }
+
+// The diagonal term of row r when every row has noise of its own (chunk_reduce_kernel<.., SRC = 3>): the weighted sum
+// of Kb basis blocks shared by all rows,  M += sum_k weights[r Kb + k] basis[k],  added in registers.  M is the carried
+// toRight term of the gap before row r (cR), BEFORE leg_row assembles the row with no A: leg_row folds cR into R and
+// then overwrites it with the next gap, and at that point fewer blocks are live than after the row is assembled
+// (adding to the finished R instead costs fp64 d = 4 160 bytes of scratch per lane more).
+// The basis address is the same in every lane (it arrives through the scalar cache, as the one block of SRC = 1
+// does); only the Kb weights of the row are per-lane vector loads, and the d x d term itself never exists in memory.
+// A null basis (the prior-precision half of a pair launch) adds nothing and reads nothing.
+template <typename T, int D>
+__device__ __forceinline__ void leg_add_weighted_basis(const T* __restrict__ basis, const T* __restrict__ weights, int Kb,
+                                                       int64_t r, T (&M)[D][D]) {
+  if (basis == nullptr) return;
+  const T* __restrict__ w = weights + (size_t)r * Kb;
+#pragma unroll 1
+  for (int k = 0; k < Kb; ++k) {
+    const T wk = w[k];
+    const T* __restrict__ bk = basis + (size_t)k * (D * D);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) M[i][j] += wk * bk[i * D + j];
+  }
+}

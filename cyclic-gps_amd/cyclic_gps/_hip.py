@@ -48,6 +48,7 @@ _SIGNATURES = {
     "cgps_leg_mahal_logdet": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "cgps_leg_mahal_logdet_pair": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "cgps_leg_mahal_logdet_pair_obs": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _i64, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "cgps_leg_mahal_logdet_pair_w": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _i64, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "cgps_peg_precision_adjoint": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "cgps_leg_loglik_batch": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _int, _i64, _vp, _vp, _vp]),
     "cgps_leg_loglik_batch_obs": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _i64, _vp, _vp, _vp]),

@@ -352,6 +352,41 @@ def leg_loglik_reductions_obs(ts, G, A_table, pattern, v):
     return out[0], out[1], out[3]
 
 
+def leg_loglik_reductions_w(ts, G, basis, weights, v):
+    """``leg_loglik_reductions`` of a series whose rows each add a term of their own, still ONE launch
+    (cgps_leg_mahal_logdet_pair_w): K = PEG precision(ts, G) + blockdiag(sum_k weights[i, k] basis[k]), the d x d terms
+    formed in registers and never written.  basis [Kb, d, d] with 1 <= Kb <= 64 and weights [N, Kb], both device tensors
+    of G's dtype (``observation_weights`` builds them); v [N, d].  No autograd graph."""
+    from . import _hip
+    n, d, dt = ts.shape[0], G.shape[0], G.dtype
+    if basis.dim() != 3 or tuple(basis.shape[1:]) != (d, d) or not 1 <= basis.shape[0] <= 64:
+        raise ValueError("basis must be [Kb, %d, %d] with 1 <= Kb <= 64, got %s" % (d, d, tuple(basis.shape)))
+    if tuple(weights.shape) != (n, basis.shape[0]):
+        raise ValueError("weights must be [%d, %d] (one row of Kb weights per time stamp), got %s"
+                         % (n, basis.shape[0], tuple(weights.shape)))
+    if tuple(v.shape) != (n, d):
+        raise ValueError("v must be [%d, %d], got %s" % (n, d, tuple(v.shape)))
+    if basis.dtype != dt or weights.dtype != dt:
+        raise ValueError("basis and weights must have G's dtype %s, got %s and %s" % (dt, basis.dtype, weights.dtype))
+    if not (basis.is_cuda and weights.is_cuda):
+        raise ValueError("basis and weights must be device tensors")
+    ts = ts.to(dt).contiguous()
+    G, basis, weights, v = G.contiguous(), basis.contiguous(), weights.contiguous(), v.to(dt).contiguous()
+    ws = _hip.pair_workspace(n, d, dt, G.device)
+    out = torch.empty(4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_w(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(basis), basis.shape[0],
+                                                       _hip.ptr(weights), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
+                                                       ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = info.tolist()
+        if bad[0] or bad[1]:
+            raise cr.NotPSDError("LEG system: a block near row %d is not positive definite (or a time gap has zero length)"
+                                 % ((bad[0] or bad[1]) - 1))
+    out = out.to(dt)
+    return out[0], out[1], out[3]
+
+
 def leg_loglik_batch_reductions(ts, G, A, v, q, plan):
     """The per-series reductions of a batch, no autograd graph: [B, 4] fp64 rows (v^T K^-1 v, log|K|, log|Sigma^-1|,
     sum q) and [B, 2] info words (cgps_leg_loglik_batch; series longer than BATCH_MAX_ROWS through
@@ -719,6 +754,94 @@ def _observed_operands(m, ts, xs, observed):
     return pattern, idx, A_table, c_table, xl, xz
 
 
+# ---- per-observation noise variances ---------------------------------------------------------------------------
+# Entry c of row i carries extra independent noise of variance s_ic >= 0: the row's noise covariance is LLT + diag(s_i),
+# so its Li has no finite table.  But A_i = B^T Li_i B is a weighted sum of obs (obs + 1) / 2 blocks shared by all rows
+# (the symmetrised outer products of B's rows), weighted by the entries of Li_i: the fused kernel gets the basis once
+# and Kb numbers per row.
+_tril = {}
+
+
+def _tril_pairs(obs, device):
+    """(c, c') of the pairs c >= c' in row-major order over the lower triangle, built once per (obs, device)."""
+    key = (obs, device)
+    t = _tril.get(key)
+    if t is None:
+        ij = torch.tril_indices(obs, obs, device=device)
+        t = _tril[key] = (ij[0], ij[1], (ij[0] == ij[1]).view(-1, 1, 1))
+    return t
+
+
+def observation_weights(m, observed, noise_var):
+    """What rows with noise variances of their own need: ``(basis, weights, Li_rows, c_rows)``.
+
+    ``noise_var``: [n, obs_dim] variances s_ic >= 0 of independent noise added to entry c of row i, or [n] for the same
+    value in every channel of a row.  ``observed``: bool [n, obs_dim], [n] for whole rows, or None (everything).  With
+    M_i = diag(observed_i), S_i its observed channels and C_i = Lambda Lambda^T + 1e-9 I + diag(s_i):
+    W_i = M_i C_i M_i + (I - M_i),  Li_rows[i] = W_i^-1 - (I - M_i)  (= (C_i[S_i, S_i])^-1 embedded in zeros),
+    c_rows[i] = |S_i| log 2 pi + log|W_i|.  The pairs c >= c' of channels, in row-major order over the lower triangle,
+    index Kb = obs_dim (obs_dim + 1) / 2 entries:  basis[k] = b_c b_c^T (c = c') or b_c b_c'^T + b_c' b_c^T (c > c'), b_c
+    row c of B, and weights[i, k] = Li_rows[i][c, c'], so that  sum_k weights[i, k] basis[k] = B^T Li_rows[i] B.
+    ``noise_var`` at entries that are not observed is ignored whatever it holds (NaN included).  Values are not checked:
+    a negative or non-finite variance at an observed entry surfaces as NotPSDError or NaN downstream, like a
+    zero-length gap -- mark missing data with ``observed``, not with an infinite variance.  obs_dim <= 8.  Batched
+    torch ops, differentiable in B, Lambda and noise_var, nothing read on the host."""
+    obs = m.B.shape[0]
+    if obs > MAX_PATTERN_OBS:
+        raise ValueError("per-row observation terms are built for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, obs))
+    if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
+        raise ValueError("noise_var must be a floating-point tensor")
+    if noise_var.dim() == 1:
+        noise_var = noise_var.unsqueeze(-1).expand(-1, obs)
+    if noise_var.dim() != 2 or noise_var.shape[1] != obs:
+        raise ValueError("noise_var must be [n] or [n, %d] (one variance per row or per observed channel), got %s"
+                         % (obs, tuple(noise_var.shape)))
+    dt, dev = m.B.dtype, m.B.device
+    s = noise_var.to(dt)
+    if observed is None:
+        Mt = torch.ones((), dtype=dt, device=dev).expand(s.shape)
+    else:
+        observed = _observed_2d(observed, obs)
+        if observed.shape[0] != s.shape[0]:
+            raise ValueError("observed has %d rows, noise_var has %d" % (observed.shape[0], s.shape[0]))
+        s = torch.where(observed, s, torch.zeros((), dtype=dt, device=s.device))
+        Mt = observed.to(dt)
+    LLT = m.LLT
+    if obs == 1:                                        # a single output: no factorisation call, the scalar log
+        W = Mt * (LLT[0, 0] + s) + (1 - Mt)             # [n, 1]
+        Li_rows = (1.0 / W - (1 - Mt)).unsqueeze(-1)
+        logdet_W = torch.log(W[:, 0])
+    else:
+        unobs = torch.diag_embed(1 - Mt)
+        W = Mt.unsqueeze(2) * (LLT + torch.diag_embed(s)) * Mt.unsqueeze(1) + unobs
+        Li_rows = torch.linalg.inv_ex(W)[0] - unobs     # the inverse's backward is matmul only (see LLT_inv); no host check
+        logdet_W = torch.logdet(W)
+    c_rows = Mt.sum(1) * math.log(2 * math.pi) + logdet_W
+    ci, cj, same = _tril_pairs(obs, dev)
+    outer = m.B[ci].unsqueeze(2) * m.B[cj].unsqueeze(1)  # b_c b_c'^T
+    basis = torch.where(same, outer, outer + outer.transpose(1, 2))
+    weights = Li_rows[:, ci, cj]
+    return basis, weights, Li_rows, c_rows
+
+
+def _noise_operands(m, ts, xs, observed, noise_var):
+    """(basis, weights, c_rows, x~ Li per row, x~) with x~ = xs where observed, 0 elsewhere."""
+    if xs.dim() != 2 or xs.shape[1] != m.B.shape[0]:
+        raise ValueError("xs must be [n, %d], got %s" % (m.B.shape[0], tuple(xs.shape)))
+    if not isinstance(noise_var, torch.Tensor) or noise_var.dim() not in (1, 2):
+        raise ValueError("noise_var must be a tensor of shape [n] or [n, %d]" % xs.shape[1])
+    if not (noise_var.shape[0] == xs.shape[0] == ts.shape[0]):
+        raise ValueError("noise_var has %d rows, xs has %d, ts has %d" % (noise_var.shape[0], xs.shape[0], ts.shape[0]))
+    if observed is not None:
+        observed = _observed_2d(observed, xs.shape[1])
+        if observed.shape[0] != xs.shape[0]:
+            raise ValueError("observed has %d rows, xs has %d" % (observed.shape[0], xs.shape[0]))
+    basis, weights, Li_rows, c_rows = observation_weights(m, observed, noise_var)
+    xz = xs if observed is None else torch.where(observed, xs, torch.zeros((), dtype=xs.dtype, device=xs.device))
+    xl = (xz.unsqueeze(1) @ Li_rows).squeeze(1)                 # x~^T Li_i: Li is symmetric
+    return basis, weights, c_rows, xl, xz
+
+
 def merge_targets(ts, xs, target_ts, check=True):
     """Insert the times ``target_ts`` [k] into the series as wholly unobserved rows: ``(ts_all [n + k], xs_all
     [n + k, obs], observed_all bool [n + k], target_index int64 [k])``, ts_all sorted (a stable sort on the device),
@@ -748,8 +871,13 @@ def compute_v(m, xs):
     return (xs @ m.LLT_inv @ m.B).contiguous()
 
 
-def _posterior_system(m, ts, xs, observed):
-    """(K_Rs, K_Os, v) of the posterior N(K^-1 v, K^-1); with ``observed``, row i adds A(m_i) and v_i = B^T Li(m_i) x~_i."""
+def _posterior_system(m, ts, xs, observed, noise_var=None):
+    """(K_Rs, K_Os, v) of the posterior N(K^-1 v, K^-1); with ``observed``, row i adds A(m_i) and v_i = B^T Li(m_i) x~_i;
+    with ``noise_var``, row i adds sum_k weights[i, k] basis[k] = B^T Li_i B and v_i = B^T Li_i x~_i."""
+    if noise_var is not None:
+        basis, weights, _, xl, _ = _noise_operands(m, ts, xs, observed, noise_var)
+        Rs, Os = peg_precision(ts, m.G)
+        return Rs + torch.einsum("nk,kij->nij", weights, basis), Os, (xl @ m.B).contiguous()
     if observed is None:
         return posterior_precision(m, ts) + (compute_v(m, xs),)
     _, idx, A_table, _, xl, _ = _observed_operands(m, ts, xs, observed)
@@ -773,7 +901,24 @@ def _log_likelihood_observed(m, ts, xs, observed):
     return -0.5 * ((obs_terms - k_mahal) + (k_det - sig_inv_det))
 
 
-def log_likelihood(m, ts, xs, observed=None):
+def _log_likelihood_noise(m, ts, xs, observed, noise_var):
+    """``log_likelihood`` with per-observation noise variances:  -1/2 [sum q_i - v^T K^-1 v + sum c_i + log|K| -
+    log|Sigma^-1|],  K = PEG precision + blockdiag(B^T Li_i B),  v_i = B^T Li_i x~_i,  q_i = x~_i^T Li_i x~_i."""
+    basis, weights, c_rows, xl, xz = _noise_operands(m, ts, xs, observed, noise_var)
+    v = (xl @ m.B).contiguous()
+    G = m.G
+    obs_terms = (xl * xz).sum() + c_rows.sum()
+    if fused_supported(ts, G) and not (torch.is_grad_enabled() and
+                                       (basis.requires_grad or weights.requires_grad or v.requires_grad)):
+        k_mahal, k_det, sig_inv_det = leg_loglik_reductions_w(ts, G, basis.to(G.dtype), weights.to(G.dtype), v)
+    else:
+        Rs, Os = peg_precision(ts, G)
+        _, sig_inv_det = cr.mahal_and_det(Rs, Os, torch.zeros_like(v))
+        k_mahal, k_det = cr.mahal_and_det(Rs=Rs + torch.einsum("nk,kij->nij", weights, basis), Os=Os, x=v)
+    return -0.5 * ((obs_terms - k_mahal) + (k_det - sig_inv_det))
+
+
+def log_likelihood(m, ts, xs, observed=None, noise_var=None):
     """log p(xs | ts) of the LEG model (models.py:301-372).  Differentiable in N, R, B, Lambda (through ``m``), xs and
     ts, for any subset of trainable parameters.  The fused reductions (no autograd graph) are taken only when none of
     ts, G, B^T (LL^T)^-1 B and v needs a gradient; otherwise the blocks go through ``peg_precision`` and
@@ -782,7 +927,18 @@ def log_likelihood(m, ts, xs, observed=None):
     ``observed`` (bool [n, obs_dim], or [n] for whole rows; None: everything): the density of the observed entries
     alone.  Entries of xs that are not observed are ignored whatever they hold; a row that observes nothing is
     marginalised out, i.e. the result is that of the series without it (``observation_tables``).  The same fused /
-    unfused choice (cgps_leg_mahal_logdet_pair_obs), the same gradients, and nothing read on the host."""
+    unfused choice (cgps_leg_mahal_logdet_pair_obs), the same gradients, and nothing read on the host.
+
+    ``noise_var`` ([n, obs_dim] or [n], >= 0; None: none, and exactly the calls above): entry c of row i carries extra
+    independent noise of variance noise_var[i, c] -- per-point error bars -- so the noise covariance of row i is
+    Lambda Lambda^T + 1e-9 I + diag(noise_var[i]) (``observation_weights``).  Combines with ``observed``; entries of
+    noise_var that are not observed are ignored whatever they hold.  The fused path (cgps_leg_mahal_logdet_pair_w) builds
+    every row's term in registers from obs_dim (obs_dim + 1) / 2 numbers per row; with a gradient wanted the unfused
+    path, differentiable in noise_var as well.  Nothing read on the host.  With target times: after ``merge_targets``
+    the per-row noise of the merged series is ``noise_all = zeros(n + k, obs_dim); noise_all[observed_all] = noise_var``
+    (the stable sort keeps the data rows in their order), passed with ``observed=observed_all``."""
+    if noise_var is not None:
+        return _log_likelihood_noise(m, ts, xs, observed, noise_var)
     if observed is not None:
         return _log_likelihood_observed(m, ts, xs, observed)
     LLT = m.LLT
@@ -895,11 +1051,12 @@ class GraphedValueAndGrad:
         return self.value, self.grads
 
 
-def insample_posterior(m, ts, xs, observed=None):
+def insample_posterior(m, ts, xs, observed=None, noise_var=None):
     """Posterior mean [N,d] and (diag, lower off-diag) covariance blocks (models.py:282-298).  The mean is
     differentiable; the covariance blocks (``cr.inverse_blocks``) carry no autograd graph.  ``observed`` as in
-    ``log_likelihood``: the posterior is given at ALL rows, those that observe nothing included (``merge_targets``)."""
-    K_Rs, K_Os, v = _posterior_system(m, ts, xs, observed)
+    ``log_likelihood``: the posterior is given at ALL rows, those that observe nothing included (``merge_targets``).
+    ``noise_var`` as in ``log_likelihood``: per-observation noise variances (the mean is differentiable in them too)."""
+    K_Rs, K_Os, v = _posterior_system(m, ts, xs, observed, noise_var)
     if K_Rs.is_cuda and not (torch.is_grad_enabled() and (K_Rs.requires_grad or K_Os.requires_grad or v.requires_grad)):
         dec, mean = cr.decompose_solve(K_Rs, K_Os, v)      # factor and solve together (cgps_decompose_solve)
     else:
@@ -930,12 +1087,12 @@ def sample_from_prior(m, ts, num_samples, seed):
         return z, sample_observations(m, z, seed)
 
 
-def sample_from_posterior(m, ts, xs, num_samples, seed, observed=None):
+def sample_from_posterior(m, ts, xs, num_samples, seed, observed=None, noise_var=None):
     """num_samples latent paths z [n, rank, S] from the posterior given xs at ts: factor and posterior mean together
     (``cr.decompose_solve``), then ``cr.sample`` with that mean -- two library calls.  No autograd graph.  ``observed``
-    as in ``log_likelihood``: joint paths through every row, observed or not."""
+    as in ``log_likelihood``: joint paths through every row, observed or not; ``noise_var`` as there too."""
     with torch.no_grad():
-        K_Rs, K_Os, v = _posterior_system(m, ts, xs, observed)
+        K_Rs, K_Os, v = _posterior_system(m, ts, xs, observed, noise_var)
         dec, mean = cr.decompose_solve(K_Rs, K_Os, v)
         return cr.sample(dec, num_samples, seed, mean=mean)
 

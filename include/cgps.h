@@ -202,6 +202,18 @@ int cgps_leg_mahal_logdet_pair_obs(const void* ts, const void* G, const void* A_
                                    const unsigned char* pattern, const void* v, int64_t N, int d, int dtype,
                                    void* ws, size_t ws_bytes, double* out4, int* info2, void* stream);
 
+/* cgps_leg_mahal_logdet_pair for a series whose rows each have a diagonal term of their own (per-observation noise
+ * variances): row i adds a weighted sum of Kb basis blocks shared by all rows,
+ *   K = PEG precision(ts, G) + blockdiag(sum_k weights[i][k] basis[k]).
+ * basis[Kb][d][d], 1 <= Kb <= 64; weights[N][Kb] in the dtype of the call (DEVICE memory); v[N][d] (NULL: zeros) is
+ * the caller's right-hand side.  The d x d terms are formed in registers and never written.  The prior-precision half
+ * (out4[2..3]) adds nothing and reads neither basis nor weights.  out4, info2, workspace and error codes: those of
+ * cgps_leg_mahal_logdet_pair; null pointers, N < 1 and Kb outside 1..64 are CGPS_ERR_ARG before anything is
+ * launched. */
+int cgps_leg_mahal_logdet_pair_w(const void* ts, const void* G, const void* basis, int Kb, const void* weights,
+                                 const void* v, int64_t N, int d, int dtype, void* ws, size_t ws_bytes, double* out4,
+                                 int* info2, void* stream);
+
 /* Adjoint of cgps_peg_precision in G and in the time gaps (training through the assembly; what
  * autograd computes through models.py:181-239 for LEGFamily.training_step, models.py:374-381).
  * gRs[N][d][d], gOs[N-1][d][d]: d loss / d Rs, d loss / d Os.  One lane per time gap, 64 gaps per
