@@ -3,6 +3,8 @@
 // d x d generator G (reference models.py:181-239, restated):
 //     E_i  = exp(-1/2 (t_{i+1} - t_i) G)
 //     a_i  = (I - E_i^T E_i)^-1 E_i^T,     b_i = (I - E_i E_i^T)^-1 E_i
+// evaluated through F_i = E_i - I (mat_expm1, gap_gram), so that a gap far below the length scale 1 / |G| keeps its
+// precision: I - E E^T is of size gap |G| and is never formed from two matrices of size 1.
 //     Rs_i = I + E_i^T b_i + E_{i-1} a_{i-1},     Os_i = -b_i                     (J[i+1, i] = Os_i)
 // Embarrassingly parallel over the time axis: one lane per block row, everything in registers.
 // A lane evaluates its own gap (i) and the gap before it (i-1), so no lane waits for a neighbour
@@ -80,15 +82,90 @@ __device__ __forceinline__ void mat_exp(T (&E)[D][D], T (&A)[D][D]) {
   }
 }
 
-// X = (I - S)^-1 B for the symmetric S (lower triangle read); returns false when I - S is not
-// positive definite
+// F = exp(A) - I without forming exp(A); A is destroyed.  For a short gap exp(A) is I plus something of the size of A,
+// and everything downstream wants that something to full relative precision (gap_gram).  The scaled series is summed
+// without its leading I,  F = A (I + A/2 (I + A/3 (...))),  and a squaring  E <- E E  reads  F <- 2 F + F F:  no step
+// adds a matrix of size 1 to one of size |A|.  At long gaps F tends to -I and an absolute error of a few eps is all
+// that the blocks ask for (exp(A) itself is then far below 1 and so is what it contributes).
 template <typename T, int D>
-__device__ __forceinline__ bool spd_solve_i_minus(const T (&S)[D][D], const T (&B)[D][D], T (&X)[D][D]) {
-  T M[D][D];
+__device__ __forceinline__ void mat_expm1(T (&F)[D][D], T (&A)[D][D]) {
+  T nrm = T(0);
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    T c = T(0);
+#pragma unroll
+    for (int i = 0; i < D; ++i) c += A[i][j] < T(0) ? -A[i][j] : A[i][j];
+    nrm = c > nrm ? c : nrm;
+  }
+  int s = 0;
+  T scale = T(1);
+  while (nrm * scale > T(0.5) && s < 60) { scale *= T(0.5); ++s; }
 #pragma unroll
   for (int i = 0; i < D; ++i)
 #pragma unroll
-    for (int j = 0; j < D; ++j) M[i][j] = ((i == j) ? T(1) : T(0)) - S[i][j];
+    for (int j = 0; j < D; ++j) {
+      A[i][j] *= scale;
+      F[i][j] = (i == j) ? T(1) : T(0);
+    }
+#pragma unroll 1
+  for (int k = exp_taylor_degree<T>(); k >= 2; --k) {
+    T P[D][D];
+    mat_mul<T, D>(P, A, F);
+    const T rk = T(1) / T(k);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) F[i][j] = ((i == j) ? T(1) : T(0)) + P[i][j] * rk;
+  }
+  {
+    T P[D][D];
+    mat_mul<T, D>(P, A, F);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) F[i][j] = P[i][j];
+  }
+#pragma unroll 1
+  for (int q = 0; q < s; ++q) {
+    T P[D][D];
+    mat_mul<T, D>(P, F, F);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) F[i][j] = fmaT(T(2), F[i][j], P[i][j]);
+  }
+}
+
+// F = exp(-1/2 dt G) - I of one time gap: the one place every assembly (unfused, fused, batched, adjoint) gets it from
+template <typename T, int D, typename GT>
+__device__ __forceinline__ void gap_expm1(T dt, const GT& G, T (&F)[D][D]) {
+  T A[D][D];
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) A[i][j] = T(-0.5) * dt * G(i, j);
+  mat_expm1<T, D>(F, A);
+}
+
+// M = I - E E^T (OUTER) or I - E^T E (!OUTER) for E = I + F, as -(F + F^T + F F^T) resp. -(F + F^T + F^T F): the
+// reference's form subtracts two matrices of size 1 and keeps eps / (gap |G|) of relative precision; here the three
+// terms are of the size of the result.
+template <typename T, int D, bool OUTER>
+__device__ __forceinline__ void gap_gram(const T (&F)[D][D], T (&M)[D][D]) {
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      T s = F[i][j] + F[j][i];
+#pragma unroll
+      for (int m = 0; m < D; ++m) s = OUTER ? fmaT(F[i][m], F[j][m], s) : fmaT(F[m][i], F[m][j], s);
+      M[i][j] = -s;
+    }
+}
+
+// X = M^-1 B (TRANS: M^-1 B^T) for the symmetric M (lower triangle read); returns false when M is not positive definite
+template <typename T, int D, bool TRANS = false>
+__device__ __forceinline__ bool spd_solve(const T (&M)[D][D], const T (&B)[D][D], T (&X)[D][D]) {
   Chol<T, D> c;
   bool f = false;
   chol_lower<T, D>(M, c, f);
@@ -96,7 +173,7 @@ __device__ __forceinline__ bool spd_solve_i_minus(const T (&S)[D][D], const T (&
   for (int j = 0; j < D; ++j) {
     T v[D];
 #pragma unroll
-    for (int i = 0; i < D; ++i) v[i] = B[i][j];
+    for (int i = 0; i < D; ++i) v[i] = TRANS ? B[j][i] : B[i][j];
     fwd_subst<T, D>(c, v);
     bwd_subst<T, D>(c, v);
 #pragma unroll
@@ -105,33 +182,51 @@ __device__ __forceinline__ bool spd_solve_i_minus(const T (&S)[D][D], const T (&
   return !f;
 }
 
+// X = (I - S)^-1 B for the symmetric S (lower triangle read); returns false when I - S is not
+// positive definite.  Only for an S that is not close to I (the prediction glue below); a time gap goes through gap_gram.
+template <typename T, int D>
+__device__ __forceinline__ bool spd_solve_i_minus(const T (&S)[D][D], const T (&B)[D][D], T (&X)[D][D]) {
+  T M[D][D];
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) M[i][j] = ((i == j) ? T(1) : T(0)) - S[i][j];
+  return spd_solve<T, D>(M, B, X);
+}
+
+template <typename T, int D>
+__device__ __forceinline__ void add_identity(T (&E)[D][D]) {
+#pragma unroll
+  for (int i = 0; i < D; ++i) E[i][i] += T(1);
+}
+
 // the two contributions of one time gap: toRight = E a (goes to the row after the gap),
 // toLeft = E^T b (to the row before it), b itself (the coupling is -b)
 template <typename T, int D>
 __device__ __forceinline__ bool gap_terms(T dt, const T (&G)[D][D], bool want_right, bool want_left, T (&toRight)[D][D],
                                           T (&toLeft)[D][D], T (&b)[D][D]) {
-  T A[D][D], E[D][D], Et[D][D];
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int j = 0; j < D; ++j) A[i][j] = T(-0.5) * dt * G[i][j];
-  mat_exp<T, D>(E, A);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int j = 0; j < D; ++j) Et[i][j] = E[j][i];
+  T E[D][D], Ma[D][D], Mb[D][D];
+  gap_expm1<T, D>(dt, [&](int i, int j) { return G[i][j]; }, E);       // F
+  if (want_right) gap_gram<T, D, false>(E, Ma);
+  if (want_left) gap_gram<T, D, true>(E, Mb);
+  add_identity<T, D>(E);                                               // E = I + F
   bool ok = true;
   if (want_right) {
-    T S[D][D], a[D][D];
-    mat_mul<T, D>(S, Et, E);                       // E^T E
-    ok = spd_solve_i_minus<T, D>(S, Et, a) && ok;  // a = (I - E^T E)^-1 E^T
+    T a[D][D];
+    ok = spd_solve<T, D, true>(Ma, E, a) && ok;    // a = (I - E^T E)^-1 E^T
     mat_mul<T, D>(toRight, E, a);
   }
   if (want_left) {
-    T S[D][D];
-    mat_mul<T, D>(S, E, Et);                       // E E^T
-    ok = spd_solve_i_minus<T, D>(S, E, b) && ok;   // b = (I - E E^T)^-1 E
-    mat_mul<T, D>(toLeft, Et, b);
+    ok = spd_solve<T, D>(Mb, E, b) && ok;          // b = (I - E E^T)^-1 E
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        T s = T(0);
+#pragma unroll
+        for (int m = 0; m < D; ++m) s = fmaT(E[m][i], b[m][j], s);
+        toLeft[i][j] = s;
+      }
   }
   return ok;
 }
@@ -467,24 +562,19 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_adjoint_kernel(
 #pragma unroll
       for (int b = 0; b < D; ++b) G[a][b] = Gg[a * D + b];
     const T tau = ts[i + 1] - ts[i];
-    T E[D][D], Et[D][D];
-    {
-      T A[D][D];
-#pragma unroll
-      for (int a = 0; a < D; ++a)
-#pragma unroll
-        for (int b = 0; b < D; ++b) A[a][b] = T(-0.5) * tau * G[a][b];
-      mat_exp<T, D>(E, A);
-    }
+    T E[D][D], Et[D][D], Mb[D][D], Ma[D][D];                 // Mb = I - E E^T, Ma = I - E^T E, both from F = E - I
+    gap_expm1<T, D>(tau, [&](int a, int b) { return G[a][b]; }, E);
+    gap_gram<T, D, true>(E, Mb);
+    gap_gram<T, D, false>(E, Ma);
+    add_identity<T, D>(E);
 #pragma unroll
     for (int a = 0; a < D; ++a)
 #pragma unroll
       for (int b = 0; b < D; ++b) Et[a][b] = E[b][a];
     T Ebar[D][D];
     {   // through c2 = E^T b (to Rs_i) and Os_i = -b
-      T S[D][D], bm[D][D], U2[D][D], gO[D][D], bbar[D][D], W[D][D], X[D][D], Y[D][D];
-      mat_mul<T, D>(S, E, Et);
-      (void)spd_solve_i_minus<T, D>(S, E, bm);                 // b = (I - E E^T)^-1 E
+      T bm[D][D], U2[D][D], gO[D][D], bbar[D][D], W[D][D], X[D][D], Y[D][D];
+      (void)spd_solve<T, D>(Mb, E, bm);                        // b = (I - E E^T)^-1 E
       load_block<T, D>(gRs + i * DD, U2);
       load_block<T, D>(gOs + i * DD, gO);
       mat_mul<T, D>(bbar, E, U2);
@@ -492,7 +582,7 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_adjoint_kernel(
       for (int a = 0; a < D; ++a)
 #pragma unroll
         for (int b = 0; b < D; ++b) bbar[a][b] -= gO[a][b];
-      (void)spd_solve_i_minus<T, D>(S, bbar, W);               // W = (I - E E^T)^-1 bbar
+      (void)spd_solve<T, D>(Mb, bbar, W);                      // W = (I - E E^T)^-1 bbar
       // Ebar = b U2^T + W + (W b^T + b W^T) E
 #pragma unroll
       for (int a = 0; a < D; ++a)
@@ -515,12 +605,11 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_adjoint_kernel(
         for (int b = 0; b < D; ++b) Ebar[a][b] += Y[a][b];
     }
     {   // through c1 = E a (to Rs_{i+1})
-      T S[D][D], am[D][D], U1[D][D], abar[D][D], V[D][D], X[D][D], Y[D][D];
-      mat_mul<T, D>(S, Et, E);
-      (void)spd_solve_i_minus<T, D>(S, Et, am);                // a = (I - E^T E)^-1 E^T
+      T am[D][D], U1[D][D], abar[D][D], V[D][D], X[D][D], Y[D][D];
+      (void)spd_solve<T, D>(Ma, Et, am);                       // a = (I - E^T E)^-1 E^T
       load_block<T, D>(gRs + (i + 1) * DD, U1);
       mat_mul<T, D>(abar, Et, U1);
-      (void)spd_solve_i_minus<T, D>(S, abar, V);               // V = (I - E^T E)^-1 abar
+      (void)spd_solve<T, D>(Ma, abar, V);                      // V = (I - E^T E)^-1 abar
       // Ebar += U1 a^T + V^T + E (a V^T + V a^T)
 #pragma unroll
       for (int a = 0; a < D; ++a)

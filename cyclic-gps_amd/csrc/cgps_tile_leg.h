@@ -4,7 +4,8 @@
 // written to HBM by cgps_peg_precision and read back -- for LEG workloads the compulsory read of Rs / Os disappears
 // (what is left is the right-hand side, d values per row) and so do two launches of a log-likelihood.
 // Included from cgps_tile.h (inside namespace cgps); the arithmetic is that of cgps_leg.h:
-//     E_g = exp(-1/2 (t_{g+1} - t_g) G),   a_g = (I - E_g^T E_g)^-1 E_g^T   (one symmetric positive definite solve)
+//     E_g = exp(-1/2 (t_{g+1} - t_g) G),   a_g = (I - E_g^T E_g)^-1 E_g^T   (one symmetric positive definite solve;
+//                                           I - E^T E from F = E - I, cancellation-free at short gaps: gap_gram)
 //     b_g = (I - E_g E_g^T)^-1 E_g = a_g^T                                   (push-through identity)
 //     row g+1 gets  toRight_g = E_g a_g,   row g gets  toLeft_g = E_g^T b_g = (a_g E_g)^T,   J[g+1, g] = -b_g
 //     R_i = I + toLeft_i + toRight_{i-1} + A
@@ -16,25 +17,14 @@
 template <typename T, int D>
 __device__ __forceinline__ bool leg_gap(const T* __restrict__ ts, const T* __restrict__ Gg, int64_t g, T (&toRight)[D][D],
                                         T (&toLeft)[D][D], T (&b)[D][D]) {
-  const T dt = ts[g + 1] - ts[g];
   T E[D][D], a[D][D];
-  {
-    T A[D][D];
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-      for (int j = 0; j < D; ++j) A[i][j] = T(-0.5) * dt * Gg[i * D + j];
-    mat_exp<T, D>(E, A);
-  }
+  gap_expm1<T, D>(ts[g + 1] - ts[g], [&](int i, int j) { return Gg[i * D + j]; }, E);   // F = E - I
   bool ok;
   {
-    T Et[D][D], S[D][D];
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-      for (int j = 0; j < D; ++j) Et[i][j] = E[j][i];
-    mat_mul<T, D>(S, Et, E);
-    ok = spd_solve_i_minus<T, D>(S, Et, a);
+    T M[D][D];
+    gap_gram<T, D, false>(E, M);                   // I - E^T E, from F (cgps_leg.h)
+    add_identity<T, D>(E);
+    ok = spd_solve<T, D, true>(M, E, a);           // a = (I - E^T E)^-1 E^T
   }
   mat_mul<T, D>(toRight, E, a);
   {

@@ -149,11 +149,16 @@ def peg_precision(ts, G):
         if not wants_grad:
             return _peg_precision_hip(ts, G)
     eye = torch.eye(d, dtype=G.dtype, device=G.device)
-    dt = ts[1:] - ts[:-1]
-    E = torch.matrix_exp(-0.5 * G.unsqueeze(0) * dt.reshape(-1, 1, 1))
-    Et = E.transpose(-1, -2)
-    a = torch.linalg.solve(eye - Et @ E, Et)          # (I - E^T E)^-1 E^T
-    b = torch.linalg.solve(eye - E @ Et, E)           # (I - E E^T)^-1 E
+    # F = E - I without cancellation, as the kernels take it (csrc/cgps_leg.h, mat_expm1): the top right block of
+    # matrix_exp([[A, I], [0, 0]]) is phi_1(A) and F = A phi_1(A).  I - E^T E = -(F + F^T + F^T F) then keeps its
+    # relative precision at gaps far below the length scale of G, where E E^T and I agree to many digits.
+    Am = -0.5 * G.unsqueeze(0) * (ts[1:] - ts[:-1]).reshape(-1, 1, 1)
+    aug = torch.cat([torch.cat([Am, eye.expand_as(Am)], -1), Am.new_zeros(Am.shape[0], d, 2 * d)], -2)
+    X = torch.matrix_exp(aug)
+    E, F = X[:, :d, :d], Am @ X[:, :d, d:]
+    Et, Ft = E.transpose(-1, -2), F.transpose(-1, -2)
+    a = torch.linalg.solve(-(F + Ft + Ft @ F), Et)    # (I - E^T E)^-1 E^T
+    b = torch.linalg.solve(-(F + Ft + F @ Ft), E)     # (I - E E^T)^-1 E
     c1, c2 = E @ a, Et @ b
     Rs = eye.repeat(ts.shape[0], 1, 1)
     Rs[:-1] += c2
@@ -887,11 +892,28 @@ def _posterior_system(m, ts, xs, observed, noise_var=None):
 
 def _log_likelihood_observed(m, ts, xs, observed):
     """``log_likelihood`` with a per-row observation pattern:  -1/2 [sum q_i - v^T K^-1 v + sum c(m_i) + log|K| -
-    log|Sigma^-1|],  K = PEG precision + blockdiag(A(m_i)),  v_i = B^T Li(m_i) x~_i,  q_i = x~_i^T Li(m_i) x~_i."""
+    log|Sigma^-1|],  K = PEG precision + blockdiag(A(m_i)),  v_i = B^T Li(m_i) x~_i,  q_i = x~_i^T Li(m_i) x~_i.
+
+    fp32 with a gradient wanted: the observation-space terms (tables, x~ Li, v, q, c) are formed in fp64 and only the
+    operands of the kernels are rounded to fp32.  sum q_i and v^T K^-1 v nearly cancel where the model explains the data,
+    and so do their gradients in Lambda and B -- each about a hundred times their sum -- so the same terms in fp32 leave
+    1e-4 .. 3e-4 of the largest entry in d ll / d Lambda whatever the kernels return; in fp64 they
+    leave what the fp32 reductions themselves do, about 2e-5."""
+    G = m.G
+    dt = G.dtype
+    wide = (dt == torch.float32 and torch.is_grad_enabled() and
+            any(t.requires_grad for t in (m.N, m.R, m.B, m.Lambda, xs, ts)))
+    if wide:
+        m, xs = LEGMatrices(m.N, m.R, m.B.double(), m.Lambda.double()), xs.double()
     pattern, idx, A_table, c_table, xl, xz = _observed_operands(m, ts, xs, observed)
     v = (xl @ m.B).contiguous()
-    G = m.G
     obs_terms = (xl * xz).sum() + c_table[idx].sum()
+    if wide:
+        Rs, Os = peg_precision(ts, G)
+        v32 = v.to(dt)
+        _, sig_inv_det = cr.mahal_and_det(Rs, Os, torch.zeros_like(v32))
+        k_mahal, k_det = cr.mahal_and_det(Rs=Rs + A_table[idx].to(dt), Os=Os, x=v32)
+        return (-0.5 * ((obs_terms - k_mahal.double()) + (k_det.double() - sig_inv_det.double()))).to(dt)
     if fused_supported(ts, G) and not (torch.is_grad_enabled() and (A_table.requires_grad or v.requires_grad)):
         k_mahal, k_det, sig_inv_det = leg_loglik_reductions_obs(ts, G, A_table, pattern, v)
     else:

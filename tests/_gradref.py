@@ -6,13 +6,15 @@
 * Oracle closed form (large N): the adjoint formulas of cyclic_reduction.py, evaluated with the CPU oracle's
   solve / inverse_blocks (oracle/cr_oracle.py).
 * LEG: the log-likelihood as a dense multivariate-normal log-density of the observations, x ~ N(0, B~ Sigma B~^T +
-  Lambda~), with Sigma the dense inverse of the PEG prior precision (torch ops on CPU tensors).
+  Lambda~), with Sigma the stationary covariance of the latent, Cov(z_i, z_j) = exp(-(t_i - t_j) G / 2)
+  (_gapref.py): it does not go through the PEG block formula that the kernels evaluate.
 """
 import functools
 import math
 
 import torch
 
+import _gapref
 import _util
 from oracle import cr_oracle as O
 
@@ -119,15 +121,12 @@ def oracle_value_and_grads(kind, Rs, Os, y, u=None):
 # ---- LEG -----------------------------------------------------------------------------------------------------------
 def leg_dense_loglik(Nm, Rm, Bm, Lm, ts, xs):
     """log p(xs | ts) of the LEG model as one dense Gaussian density over all n * obs observations (fp64 CPU, torch ops,
-    differentiable in all six arguments).  Latent z ~ N(0, Sigma) with Sigma^-1 the PEG prior precision of
+    differentiable in all six arguments).  Latent z ~ N(0, Sigma), Sigma = _gapref.prior_covariance(ts, G) with
     G = N N^T + R - R^T + 1e-5 I; x_t = B z_t + e_t, e_t ~ N(0, Lambda Lambda^T + 1e-9 I)."""
-    from cyclic_gps import leg
     d = Nm.shape[0]
     n, obs = xs.shape
     G = Nm @ Nm.T + Rm - Rm.T + 1e-5 * torch.eye(d, dtype=F64)
-    Rs, Os = leg.peg_precision(ts, G)                   # CPU tensors: batched torch ops, no kernels
-    P = dense_J(Rs, Os)
-    Sigma = torch.cholesky_inverse(torch.linalg.cholesky(P))
+    Sigma = _gapref.prior_covariance(ts, G)             # the covariance form: no block formula, no 1 / gap
     Bt = torch.kron(torch.eye(n, dtype=F64), Bm)
     LLT = Lm @ Lm.T + 1e-9 * torch.eye(obs, dtype=F64)
     C = Bt @ Sigma @ Bt.T + torch.kron(torch.eye(n, dtype=F64), LLT)

@@ -2,14 +2,14 @@
 kernels and of ``leg.observation_tables``: the observed entries alone as ONE dense Gaussian, built like
 ``_gradref.leg_dense_loglik``.
 
-Latent z ~ N(0, Sigma), Sigma^-1 the PEG prior precision of G = N N^T + R - R^T + 1e-5 I; x_t = B z_t + e_t,
-e_t ~ N(0, Lambda Lambda^T + 1e-9 I); only the entries (t, c) with mask[t, c] are data.  Entries of xs outside the mask
-are never touched (they may hold NaN)."""
+Latent z ~ N(0, Sigma), Sigma the stationary covariance (_gapref.prior_covariance) of G = N N^T + R - R^T + 1e-5 I;
+x_t = B z_t + e_t, e_t ~ N(0, Lambda Lambda^T + 1e-9 I); only the entries (t, c) with mask[t, c] are data.  Entries of
+xs outside the mask are never touched (they may hold NaN)."""
 import math
 
 import torch
 
-import _gradref as gr
+import _gapref
 
 F64 = torch.float64
 
@@ -35,12 +35,10 @@ def leg_case(d, obs, n, seed, keep=0.6):
 
 def _dense_parts(Nm, Rm, Bm, Lm, ts, xs, mask):
     """(Sigma [n d, n d], H = rows of kron(I, B) of the observed entries, C = H Sigma H^T + noise, the observed x)"""
-    from cyclic_gps import leg
     d = Nm.shape[0]
     n, obs = xs.shape
     G = Nm @ Nm.T + Rm - Rm.T + 1e-5 * torch.eye(d, dtype=F64)
-    Rs, Os = leg.peg_precision(ts, G)                   # CPU tensors: batched torch ops, no kernels
-    Sigma = torch.cholesky_inverse(torch.linalg.cholesky(gr.dense_J(Rs, Os)))
+    Sigma = _gapref.prior_covariance(ts, G)             # the covariance form: no block formula, no 1 / gap
     idx = mask.reshape(-1).nonzero().flatten()
     H = torch.kron(torch.eye(n, dtype=F64), Bm)[idx]
     LLT = Lm @ Lm.T + 1e-9 * torch.eye(obs, dtype=F64)

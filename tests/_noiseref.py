@@ -2,14 +2,14 @@
 the HIP kernels and of ``leg.observation_weights``: ``_missref.py`` with diag(s) added to the noise of the observed
 entries, the observed entries alone as ONE dense Gaussian.
 
-Latent z ~ N(0, Sigma), Sigma^-1 the PEG prior precision of G = N N^T + R - R^T + 1e-5 I; x_t = B z_t + e_t + f_t,
-e_t ~ N(0, Lambda Lambda^T + 1e-9 I), f_t ~ N(0, diag(s_t)); only the entries (t, c) with mask[t, c] are data.  Entries
-of xs and s outside the mask are never touched (they may hold NaN)."""
+Latent z ~ N(0, Sigma), Sigma the stationary covariance (_gapref.prior_covariance) of G = N N^T + R - R^T + 1e-5 I;
+x_t = B z_t + e_t + f_t, e_t ~ N(0, Lambda Lambda^T + 1e-9 I), f_t ~ N(0, diag(s_t)); only the entries (t, c) with
+mask[t, c] are data.  Entries of xs and s outside the mask are never touched (they may hold NaN)."""
 import math
 
 import torch
 
-import _gradref as gr
+import _gapref
 import _missref as mr
 
 F64 = torch.float64
@@ -24,12 +24,10 @@ def leg_case(d, obs, n, seed, keep=0.6):
 
 def _dense_parts(Nm, Rm, Bm, Lm, ts, xs, s, mask):
     """(Sigma [n d, n d], H = rows of kron(I, B) of the observed entries, C = H Sigma H^T + noise, the observed x)"""
-    from cyclic_gps import leg
     d = Nm.shape[0]
     n, obs = xs.shape
     G = Nm @ Nm.T + Rm - Rm.T + 1e-5 * torch.eye(d, dtype=F64)
-    Rs, Os = leg.peg_precision(ts, G)                   # CPU tensors: batched torch ops, no kernels
-    Sigma = torch.cholesky_inverse(torch.linalg.cholesky(gr.dense_J(Rs, Os)))
+    Sigma = _gapref.prior_covariance(ts, G)             # the covariance form: no block formula, no 1 / gap
     idx = mask.reshape(-1).nonzero().flatten()
     H = torch.kron(torch.eye(n, dtype=F64), Bm)[idx]
     LLT = Lm @ Lm.T + 1e-9 * torch.eye(obs, dtype=F64)
