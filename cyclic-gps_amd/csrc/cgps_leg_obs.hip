@@ -1,7 +1,8 @@
 // cgps_leg_obs.hip -- the fused LEG reductions for series whose rows differ in their observation model.  Missing
 // observations: every row names the entry of a table of diagonal terms it adds (chunk_reduce_kernel<.., SRC = 2>,
-// cgps_tile.h; for many series in one launch leg_batch_kernel<.., OBS = true>, cgps_tile_leg_batch.h).  Noise variances
-// of their own: every row adds a weighted sum of a basis shared by all rows (chunk_reduce_kernel<.., SRC = 3>).
+// cgps_tile.h; for many series in one launch leg_batch_kernel<.., LEG_ROWS_TABLE>, cgps_tile_leg_batch.h).  Noise variances
+// of their own: every row adds a weighted sum of a basis shared by all rows (chunk_reduce_kernel<.., SRC = 3>; for many
+// series in one launch leg_batch_kernel<.., LEG_ROWS_WEIGHTED>).
 // A translation unit of its own: these are the heaviest stage-1 instantiations of the library and compile next to
 // cgps_mahal.hip, not after it.
 #include "cgps_host.h"
@@ -64,6 +65,24 @@ int cgps_leg_loglik_batch_obs(const void* ts, const int64_t* offsets, int64_t B,
     if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch_obs: not built for this block size (d = 8, fp64 d = 6)");
     if (B == 0) return (int)CGPS_OK;
     return check_launch("LEG batched reduction (per-row observation pattern)");
+  });
+}
+
+int cgps_leg_loglik_batch_w(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* basis, int Kb,
+                            const void* weights, const void* v, const void* q, int d, int dtype, int64_t max_rows, double* out4,
+                            int* info2, void* stream) {
+  if (B < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !basis || !weights || !out4 || !info2)))
+    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_w: null pointer or B < 0");
+  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_w: B = %lld series, at most 2^31 - 1", (long long)B);
+  if (Kb < 1 || Kb > 64) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_w: Kb = %d basis blocks, outside 1..64", Kb);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int rc = cgps::run_leg_batch_w<T, D>((const T*)ts, offsets, B, (const T*)G, (const T*)basis, Kb, (const T*)weights,
+                                               (const T*)v, (const T*)q, max_rows, out4, info2, (hipStream_t)stream);
+    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch_w: not built for this block size (d = 8, fp64 d = 6)");
+    if (B == 0) return (int)CGPS_OK;
+    return check_launch("LEG batched reduction (per-row weighted basis)");
   });
 }
 

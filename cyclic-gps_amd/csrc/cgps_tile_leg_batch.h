@@ -1,5 +1,6 @@
-// Batched LEG log-likelihood reductions: many independent series in ONE launch (cgps_leg_loglik_batch, and
-// cgps_leg_loglik_batch_obs for rows that differ in what they observe).
+// Batched LEG log-likelihood reductions: many independent series in ONE launch (cgps_leg_loglik_batch,
+// cgps_leg_loglik_batch_obs for rows that differ in what they observe, and cgps_leg_loglik_batch_w for rows with noise
+// variances of their own).
 // Included from cgps_mahal.hip and from cgps_leg_obs.hip, after cgps_tile.h (the chunk walk, the in-LDS reduction and
 // the in-register assembly of cgps_tile_leg.h are reused as they are).
 //
@@ -20,23 +21,32 @@
 // K_b / S_b that was not positive definite (a zero-length gap included); a failed system's entries are NaN.
 // A series with more than max_rows rows is skipped (nothing written: the caller reduces it with another call).
 //
-// OBS = true (cgps_leg_loglik_batch_obs): rows differ in what they observe.  Ag is then a table of `entries` blocks and
-// row r of series b adds entry pattern[offsets[b] + r] of it (leg_obs_block in cgps_tile_leg.h: the index is clamped,
-// the block is read with per-lane vector loads straight from global memory -- at most 256 blocks, they stay in cache);
-// `pattern` holds one byte per row of the CONCATENATED batch.  The prior-precision workgroup has a null table and reads
-// neither table nor pattern.  OBS = false reads neither argument, and every difference is an `if constexpr`: its
-// instruction stream is the one it had before the flag existed.  The OBS = true kernels are instantiated by the
-// translation unit that calls run_leg_batch_obs (cgps_leg_obs.hip).
+// ROWS names where a row's diagonal term comes from (LEG_ROWS_PLAIN: the one block Ag, the same for every row).
+// ROWS = LEG_ROWS_TABLE (cgps_leg_loglik_batch_obs): rows differ in what they observe.  Ag is then a table of `entries`
+// blocks and row r of series b adds entry pattern[offsets[b] + r] of it (leg_obs_block in cgps_tile_leg.h: the index is
+// clamped, the block is read with per-lane vector loads straight from global memory -- at most 256 blocks, they stay in
+// cache); `pattern` holds one byte per row of the CONCATENATED batch.  The prior-precision workgroup has a null table
+// and reads neither table nor pattern.
+// ROWS = LEG_ROWS_WEIGHTED (cgps_leg_loglik_batch_w): every row has noise of its own.  The same arguments carry other
+// things, as FoldArgs does for chunk_reduce_kernel<.., SRC = 3>: Ag is a basis of `entries` = Kb blocks and `pattern`
+// points at the weights of the CONCATENATED batch, [sum n_b][Kb] values of T; row r of series b adds
+// sum_k weights[(offsets[b] + r) Kb + k] basis[k] to the carried toRight term before leg_row assembles the row with no A
+// (leg_add_weighted_basis in cgps_tile_leg.h, and its note on that placement).  The prior-precision workgroup has a
+// null basis and reads neither basis nor weights.
+// LEG_ROWS_PLAIN reads neither argument, and every difference is an `if constexpr` on the kernel itself: each source's
+// instruction stream is the one it had before the others existed.  The TABLE and WEIGHTED kernels are instantiated
+// by the translation unit that calls run_leg_batch_obs / run_leg_batch_w (cgps_leg_obs.hip).
 #pragma once
 
 namespace cgps {
 
 constexpr int LEG_BATCH_THREADS = 256;
+constexpr int LEG_ROWS_PLAIN = 0, LEG_ROWS_TABLE = 1, LEG_ROWS_WEIGHTED = 2;
 
 template <typename T, int D>
 constexpr int leg_batch_lanes() { return TileCfg<T, D>::NG1; }       // 256, or 128 for 7 x 7 fp64 (LDS)
 
-template <typename T, int D, int NT, int NW, bool OBS = false>
+template <typename T, int D, int NT, int NW, int ROWS = LEG_ROWS_PLAIN>
 __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ ts, const int64_t* __restrict__ offsets,
                                                           const T* __restrict__ Gg, const T* __restrict__ Ag,
                                                           const T* __restrict__ vg, const T* __restrict__ qg,
@@ -54,7 +64,9 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
   const T* __restrict__ tsb = ts + off;
   const T* __restrict__ vb = (prior || vg == nullptr) ? nullptr : vg + off * D;
   const T* __restrict__ Ab = prior ? nullptr : Ag;
-  const unsigned char* __restrict__ pb = OBS ? pattern + off : nullptr;       // the series' own bytes: local row + offset
+  // the series' own bytes / weights: what the rows below index is the local row plus the series' offset
+  const unsigned char* __restrict__ pb = ROWS == LEG_ROWS_TABLE ? pattern + off : nullptr;
+  const T* __restrict__ wb = ROWS == LEG_ROWS_WEIGHTED ? reinterpret_cast<const T*>(pattern) + off * (int64_t)entries : nullptr;
   if (tid == 0) *sm.sfail = 0x7fffffff;
 
   const int64_t C = (n + NT - 1) / NT;                         // rows per lane
@@ -79,17 +91,23 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
       set_zero<T, D>(cR);
       set_zero<T, D>(cB);
     }
-    if constexpr (OBS)
+    if constexpr (ROWS == LEG_ROWS_TABLE)
       leg_row<T, D>(tsb, Gg, leg_obs_block<T, D>(Ab, pb, entries, r0), vb, r0, n, cR, cB, Rc, Cc, yc, fail);
-    else
+    else if constexpr (ROWS == LEG_ROWS_WEIGHTED) {
+      leg_add_weighted_basis<T, D>(Ab, wb, entries, r0, cR);
+      leg_row<T, D>(tsb, Gg, (const T*)nullptr, vb, r0, n, cR, cB, Rc, Cc, yc, fail);
+    } else
       leg_row<T, D>(tsb, Gg, Ab, vb, r0, n, cR, cB, Rc, Cc, yc, fail);
   }
 #pragma unroll 1
   for (int j = 0; j < L - 1; ++j) {
     T Rn[D][D], On[D][D], yn[D];
-    if constexpr (OBS)
+    if constexpr (ROWS == LEG_ROWS_TABLE)
       leg_row<T, D>(tsb, Gg, leg_obs_block<T, D>(Ab, pb, entries, r0 + j + 1), vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
-    else
+    else if constexpr (ROWS == LEG_ROWS_WEIGHTED) {
+      leg_add_weighted_basis<T, D>(Ab, wb, entries, r0 + j + 1, cR);
+      leg_row<T, D>(tsb, Gg, (const T*)nullptr, vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
+    } else
       leg_row<T, D>(tsb, Gg, Ab, vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
     eliminate_forward<T, D>(Rc, yc, Cc, dRa, dya, On, Rn, yn, pl, mah, fail);
   }
@@ -164,7 +182,7 @@ int run_leg_batch(const T* ts, const int64_t* offsets, int64_t B, const T* G, co
   }
 }
 
-// the per-row pattern form (OBS = true); entries in 1..256 and the non-null table and pattern are the caller's checks
+// the per-row pattern form (LEG_ROWS_TABLE); entries in 1..256 and the non-null table and pattern are the caller's checks
 template <typename T, int D>
 int run_leg_batch_obs(const T* ts, const int64_t* offsets, int64_t B, const T* G, const T* table, int entries,
                       const unsigned char* pattern, const T* v, const T* q, int64_t max_rows, double* out4, int* info2,
@@ -180,11 +198,36 @@ int run_leg_batch_obs(const T* ts, const int64_t* offsets, int64_t B, const T* G
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
     std::call_once(once[dev], [lds] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, true>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_TABLE>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
-    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, true>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets, G, table,
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_TABLE>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets, G, table,
                        v, q, max_rows, out4, info2, entries, pattern);
+    return 0;
+  }
+}
+
+// the per-row weighted-basis form (LEG_ROWS_WEIGHTED): weights [sum n_b][Kb] of the concatenated batch; Kb in 1..64 and
+// the non-null basis and weights are the caller's checks
+template <typename T, int D>
+int run_leg_batch_w(const T* ts, const int64_t* offsets, int64_t B, const T* G, const T* basis, int Kb, const T* weights,
+                    const T* v, const T* q, int64_t max_rows, double* out4, int* info2, hipStream_t st) {
+  if constexpr (!leg_batch_supported<T, D>()) {
+    return -2;
+  } else {
+    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
+    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
+    const size_t lds = leg_batch_lds_bytes<T, D>();
+    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
+    std::call_once(once[dev], [lds] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_WEIGHTED>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_WEIGHTED>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets,
+                       G, basis, v, q, max_rows, out4, info2, Kb, reinterpret_cast<const unsigned char*>(weights));
     return 0;
   }
 }

@@ -306,7 +306,7 @@ def _cached_batch_plan(lengths, device):
     plan = _plans.pop(key, None)                                 # (put back below, as the most recent)
     if _capturing(device):
         if plan is None:
-            raise RuntimeError("log_likelihood_batch(observed=) inside a graph capture needs one ordinary call with "
+            raise RuntimeError("log_likelihood_batch(observed= / noise_var=) inside a graph capture needs one ordinary call with "
                                "the same lengths before the capture (leg.Graphed's warm-up is one)")
         _captured_plans[key] = plan
         return plan
@@ -448,6 +448,53 @@ def leg_loglik_batch_reductions_obs(ts, G, A_table, pattern, v, q, plan):
     for b in plan.long:
         s, e = plan.starts[b], plan.starts[b + 1]
         o4, i2 = _leg_pair_obs_raw(ts[s:e], G, A_table, pattern[s:e], v[s:e])
+        out[b, :3] = o4[[0, 1, 3]]
+        out[b, 3] = q[s:e].to(torch.float64).sum()
+        info[b] = i2
+    return out, info
+
+
+def _leg_pair_w_raw(ts, G, basis, weights, v):
+    """cgps_leg_mahal_logdet_pair_w of one series: (out4 fp64, info2), nothing read on the host."""
+    from . import _hip
+    n, d, dt = ts.shape[0], G.shape[0], G.dtype
+    ws = _hip.pair_workspace(n, d, dt, G.device)
+    out = torch.empty(4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_w(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(basis), basis.shape[0],
+                                                       _hip.ptr(weights), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
+                                                       ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    return out, info
+
+
+def leg_loglik_batch_reductions_w(ts, G, basis, weights, v, q, plan):
+    """``leg_loglik_batch_reductions`` of series whose rows each add a term of their own, still ONE launch
+    (cgps_leg_loglik_batch_w): K_b = PEG precision(ts_b, G) + blockdiag(sum_k weights[i, k] basis[k]) over the series'
+    rows, the d x d terms formed in registers and never written.  basis [Kb, d, d] with 1 <= Kb <= 64 and weights
+    [R, Kb], one row per row of the concatenated batch, both device tensors of G's dtype (``observation_weights`` builds
+    them); series longer than BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_w with their slice of the weights.
+    ts, v, q in G's dtype, contiguous.  No autograd graph."""
+    from . import _hip
+    d, dt = G.shape[0], G.dtype
+    if basis.dim() != 3 or tuple(basis.shape[1:]) != (d, d) or not 1 <= basis.shape[0] <= 64:
+        raise ValueError("basis must be [Kb, %d, %d] with 1 <= Kb <= 64, got %s" % (d, d, tuple(basis.shape)))
+    if tuple(weights.shape) != (plan.R, basis.shape[0]):
+        raise ValueError("weights must be [%d, %d] (one row of Kb weights per row of the batch), got %s"
+                         % (plan.R, basis.shape[0], tuple(weights.shape)))
+    if basis.dtype != dt or weights.dtype != dt:
+        raise ValueError("basis and weights must have G's dtype %s, got %s and %s" % (dt, basis.dtype, weights.dtype))
+    if not (basis.is_cuda and weights.is_cuda):
+        raise ValueError("basis and weights must be device tensors")
+    basis, weights = basis.contiguous(), weights.contiguous()
+    out = torch.empty(plan.B, 4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(plan.B, 2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_loglik_batch_w(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, _hip.ptr(G), _hip.ptr(basis),
+                                                  basis.shape[0], _hip.ptr(weights), _hip.ptr(v), _hip.ptr(q), d,
+                                                  _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out), _hip.ptr(info),
+                                                  _hip.stream_ptr()))
+    for b in plan.long:
+        s, e = plan.starts[b], plan.starts[b + 1]
+        o4, i2 = _leg_pair_w_raw(ts[s:e], G, basis, weights[s:e], v[s:e])
         out[b, :3] = o4[[0, 1, 3]]
         out[b, 3] = q[s:e].to(torch.float64).sum()
         info[b] = i2
@@ -597,12 +644,77 @@ class _LegBatchObsFn(torch.autograd.Function):
         return gts, gG, gA, gv, gq, None, None
 
 
-def _log_likelihood_per_series(m, ts, xs, lengths, observed=None):
+def _rows_product(a, b, rows=4096):
+    """a^T b of two tall matrices a [R, p] and b [R, q] (contiguous) as batched products over chunks of ``rows`` rows,
+    added up by one reduction in a fixed order, plus the product of the remainder.  One ``a.T @ b`` with R in the
+    hundreds of thousands and p, q of a few dozen is a single GEMM tile's worth of output with all of R as its inner
+    dimension: 55 ms at R = 514 048, p = 1, q = 25 on an MI355X."""
+    R = a.shape[0]
+    C = R // rows
+    out = a[C * rows:].T @ b[C * rows:]
+    if C:
+        out = out + torch.bmm(a[:C * rows].reshape(C, rows, -1).transpose(1, 2), b[:C * rows].reshape(C, rows, -1)).sum(0)
+    return out
+
+
+class _LegBatchWFn(torch.autograd.Function):
+    """``_LegBatchFn`` with a weighted basis per row.  Forward: cgps_leg_loglik_batch_w (one launch).  Backward: the same
+    concatenated, decoupled system with Rs + sum_k weights[i, k] basis[k] as K's diagonal; the rows' block gradients gR_i
+    go to the basis as sum_i weights[i, k] gR_i and to the weights as <gR_i, basis[k]>, both plain matrix products."""
+
+    @staticmethod
+    def forward(ctx, ts, G, basis, weights, v, q, plan):
+        ctx.plan = plan
+        ctx.save_for_backward(ts, G, basis, weights, v)
+        out, info = leg_loglik_batch_reductions_w(ts.detach(), G.detach(), basis.detach(), weights.detach(), v.detach(),
+                                                  q.detach(), plan)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            _raise_batch_not_pd(info)
+        return out.to(G.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        ts, G, basis, weights, v = ctx.saved_tensors
+        plan = ctx.plan
+        need_ts, need_G, need_b, need_w, need_v, need_q = ctx.needs_input_grad[:6]
+        gts = gG = gb = gw = gv = gq = None
+        gout = gout.to(G.dtype)
+        if need_q:
+            gq = plan.per_row(gout[:, 3])
+        if need_ts or need_G or need_b or need_w or need_v:
+            Kb, d = basis.shape[0], G.shape[0]
+            Rs, Os = _peg_precision_seg(ts, G, plan.cut)
+            gm, gl = plan.per_row(gout[:, 0]), plan.per_row(gout[:, 1])
+            dec, w = cr.decompose_solve(Rs + torch.einsum("nk,kij->nij", weights, basis), Os, v)
+            if need_v:
+                gv = 2 * gm.unsqueeze(-1) * w
+            if need_ts or need_G or need_b or need_w:
+                Sd, So = cr.inverse_blocks(dec)
+                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
+                if need_b:
+                    gb = _rows_product(weights, gR.reshape(-1, d * d)).reshape(Kb, d, d)
+                if need_w:
+                    gw = gR.reshape(-1, d * d) @ basis.reshape(Kb, d * d).T
+                if need_ts or need_G:
+                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
+                    if plan.R > 1:           # (one row: its block is I whatever G and ts are)
+                        gs = plan.per_row(gout[:, 2])
+                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
+                        gR = gR + gs.view(-1, 1, 1) * Sd0
+                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
+                    gG, gts = _peg_precision_adjoint_seg(ts, G, plan.cut, gR, gO, need_ts)
+                    if not need_G:
+                        gG = None
+        return gts, gG, gb, gw, gv, gq, None
+
+
+def _log_likelihood_per_series(m, ts, xs, lengths, observed=None, noise_var=None):
     """One ``log_likelihood`` per series: d = 8, fp64 d = 6 and CPU tensors (no batched kernel there)."""
     outs, s = [], 0
     for b, n in enumerate(lengths):
         try:
-            outs.append(log_likelihood(m, ts[s:s + n], xs[s:s + n], None if observed is None else observed[s:s + n]))
+            outs.append(log_likelihood(m, ts[s:s + n], xs[s:s + n], None if observed is None else observed[s:s + n],
+                                       None if noise_var is None else noise_var[s:s + n]))
         except cr.NotPSDError as e:
             raise cr.NotPSDError("LEG batch: series %d: %s" % (b, e)) from None
         s += n
@@ -626,7 +738,24 @@ def _batch_observed(observed, xs_shape, dense):
     return observed
 
 
-def log_likelihood_batch(m, ts, xs, lengths=None, observed=None):
+def _batch_noise_var(noise_var, xs_shape, dense):
+    """``noise_var`` in the layout of the batch's xs, flattened to the rows of the concatenated batch ([R, obs] or [R]);
+    raises ValueError before anything is launched."""
+    if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
+        raise ValueError("noise_var must be a floating-point tensor")
+    xs_shape = tuple(xs_shape)
+    if dense:
+        if tuple(noise_var.shape) not in (xs_shape, xs_shape[:2]):
+            raise ValueError("dense layout wants noise_var[B, n, obs_dim] or noise_var[B, n] like xs %s, got %s"
+                             % (xs_shape, tuple(noise_var.shape)))
+        return noise_var.reshape((xs_shape[0] * xs_shape[1],) + tuple(noise_var.shape[2:]))
+    if tuple(noise_var.shape) not in (xs_shape, xs_shape[:1]):
+        raise ValueError("ragged layout wants noise_var[sum(lengths), obs_dim] or noise_var[sum(lengths)] like xs %s, got %s"
+                         % (xs_shape, tuple(noise_var.shape)))
+    return noise_var
+
+
+def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None):
     """log p(xs_b | ts_b) of the LEG model for B independent series (models.py:301-372 for each), as a [B] tensor of
     the model's dtype; ``out.sum()`` is what a training step over the batch minimises.
 
@@ -647,21 +776,42 @@ def log_likelihood_batch(m, ts, xs, lengths=None, observed=None):
     batch of series of unequal true length is the mask whose tail rows are False (the padded time stamps must still
     increase); a series that observes nothing at all has log-likelihood 0.  Still one launch
     (cgps_leg_loglik_batch_obs; ``observation_tables`` for the operands), the same gradients, the same fallbacks and
-    errors, and nothing read on the host when ``cr.CHECK_POSITIVE_DEFINITE`` is off."""
+    errors, and nothing read on the host when ``cr.CHECK_POSITIVE_DEFINITE`` is off.
+
+    ``noise_var`` (floating point, >= 0, in the layout of xs: [B, n, obs_dim] or [B, n] for one value per row; ragged
+    [sum(lengths), obs_dim] or [sum(lengths)]; None: none, and exactly the calls above): per-point error bars, every
+    slot being what ``log_likelihood(..., noise_var=)`` gives for that series -- the noise covariance of row i is
+    Lambda Lambda^T + 1e-9 I + diag(noise_var[i]).  Combines with ``observed``; entries of noise_var that are not
+    observed are ignored whatever they hold (NaN included).  Still one launch (cgps_leg_loglik_batch_w: every row's term
+    is built in registers from obs_dim (obs_dim + 1) / 2 numbers; ``observation_weights`` for the operands),
+    differentiable in noise_var as well, the same fallbacks and errors, and nothing read on the host when
+    ``cr.CHECK_POSITIVE_DEFINITE`` is off."""
     dense = lengths is None
     xs_shape = xs.shape
     ts, xs, lengths = _batch_layout(ts, xs, lengths)
-    if observed is not None:
-        observed = _batch_observed(observed, xs_shape, dense)
+    if observed is not None or noise_var is not None:
+        if observed is not None:
+            observed = _batch_observed(observed, xs_shape, dense)
+        if noise_var is not None:
+            noise_var = _batch_noise_var(noise_var, xs_shape, dense)
         if xs.shape[1] != m.B.shape[0]:
             raise ValueError("xs must have %d channels, got %s" % (m.B.shape[0], tuple(xs_shape)))
-        observed = _observed_2d(observed, xs.shape[1])
+        if observed is not None:
+            observed = _observed_2d(observed, xs.shape[1])
     G = m.G
     dt = G.dtype
     if not lengths:
         return torch.empty(0, dtype=dt, device=ts.device)
     if not batch_supported(ts, G):
-        return _log_likelihood_per_series(m, ts, xs, lengths, observed)
+        return _log_likelihood_per_series(m, ts, xs, lengths, observed, noise_var)
+    if noise_var is not None:
+        plan = _cached_batch_plan(lengths, G.device)
+        basis, weights, c_rows, xl, xz = _noise_operands(m, ts, xs, observed, noise_var)
+        v = (xl @ m.B).to(dt).contiguous()
+        q = ((xl * xz).sum(-1) + c_rows).to(dt).contiguous()             # the observation constant rides in sum q
+        red = _LegBatchWFn.apply(ts.to(dt).contiguous(), G.contiguous(), basis.to(dt).contiguous(),
+                                 weights.to(dt).contiguous(), v, q, plan)
+        return -0.5 * ((red[:, 3] - red[:, 0]) + (red[:, 1] - red[:, 2]))
     if observed is not None:
         plan = _cached_batch_plan(lengths, G.device)
         pattern, idx, A_table, c_table, xl, xz = _observed_operands(m, ts, xs, observed)

@@ -254,6 +254,19 @@ int cgps_leg_loglik_batch_obs(const void* ts, const int64_t* offsets, int64_t B,
                               int P, const unsigned char* pattern, const void* v, const void* q, int d, int dtype,
                               int64_t max_rows, double* out4, int* info2, void* stream);
 
+/* cgps_leg_loglik_batch for series whose rows each have a diagonal term of their own (per-observation noise variances,
+ * many series at once): row i of the CONCATENATED batch adds a weighted sum of Kb basis blocks shared by all rows,
+ *   K_b = PEG precision(ts_b, G) + blockdiag(sum_k weights[offsets[b] + r][k] basis[k]),  r = 0 .. n_b - 1.
+ * basis[Kb][d][d], 1 <= Kb <= 64; weights[sum n_b][Kb] in the dtype of the call (DEVICE memory); v and q are the
+ * caller's, built with the same per-row terms (q carries the rows' observation constants).  The d x d terms are formed
+ * in registers and never written.  The prior-precision system (out4[b][2]) adds nothing, reads neither basis nor
+ * weights, and its value is that of cgps_leg_loglik_batch bit for bit.  out4, info2, max_rows and error codes: those of
+ * cgps_leg_loglik_batch; a null basis or weights with B > 0 and Kb outside 1..64 are CGPS_ERR_ARG before anything is
+ * launched; B = 0 returns CGPS_OK.  No workspace. */
+int cgps_leg_loglik_batch_w(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* basis, int Kb,
+                            const void* weights, const void* v, const void* q, int d, int dtype, int64_t max_rows,
+                            double* out4, int* info2, void* stream);
+
 /* cgps_peg_precision of several series concatenated (models.py:181-239 for each): cut[N-1] (device bytes),
  * cut[g] != 0 when rows g and g+1 belong to different series.  Such a gap is never evaluated, its coupling
  * block Os[g] is 0 and it adds nothing to Rs[g] or Rs[g+1]: the blocks of a block-diagonal system of

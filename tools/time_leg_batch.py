@@ -13,6 +13,14 @@ backward of out.sum() with all four matrices trainable, for B in --batches.
         series-cut mask: about R bytes from the host) between calls, the fully observed call builds it every time;
         *_obs_us is the call as users get it, *_obs_cold_us the call with the plan cache emptied first, so that both
         sides build a plan, and *_ratio_to_full is taken from the latter
+    python tools/time_leg_batch.py --noise [--batches 1,64,1024]
+        every entry with a noise variance of its own, uniform in [0, 1], at obs_dim 1 (the golden model) and obs_dim 3
+        (its B and Lambda extended, see noise_model): log_likelihood_batch(noise_var=s) against (a) a Python loop of
+        log_likelihood(noise_var=) and (b) the fully observed log_likelihood_batch on the same shapes, forward and
+        forward + backward, the batched calls alternated inside every repetition.  kernel_* are the launches alone
+        (leg_loglik_batch_reductions_w against leg_loglik_batch_reductions on operands built beforehand); the other
+        figures are whole calls, the torch work that builds weights, v, q and c included; *_cold empties the plan cache
+        first, as under --observed
 """
 import argparse
 import json
@@ -140,6 +148,103 @@ def observed_row(m, ts, xs, fraction, reps, loop_reps):
     return row
 
 
+def noise_model(m, xs, obs_dim):
+    """obs_dim 1: the golden model and data.  obs_dim 3: channel c observes the golden loading rotated by c places and
+    scaled by 1 - c / 4, its own noise 1 + c / 2 times the golden one, correlated with its neighbour (Lambda lower
+    bidiagonal); the data of channel c are the series of c places further on in the batch."""
+    if obs_dim == 1:
+        return m, xs
+    Bm = torch.cat([(1 - c / 4) * torch.roll(m.B, c, 1) for c in range(obs_dim)])
+    lam = float(m.Lambda[0, 0])
+    Lm = torch.diag(torch.tensor([lam * (1 + c / 2) for c in range(obs_dim)], dtype=m.B.dtype))
+    Lm = Lm + 0.3 * lam * torch.diag(torch.ones(obs_dim - 1, dtype=m.B.dtype), -1)
+    return leg.LEGMatrices(m.N, m.R, Bm, Lm.to(m.B.device)), torch.cat([torch.roll(xs, c, 0) for c in range(obs_dim)], -1)
+
+
+def noise_row(m, ts, xs, obs_dim, reps, loop_reps):
+    """The batch with per-observation noise against its two baselines: kernels alone, forward, forward + backward."""
+    B, n = ts.shape
+    m, xs = noise_model(m, xs, obs_dim)
+    s = torch.rand(xs.shape, generator=torch.Generator().manual_seed(B), dtype=xs.dtype).cuda()
+    with torch.no_grad():
+        ref = torch.stack([leg.log_likelihood(m, ts[b], xs[b], noise_var=s[b]) for b in range(B)])
+        out = leg.log_likelihood_batch(m, ts, xs, noise_var=s)
+    err = float(((out - ref).abs() / ref.abs().clamp_min(1.0)).max())
+    assert err < 1e-9, err
+    mg = trainable(m)
+
+    def zero():
+        for p in (mg.N, mg.R, mg.B, mg.Lambda):
+            p.grad = None
+
+    # the launches alone, on operands built once
+    plan = leg._BatchPlan([n] * B, ts.device)
+    with torch.no_grad():
+        tsf, xsf = ts.reshape(-1).contiguous(), xs.reshape(B * n, obs_dim)
+        G = m.G.contiguous()
+        basis, weights, c_rows, xl, xz = leg._noise_operands(m, tsf, xsf, None, s.reshape(B * n, obs_dim))
+        basis, weights = basis.contiguous(), weights.contiguous()
+        v = (xl @ m.B).contiguous()
+        q = ((xl * xz).sum(-1) + c_rows).contiguous()
+        A = (m.B.T @ m.LLT_inv @ m.B).contiguous()
+
+    def kernel_w():
+        leg.leg_loglik_batch_reductions_w(tsf, G, basis, weights, v, q, plan)
+
+    def kernel_full():
+        leg.leg_loglik_batch_reductions(tsf, G, A, v, q, plan)
+
+    def fwd_w():
+        with torch.no_grad():
+            leg.log_likelihood_batch(m, ts, xs, noise_var=s)
+
+    def fwd_w_cold():
+        leg._plans.clear()
+        fwd_w()
+
+    def fwd_full():
+        with torch.no_grad():
+            leg.log_likelihood_batch(m, ts, xs)
+
+    def fwd_loop():
+        with torch.no_grad():
+            for b in range(B):
+                leg.log_likelihood(m, ts[b], xs[b], noise_var=s[b])
+
+    def fb_w():
+        zero()
+        leg.log_likelihood_batch(mg, ts, xs, noise_var=s).sum().backward()
+
+    def fb_w_cold():
+        leg._plans.clear()
+        fb_w()
+
+    def fb_full():
+        zero()
+        leg.log_likelihood_batch(mg, ts, xs).sum().backward()
+
+    def fb_loop():
+        zero()
+        for b in range(B):
+            leg.log_likelihood(mg, ts[b], xs[b], noise_var=s[b]).backward()
+
+    row = {"B": B, "rows": n, "d": 5, "dtype": "float64", "noise": True, "obs_dim": obs_dim, "Kb": int(basis.shape[0]),
+           "max_rel_err_vs_loop": err}
+    got = timed_alternating({"kernel_w": kernel_w, "kernel_full": kernel_full}, reps, 3)
+    got.update(timed_alternating({"fwd_w": fwd_w, "fwd_w_cold": fwd_w_cold, "fwd_full": fwd_full}, reps, 3))
+    got.update(timed_alternating({"fwdbwd_w": fb_w, "fwdbwd_w_cold": fb_w_cold, "fwdbwd_full": fb_full}, reps, 3))
+    got["fwd_loop"] = timed(fwd_loop, loop_reps, 1)
+    got["fwdbwd_loop"] = timed(fb_loop, loop_reps, 1)
+    for name, (med, low) in got.items():
+        row[name + "_us"], row[name + "_min_us"] = med, low
+    row["kernel_ratio_to_full"] = row["kernel_w_us"] / row["kernel_full_us"]
+    for k in ("fwd", "fwdbwd"):
+        row[k + "_speedup_vs_loop"] = row[k + "_loop_us"] / row[k + "_w_us"]
+        row[k + "_ratio_to_full"] = row[k + "_w_cold_us"] / row[k + "_full_us"]        # a plan built on both sides
+        row[k + "_cached_ratio_to_full"] = row[k + "_w_us"] / row[k + "_full_us"]
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="1,64,1024")
@@ -148,10 +253,17 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--observed", type=float, default=None, metavar="FRACTION")
+    ap.add_argument("--noise", action="store_true")
     a = ap.parse_args()
     res = []
     for B in [int(x) for x in a.batches.split(",")]:
         m, ts, xs = workload(B)
+        if a.noise:
+            for obs_dim in (1, 3):
+                row = noise_row(m, ts, xs, obs_dim, a.reps, a.loop_reps if B > 64 else a.reps)
+                print(json.dumps(row), flush=True)
+                res.append(row)
+            continue
         if a.observed is not None:
             row = observed_row(m, ts, xs, a.observed, a.reps, a.loop_reps if B > 64 else a.reps)
             print(json.dumps(row), flush=True)
