@@ -235,11 +235,23 @@ __device__ __forceinline__ bool gap_terms(T dt, const T (&G)[D][D], bool want_ri
 // independent series (cgps_peg_precision_seg).  Such a gap is never evaluated -- it may be zero or negative --
 // its coupling block is 0 and it adds nothing to either diagonal block; with cut == nullptr the arithmetic is
 // the one-series kernel's, unchanged.
-template <typename T, int D>
+//
+// TERM (cgps_leg_posterior_blocks_seg): a row's diagonal term of the POSTERIOR precision, added to the finished PEG
+// block as the last operation before its store, so that K's diagonal is written once instead of Rs being written, read,
+// added to and written again.  PEG_TERM_NONE: nothing (the two assembly entry points: none of the three arguments is
+// read, and every difference below is an `if constexpr`).  PEG_TERM_PLAIN: the one block term[d][d].  PEG_TERM_TABLE:
+// entry rows[i] (a byte) of term[entries][d][d], the index clamped to entries - 1 as leg_obs_block clamps it.
+// PEG_TERM_WEIGHTED: sum_k w[i][k] term[k] with w = rows as T[N][entries], summed over k in registers and added once.
+constexpr int PEG_TERM_NONE = 0, PEG_TERM_PLAIN = 1, PEG_TERM_TABLE = 2, PEG_TERM_WEIGHTED = 3;
+
+template <typename T, int D, int TERM = PEG_TERM_NONE>
 __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __restrict__ ts, const T* __restrict__ Gg,
                                                                     int64_t N, T* __restrict__ Rs, T* __restrict__ Os,
                                                                     int* __restrict__ info,
-                                                                    const unsigned char* __restrict__ cut = nullptr) {
+                                                                    const unsigned char* __restrict__ cut = nullptr,
+                                                                    const T* __restrict__ term = nullptr,
+                                                                    const void* __restrict__ rows = nullptr,
+                                                                    int entries = 0) {
   constexpr int DD = D * D;
   const int64_t i = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
   if (i >= N) return;
@@ -277,6 +289,39 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
     for (int a = 0; a < D; ++a)
 #pragma unroll
       for (int b = 0; b < D; ++b) R[a][b] += c1[a][b];
+  }
+  if constexpr (TERM == PEG_TERM_PLAIN || TERM == PEG_TERM_TABLE) {
+    const T* __restrict__ tb = term;
+    if constexpr (TERM == PEG_TERM_TABLE) {
+      const int p = (int)static_cast<const unsigned char*>(rows)[i];
+      tb = term + (size_t)(p < entries - 1 ? p : entries - 1) * DD;
+    }
+    T A[D][D];
+    load_block<T, D>(tb, A);
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = 0; b < D; ++b) R[a][b] += A[a][b];
+  } else if constexpr (TERM == PEG_TERM_WEIGHTED) {
+    const T* __restrict__ w = static_cast<const T*>(rows) + i * (int64_t)entries;
+    T S[D][D];
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = 0; b < D; ++b) S[a][b] = T(0);
+#pragma unroll 1
+    for (int k = 0; k < entries; ++k) {
+      const T wk = w[k];
+      const T* __restrict__ bk = term + (size_t)k * DD;
+#pragma unroll
+      for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) S[a][b] = fmaT(wk, bk[a * D + b], S[a][b]);
+    }
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int b = 0; b < D; ++b) R[a][b] += S[a][b];
   }
   store_block<T, D>(Rs + i * DD, R);
   if (!ok) report_fail(info, i);
@@ -324,16 +369,15 @@ __device__ __forceinline__ void leg_forecast(const T (&E)[D][D], const T* __rest
   }
 }
 
+// One target of one series: ts[n] the series' own time stamps, mu[n][d], Pd[n][d][d], Co[n-1][d][d] its own posterior,
+// t the target.  Reads rows 0 .. n-1 and off-diagonal blocks 0 .. n-2 of what it is handed and nothing else, so a caller
+// that hands it a slice of a concatenated batch (leg_intercast_seg_kernel) never touches a neighbouring series.
 template <typename T, int D>
-__global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __restrict__ ts, int64_t n,
-                                                                    const T* __restrict__ tt, int64_t p,
-                                                                    const T* __restrict__ Gg, const T* __restrict__ mu,
-                                                                    const T* __restrict__ Pd, const T* __restrict__ Co,
-                                                                    T* __restrict__ out_mean, T* __restrict__ out_cov) {
+__device__ __forceinline__ void leg_intercast_target(const T* __restrict__ ts, int64_t n, const T* __restrict__ Gg,
+                                                     const T* __restrict__ mu, const T* __restrict__ Pd,
+                                                     const T* __restrict__ Co, const T t, T* __restrict__ out_mean,
+                                                     T* __restrict__ out_cov) {
   constexpr int DD = D * D;
-  const int64_t k = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
-  if (k >= p) return;
-  const T t = tt[k];
   int64_t lo = 0, hi = n;                          // first index with ts[idx] >= t (torch.searchsorted, right = False)
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;
@@ -348,11 +392,14 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __r
   const bool at_first = idx == 0 && close(t, t_first);
   const bool at_last = idx > 0 && close(t, t_last);
   const bool back = idx == 0 && !at_first, fwd = idx == n && !at_last;
-  T mean[D], cov[D][D];
+  // (every branch stores its own result: nothing of the d + d*d values is carried across the branches)
   if (at_first || at_last) {
     const int64_t r = at_first ? 0 : n - 1;
+    T mean[D], cov[D][D];
     load_vec<T, D>(mu + r * D, mean);
     load_block<T, D>(Pd + r * DD, cov);
+    store_vec<T, D>(out_mean, mean);
+    store_block<T, D>(out_cov, cov);
   } else {
     T G[D][D];
 #pragma unroll
@@ -377,9 +424,11 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __r
           for (int b = a + 1; b < D; ++b) { const T v = E[a][b]; E[a][b] = E[b][a]; E[b][a] = v; }
       }
       const int64_t r = back ? 0 : n - 1;
-      T m0[D];
+      T m0[D], mean[D], cov[D][D];
       load_vec<T, D>(mu + r * D, m0);
       leg_forecast<T, D>(E, m0, Pd + r * DD, mean, cov);
+      store_vec<T, D>(out_mean, mean);
+      store_block<T, D>(out_cov, cov);
     } else {
       int64_t j = idx < 1 ? 1 : idx;
       if (j > n - 1) j = n - 1;
@@ -417,7 +466,7 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __r
           for (int m = 0; m < D; ++m) s = fmaT(-W[a][m], E3[m][b], s);
           Ma[a][b] = s;
         }
-      T m0[D], m1[D];
+      T m0[D], m1[D], mean[D], cov[D][D];
       load_vec<T, D>(mu + (j - 1) * D, m0);
       load_vec<T, D>(mu + j * D, m1);
 #pragma unroll
@@ -469,10 +518,45 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __r
           }
           cov[a][b] = c;
         }
+      store_vec<T, D>(out_mean, mean);
+      store_block<T, D>(out_cov, cov);
     }
   }
-  store_vec<T, D>(out_mean + k * D, mean);
-  store_block<T, D>(out_cov + k * DD, cov);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __restrict__ ts, int64_t n,
+                                                                    const T* __restrict__ tt, int64_t p,
+                                                                    const T* __restrict__ Gg, const T* __restrict__ mu,
+                                                                    const T* __restrict__ Pd, const T* __restrict__ Co,
+                                                                    T* __restrict__ out_mean, T* __restrict__ out_cov) {
+  const int64_t k = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
+  if (k >= p) return;
+  leg_intercast_target<T, D>(ts, n, Gg, mu, Pd, Co, tt[k], out_mean + k * D, out_cov + k * (D * D));
+}
+
+// The same for B series concatenated (cgps_leg_intercast_seg): series b is rows roff[b] .. roff[b+1]-1 of ts, mu, Pd
+// (and of Co, whose entry at a series' last row is the cut gap and is never read), its targets are
+// tt[toff[b] .. toff[b+1]-1].  One lane per target: it finds its series as the one b with toff[b] <= k < toff[b+1]
+// (binary search; series without targets are stepped over), then works on that series' slices alone.
+template <typename T, int D>
+__global__ __launch_bounds__(LEG_THREADS) void leg_intercast_seg_kernel(
+    const T* __restrict__ ts, const int64_t* __restrict__ roff, const T* __restrict__ tt,
+    const int64_t* __restrict__ toff, int64_t B, int64_t p, const T* __restrict__ Gg, const T* __restrict__ mu,
+    const T* __restrict__ Pd, const T* __restrict__ Co, T* __restrict__ out_mean, T* __restrict__ out_cov) {
+  constexpr int DD = D * D;
+  const int64_t k = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
+  if (k >= p) return;
+  int64_t lo = 0, hi = B;                          // first b with toff[b + 1] > k
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (toff[mid + 1] <= k) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= B) return;                             // (offsets that do not cover p targets: nothing is written)
+  const int64_t r0 = roff[lo], n = roff[lo + 1] - r0;
+  if (n < 1) return;                               // (a series needs a row)
+  leg_intercast_target<T, D>(ts + r0, n, Gg, mu + r0 * D, Pd + r0 * DD, Co + r0 * DD, tt[k], out_mean + k * D,
+                             out_cov + k * DD);
 }
 
 // ---- adjoint of the assembly (training through the path, reference models.py:374-381) -----------------

@@ -88,4 +88,60 @@ int cgps_leg_intercast(const void* ts, int64_t n, const void* target_ts, int64_t
   });
 }
 
+int cgps_leg_intercast_seg(const void* ts, const int64_t* row_offsets, const void* target_ts, const int64_t* target_offsets,
+                           int64_t B, int64_t P, const void* G, int d, int dtype, const void* ip_mean,
+                           const void* ip_cov_diag, const void* ip_cov_offdiag, void* out_mean, void* out_cov,
+                           void* stream) {
+  if (B < 0 || P < 0) return fail(CGPS_ERR_ARG, "cgps_leg_intercast_seg: B < 0 or P < 0");
+  if (B == 0 || P == 0) return CGPS_OK;
+  // (ip_cov_offdiag may be null: a batch of one one-row series has no off-diagonal block)
+  if (!ts || !row_offsets || !target_ts || !target_offsets || !G || !ip_mean || !ip_cov_diag || !out_mean || !out_cov)
+    return fail(CGPS_ERR_ARG, "cgps_leg_intercast_seg: null pointer");
+  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_intercast_seg: B = %lld series, at most 2^31 - 1", (long long)B);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int64_t nb = (P + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+    if (nb > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_intercast_seg: P = %lld targets, too many for one launch", (long long)P);
+    hipLaunchKernelGGL((cgps::leg_intercast_seg_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEG_THREADS), 0,
+                       (hipStream_t)stream, (const T*)ts, row_offsets, (const T*)target_ts, target_offsets, B, P,
+                       (const T*)G, (const T*)ip_mean, (const T*)ip_cov_diag, (const T*)ip_cov_offdiag, (T*)out_mean,
+                       (T*)out_cov);
+    return check_launch("leg_intercast_seg");
+  });
+}
+
+int cgps_leg_posterior_blocks_seg(const void* ts, const void* G, const unsigned char* cut, int64_t N, int d, int dtype,
+                                  int source, const void* term, int entries, const void* rows, void* K_Rs, void* Os,
+                                  int* info, void* stream) {
+  if (bad_common(N, d) || !ts || !G || !term || !K_Rs || (N > 1 && !Os) || !info)
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_seg: null pointer or N < 1");
+  if (source < CGPS_ROWS_PLAIN || source > CGPS_ROWS_WEIGHTED)
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_seg: source = %d, outside 0..2", source);
+  if (source != CGPS_ROWS_PLAIN && !rows) return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_seg: null pattern or weights");
+  if (source == CGPS_ROWS_TABLE && (entries < 1 || entries > 256))
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_seg: %d table entries, outside 1..256", entries);
+  if (source == CGPS_ROWS_WEIGHTED && (entries < 1 || entries > 64))
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_seg: Kb = %d basis blocks, outside 1..64", entries);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nb = (N + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+    if (nb > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_seg: N = %lld rows, too many for one launch", (long long)N);
+    (void)hipMemsetAsync(info, 0, sizeof(int), st);
+    const dim3 grid((unsigned)nb), block(cgps::LEG_THREADS);
+    if (source == CGPS_ROWS_PLAIN)
+      hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D, cgps::PEG_TERM_PLAIN>), grid, block, 0, st, (const T*)ts, (const T*)G,
+                         N, (T*)K_Rs, (T*)Os, info, cut, (const T*)term, rows, entries);
+    else if (source == CGPS_ROWS_TABLE)
+      hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D, cgps::PEG_TERM_TABLE>), grid, block, 0, st, (const T*)ts, (const T*)G,
+                         N, (T*)K_Rs, (T*)Os, info, cut, (const T*)term, rows, entries);
+    else
+      hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D, cgps::PEG_TERM_WEIGHTED>), grid, block, 0, st, (const T*)ts,
+                         (const T*)G, N, (T*)K_Rs, (T*)Os, info, cut, (const T*)term, rows, entries);
+    return check_launch("leg_posterior_blocks_seg");
+  });
+}
+
 }  // extern "C"

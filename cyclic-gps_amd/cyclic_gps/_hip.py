@@ -16,6 +16,7 @@ F32, F64 = 0, 1
 OP_MAHAL_LOGDET, OP_DECOMPOSE, OP_HALFSOLVE, OP_BACKSOLVE, OP_SOLVE, OP_LOGDET_FACTOR, OP_INVERSE_BLOCKS, \
     OP_MAHAL_LOGDET_LEVELWISE, OP_DECOMPOSE_SOLVE = range(9)
 MAX_LEVELS = 64
+ROWS_PLAIN, ROWS_TABLE, ROWS_WEIGHTED = range(3)
 
 _lib = None
 
@@ -56,6 +57,8 @@ _SIGNATURES = {
     "cgps_peg_precision_seg": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "cgps_peg_precision_adjoint_seg": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "cgps_leg_intercast": (_int, [_vp, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cgps_leg_intercast_seg": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cgps_leg_posterior_blocks_seg": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "cgps_record_elems": (_int, [_int, _int, ctypes.POINTER(_i64)]),
     "cgps_shard_reduce": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp, _vp, _vp]),
     "cgps_finish_records": (_int, [_vp, _sz, _vp, _sz, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),

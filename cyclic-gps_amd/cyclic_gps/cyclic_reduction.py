@@ -89,7 +89,9 @@ def _raise_if_not_pd(info, *blocks):
                 nan = int(torch.isnan(t).sum().item()) if t is not None and t.numel() else 0
                 if nan:
                     raise NanError("%d of %d elements of the %s tensor are NaN." % (nan, t.numel(), tuple(t.shape)))
-            raise NotPSDError("block row %d is not positive definite" % (bad - 1))
+            err = NotPSDError("block row %d is not positive definite" % (bad - 1))
+            err.row = bad - 1         # (for callers that name the row in terms of their own: leg.insample_posterior_batch)
+            raise err
 
 
 class CRDecomp(tuple):

@@ -282,6 +282,14 @@ class _BatchPlan:
     def per_row(self, g):
         return g.repeat_interleave(self.lens, output_size=self.R)
 
+    def boundary_rows(self):
+        """Device int64 [B-1]: the gaps (rows of an off-diagonal array) that lie between two series.  Built at the first
+        use (a copy from the host: not inside a graph capture) and kept."""
+        rows = getattr(self, "_boundary_rows", None)
+        if rows is None:
+            rows = self._boundary_rows = (torch.tensor(self.starts[1:-1], dtype=torch.int64) - 1).to(self.offsets.device)
+        return rows
+
 
 PLAN_CACHE_SIZE = 8
 _plans = {}                 # (lengths, device) -> plan, least recently used first
@@ -292,29 +300,33 @@ def _capturing(device):
     return torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing()
 
 
-def _cached_batch_plan(lengths, device):
+def _cached_batch_plan(lengths, device, make=None):
     """The plan of these lengths, built once: a repeated call -- a training loop over one data set, a graph capture
     after its warm-up -- then copies nothing from the host.  The PLAN_CACHE_SIZE most recently used plans are kept.
     A plan handed out while the current stream is being captured is kept for as long as the process lives: the
     captured kernels hold the addresses of its device tensors and nothing else would own them, whoever made the
     capture and whatever they kept of its results.  A capture cannot build a plan (that is a copy from the host):
-    RuntimeError unless an ordinary call with the same lengths came first, as ``Graphed``'s warm-up is."""
+    RuntimeError unless an ordinary call with the same lengths came first, as ``Graphed``'s warm-up is.  ``make``
+    (None: ``_BatchPlan``) is another plan class with caches of its own, ``make.plans`` and ``make.captured``
+    (``predict._TargetPlan``): the kinds do not compete for slots."""
     key = (tuple(lengths), str(device))
-    plan = _captured_plans.get(key)
+    plans, captured = (_plans, _captured_plans) if make is None else (make.plans, make.captured)
+    plan = captured.get(key)
     if plan is not None:
         return plan
-    plan = _plans.pop(key, None)                                 # (put back below, as the most recent)
+    plan = plans.pop(key, None)                                  # (put back below, as the most recent)
     if _capturing(device):
         if plan is None:
-            raise RuntimeError("log_likelihood_batch(observed= / noise_var=) inside a graph capture needs one ordinary call with "
-                               "the same lengths before the capture (leg.Graphed's warm-up is one)")
-        _captured_plans[key] = plan
+            raise RuntimeError("a batched call inside a graph capture (log_likelihood_batch(observed= / noise_var=), the batched "
+                               "posterior and predictions) needs one ordinary call with the same lengths before the capture "
+                               "(leg.Graphed's warm-up is one)")
+        captured[key] = plan
         return plan
     if plan is None:
-        plan = _BatchPlan(lengths, device)
-        while len(_plans) >= PLAN_CACHE_SIZE:
-            _plans.pop(next(iter(_plans)))
-    _plans[key] = plan
+        plan = (make or _BatchPlan)(lengths, device)
+        while len(plans) >= PLAN_CACHE_SIZE:
+            plans.pop(next(iter(plans)))
+    plans[key] = plan
     return plan
 
 
@@ -1235,6 +1247,197 @@ def insample_posterior(m, ts, xs, observed=None, noise_var=None):
         dec = cr.decompose(Rs=K_Rs, Os=K_Os)
         mean = cr.solve(dec, v)
     return mean, cr.inverse_blocks(dec)
+
+
+# ---- the posterior of many series at once ------------------------------------------------------------------------
+def _batch_posterior_args(m, ts, xs, lengths, observed, noise_var):
+    """Everything ``insample_posterior_batch`` checks before it launches anything: (ts [R], xs [R, obs], lengths,
+    observed [R, obs] or None, noise_var [R, obs] / [R] or None, dense, (B, n) of the dense layout or None)."""
+    dense = lengths is None
+    xs_shape = tuple(xs.shape)
+    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    if xs.shape[1] != m.B.shape[0]:
+        raise ValueError("xs must have %d channels, got %s" % (m.B.shape[0], xs_shape))
+    if observed is not None:
+        observed = _observed_2d(_batch_observed(observed, xs_shape, dense), xs.shape[1])
+    if noise_var is not None:
+        noise_var = _batch_noise_var(noise_var, xs_shape, dense)
+        if noise_var.dim() == 2 and noise_var.shape[1] != xs.shape[1]:
+            raise ValueError("noise_var must have %d channels, got %s" % (xs.shape[1], tuple(noise_var.shape)))
+    return ts, xs, lengths, observed, noise_var, dense, (xs_shape[:2] if dense else None)
+
+
+def _posterior_batch_supported(ts, G):
+    """The concatenated system runs on the general kernels: GPU tensors, every rank 1..8, both precisions."""
+    return G.is_cuda and ts.is_cuda and G.dtype in (torch.float32, torch.float64) and 1 <= G.shape[0] <= 8
+
+
+def _series_of_row(plan, row):
+    """(series, local row) of a row of the concatenated batch."""
+    import bisect
+    b = min(max(bisect.bisect_right(plan.starts, row) - 1, 0), plan.B - 1)
+    return b, row - plan.starts[b]
+
+
+def _posterior_blocks_seg(ts, G, cut, source, term, rows=None):
+    """(K_Rs, Os, info) of concatenated series with every row's term added inside the assembly kernel
+    (cgps_leg_posterior_blocks_seg): K's diagonal blocks are written once.  source: _hip.ROWS_PLAIN (term [d, d]),
+    ROWS_TABLE (term [entries, d, d], rows = pattern bytes [n]) or ROWS_WEIGHTED (term = basis [Kb, d, d], rows = weights
+    [n, Kb]); cut may be None (one series).  Contiguous operands of G's dtype.  No autograd graph."""
+    from . import _hip
+    n, d = ts.shape[0], G.shape[0]
+    entries = 0 if source == _hip.ROWS_PLAIN else term.shape[0]
+    K_Rs = torch.empty(n, d, d, dtype=G.dtype, device=G.device)
+    Os = torch.empty(max(n - 1, 0), d, d, dtype=G.dtype, device=G.device)
+    info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_posterior_blocks_seg(
+        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), n, d, _hip.dtype_code(G.dtype), source, _hip.ptr(term), entries,
+        _hip.ptr(rows), _hip.ptr(K_Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
+    return K_Rs, Os, info
+
+
+def _posterior_system_batch(m, ts, xs, observed, noise_var, plan):
+    """(K_Rs, K_Os, v) of the concatenated, block-diagonal posterior system of all series: ``_posterior_system`` with the
+    series-aware assembly (zero coupling across a series boundary, the gap there never evaluated) and the rows' terms
+    added inside it (cgps_leg_posterior_blocks_seg).  CGPS_LEG_BLOCKS_COMPOSED=1 takes the composition it replaces
+    instead -- cgps_peg_precision_seg, then the gather or einsum and the add as torch passes -- for A/B timing.  With
+    ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series."""
+    from . import _hip
+    G = m.G
+    dt = G.dtype
+    if noise_var is not None:
+        basis, weights, _, xl, _ = _noise_operands(m, ts, xs, observed, noise_var)
+        source, term, rows = _hip.ROWS_WEIGHTED, basis.to(dt).contiguous(), weights.to(dt).contiguous()
+    elif observed is not None:
+        pattern, _, A_table, _, xl, _ = _observed_operands(m, ts, xs, observed)
+        source, term, rows = _hip.ROWS_TABLE, A_table.to(dt).contiguous(), pattern.contiguous()
+    else:
+        Li = m.LLT_inv
+        xl = xs @ Li
+        source, term, rows = _hip.ROWS_PLAIN, (m.B.T @ Li @ m.B).to(dt).contiguous(), None
+    v = (xl @ m.B).to(dt).contiguous()
+    tsc, Gc = ts.to(dt).contiguous(), G.contiguous()
+    if os.environ.get("CGPS_LEG_BLOCKS_COMPOSED") == "1":
+        R, d = plan.R, G.shape[0]
+        Rs = torch.empty(R, d, d, dtype=dt, device=G.device)
+        Os = torch.empty(max(R - 1, 0), d, d, dtype=dt, device=G.device)
+        info = torch.zeros(1, dtype=torch.int32, device=G.device)
+        _hip.check(_hip.lib().cgps_peg_precision_seg(_hip.ptr(tsc), _hip.ptr(Gc), _hip.ptr(plan.cut), R, d, _hip.dtype_code(dt),
+                                                     _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
+        if source == _hip.ROWS_WEIGHTED:
+            K_Rs = Rs.add_(torch.einsum("nk,kij->nij", rows, term))
+        elif source == _hip.ROWS_TABLE:
+            K_Rs = Rs.add_(term[rows.long().clamp(max=term.shape[0] - 1)])
+        else:
+            K_Rs = Rs.add_(term.unsqueeze(0))
+    else:
+        K_Rs, Os, info = _posterior_blocks_seg(tsc, Gc, plan.cut, source, term, rows)
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = int(info.item())
+        if bad:
+            b, r = _series_of_row(plan, bad - 1)
+            raise cr.NotPSDError("LEG batch: series %d: the time gap next to its row %d gives a singular PEG block "
+                                 "(zero-length gap?)" % (b, r))
+    return K_Rs, Os, v
+
+
+def _insample_posterior_flat(m, ts, xs, lengths, observed, noise_var):
+    """(mean [R, d], cov_diag [R, d, d], cov_off [R-1, d, d], plan) of the concatenated batch (already validated)."""
+    plan = _cached_batch_plan(lengths, m.N.device)
+    K_Rs, K_Os, v = _posterior_system_batch(m, ts, xs, observed, noise_var, plan)
+    try:
+        dec, mean = cr.decompose_solve(K_Rs, K_Os, v)
+    except cr.NotPSDError as e:
+        row = getattr(e, "row", None)
+        if row is None:
+            raise
+        b, r = _series_of_row(plan, row)
+        raise cr.NotPSDError("LEG batch: series %d: a block near its row %d is not positive definite" % (b, r)) from None
+    Sd, So = cr.inverse_blocks(dec)
+    if plan.B > 1:
+        So.index_fill_(0, plan.boundary_rows(), 0)           # (zero up to its sign or a failed series' NaN: exactly zero)
+    return mean, Sd, So, plan
+
+
+def _insample_posterior_per_series(m, ts, xs, lengths, observed, noise_var):
+    """One ``insample_posterior`` per series (what inputs outside ``_posterior_batch_supported`` get: they behave as they
+    do for one series), concatenated, the entry of cov_off at a series boundary zero."""
+    means, Sds, Sos, s = [], [], [], 0
+    d = m.N.shape[0]
+    for b, n in enumerate(lengths):
+        try:
+            mean, (Sd, So) = insample_posterior(m, ts[s:s + n], xs[s:s + n], None if observed is None else observed[s:s + n],
+                                                None if noise_var is None else noise_var[s:s + n])
+        except cr.NotPSDError as e:
+            raise cr.NotPSDError("LEG batch: series %d: %s" % (b, e)) from None
+        means.append(mean)
+        Sds.append(Sd)
+        Sos.append(So)
+        if b + 1 < len(lengths):
+            Sos.append(So.new_zeros(1, d, d))
+        s += n
+    return torch.cat(means), torch.cat(Sds), torch.cat(Sos)
+
+
+def _posterior_flat(m, ts, xs, lengths, observed, noise_var):
+    """(mean, cov_diag, cov_off) of the concatenated batch by whichever path the inputs get."""
+    if _posterior_batch_supported(ts, m.G):
+        return _insample_posterior_flat(m, ts, xs, lengths, observed, noise_var)[:3]
+    return _insample_posterior_per_series(m, ts, xs, lengths, observed, noise_var)
+
+
+def insample_posterior_batch(m, ts, xs, lengths=None, observed=None, noise_var=None):
+    """``insample_posterior`` of B independent series in one call: posterior mean and (diagonal, lower off-diagonal)
+    covariance blocks of every series (models.py:282-298 for each).  Inference only: the call runs under
+    ``torch.no_grad`` and NOTHING it returns carries an autograd graph (the mean included, unlike
+    ``insample_posterior``'s).
+
+    Layouts, ``lengths``, ``observed`` and ``noise_var``: those of ``log_likelihood_batch``.  Dense (``lengths=None``):
+    ts[B, n], xs[B, n, obs_dim] give mean [B, n, d], cov_diag [B, n, d, d], cov_off [B, n-1, d, d].  Ragged: ts[R],
+    xs[R, obs_dim] and host ``lengths`` give mean [R, d], cov_diag [R, d, d], cov_off [R-1, d, d]; series b's
+    off-diagonal blocks are rows starts[b] .. starts[b+1]-2 and the entry at a series boundary is exactly zero.  The
+    posterior is given at ALL rows, those that observe nothing included; what xs (and noise_var) hold at unobserved
+    entries is ignored, NaN included.  A padded dense batch is the mask whose tail rows are False.  noise_var values are
+    not checked (``observation_weights``): a negative or non-finite variance at an observed entry surfaces as
+    NotPSDError or NaN.  B = 0 returns empty tensors.  Every ValueError is raised before anything is launched.
+
+    How: the concatenated system of all series is block-diagonal -- cgps_peg_precision_seg writes zero coupling across
+    a series boundary -- and the inverse of a block-diagonal matrix is block-diagonal, so ONE ``cr.decompose_solve`` and
+    ONE ``cr.inverse_blocks`` of the concatenated system are the posterior of every series: every rank 1..8, both
+    precisions, no limit on a series' length.  A repeated call with the same lengths copies nothing
+    from the host (``_cached_batch_plan``); with ``cr.CHECK_POSITIVE_DEFINITE`` off nothing is read on the host either,
+    and the call can be captured (``Graphed``) after one ordinary call with the same lengths.
+
+    Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a block that is not positive definite, or a zero-length gap, raises
+    ``cr.NotPSDError`` naming the series and its local row.  With the check off the failed series' results are NaN, and
+    the NaN CAN REACH OTHER SERIES: the concatenated reduction multiplies a neighbour's blocks by the zero coupling, and
+    0 * NaN = NaN (unlike ``log_likelihood_batch``, whose series never meet).
+
+    CPU tensors, or a rank or dtype outside the kernels', go through ``insample_posterior`` series by series and behave
+    as that does (there is no CPU implementation)."""
+    with torch.no_grad():
+        ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        d, dt = m.N.shape[0], m.N.dtype
+        if not lengths:
+            e = lambda *shape: torch.empty(shape, dtype=dt, device=ts.device)      # noqa: E731
+            if dense:
+                return e(0, bn[1], d), (e(0, bn[1], d, d), e(0, max(bn[1] - 1, 0), d, d))
+            return e(0, d), (e(0, d, d), e(0, d, d))
+        mean, Sd, So = _posterior_flat(m, ts, xs, lengths, observed, noise_var)
+        if dense:
+            return _dense_posterior(mean, Sd, So, bn[0], bn[1])
+        return mean, (Sd, So)
+
+
+def _dense_posterior(mean, Sd, So, B, n):
+    """The concatenated posterior of B series of n rows each as mean [B, n, d], (cov_diag [B, n, d, d], cov_off
+    [B, n-1, d, d]): the boundary entries of cov_off are dropped."""
+    d = mean.shape[-1]
+    if n > 1:
+        So = So.as_strided((B, n - 1, d, d), (n * d * d, d * d, d, 1), So.storage_offset()).contiguous()
+    else:
+        So = So.new_empty(B, 0, d, d)
+    return mean.reshape(B, n, d), (Sd.reshape(B, n, d, d), So)
 
 
 # ---- drawing from the process -----------------------------------------------------------------------

@@ -174,3 +174,149 @@ def make_predictions(m, ts, xs, target_ts, check_sorted=True):
     the call is then capturable in a HIP graph (``leg.Graphed``)."""
     pm, pv = predictive_posterior(m, ts, xs, target_ts, check_sorted=check_sorted)
     return pm @ m.B.T, m.B.unsqueeze(0) @ pv @ m.B.T.unsqueeze(0)
+
+
+# ---- many series at once ---------------------------------------------------------------------------------------
+class _TargetPlan:
+    """What the target lengths fix on the host: device offsets of every series' targets, and the mask of the pairs of
+    neighbouring targets that belong to different series (the sortedness check skips them).  A series may have no
+    target."""
+
+    plans = {}          # (lengths, device) -> plan, least recently used first (leg._cached_batch_plan)
+    captured = {}       # plans that a stream capture has read: never dropped
+
+    def __init__(self, lengths, device):
+        self.lengths = lengths
+        self.B, self.P = len(lengths), sum(lengths)
+        off = [0]
+        for p in lengths:
+            off.append(off[-1] + p)
+        self.starts = off
+        self.offsets = torch.tensor(off, dtype=torch.int64).to(device, non_blocking=True)
+        across = torch.zeros(max(self.P - 1, 0), dtype=torch.bool)
+        inner = [o - 1 for o in off[1:-1] if 0 < o < self.P]
+        if inner:
+            across[torch.tensor(inner)] = True
+        self.across = across.to(device, non_blocking=True)
+
+
+def _batch_targets(target_ts, target_lengths, lengths, dense):
+    """(target_ts [P], target lengths as a list of ints, shape of the dense targets (B, p) or None); raises ValueError
+    before anything is launched."""
+    B = len(lengths)
+    if not isinstance(target_ts, torch.Tensor) or not target_ts.dtype.is_floating_point:
+        raise ValueError("target_ts must be a floating-point tensor")
+    if dense:
+        if target_lengths is not None:
+            raise ValueError("target_lengths belongs to the ragged layout (give lengths as well)")
+        if target_ts.dim() == 1:
+            target_ts = target_ts.unsqueeze(0).expand(B, -1)
+        if target_ts.dim() != 2 or target_ts.shape[0] != B:
+            raise ValueError("dense layout wants target_ts[B, p] or target_ts[p] shared by all %d series, got %s"
+                             % (B, tuple(target_ts.shape)))
+        p = int(target_ts.shape[1])
+        return target_ts.reshape(B * p), [p] * B, (B, p)
+    if target_lengths is None:
+        raise ValueError("ragged layout wants target_lengths: how many of target_ts belong to each series")
+    if isinstance(target_lengths, torch.Tensor):
+        if (target_lengths.is_cuda or target_lengths.dim() != 1 or target_lengths.dtype.is_floating_point
+                or target_lengths.dtype == torch.bool):
+            raise ValueError("target_lengths must be host data: a list or a 1-d CPU integer tensor")
+        target_lengths = target_lengths.tolist()
+    target_lengths = [int(p) for p in target_lengths]
+    if target_ts.dim() != 1:
+        raise ValueError("ragged layout wants target_ts[sum(target_lengths)], got %s" % (tuple(target_ts.shape),))
+    if len(target_lengths) != B:
+        raise ValueError("target_lengths names %d series, lengths %d" % (len(target_lengths), B))
+    bad = [b for b, p in enumerate(target_lengths) if p < 0]
+    if bad:
+        raise ValueError("series %d has %d targets" % (bad[0], target_lengths[bad[0]]))
+    if sum(target_lengths) != target_ts.shape[0]:
+        raise ValueError("target_lengths sum to %d targets, target_ts has %d" % (sum(target_lengths), target_ts.shape[0]))
+    return target_ts, target_lengths, None
+
+
+def _intercast_seg_hip(G, ip_mean, Rs, Os, ts, plan, target_ts, tplan):
+    """All targets of all series in one HIP kernel (cgps_leg_intercast_seg, csrc/cgps_leg.h): a lane per target finds
+    its series and does what ``_intercast_hip`` does for that series alone."""
+    from . import _hip
+    dt, dev = ip_mean.dtype, ip_mean.device
+    d, P = G.shape[0], tplan.P
+    c = lambda t: t.detach().to(device=dev, dtype=dt).contiguous()   # noqa: E731
+    ts_, tt_, G_, mu_, Rs_, Os_ = c(ts), c(target_ts), c(G), c(ip_mean), c(Rs), c(Os)
+    means = torch.empty(P, d, dtype=dt, device=dev)
+    covs = torch.empty(P, d, d, dtype=dt, device=dev)
+    _hip.check(_hip.lib().cgps_leg_intercast_seg(
+        _hip.ptr(ts_), _hip.ptr(plan.offsets), _hip.ptr(tt_), _hip.ptr(tplan.offsets), plan.B, P, _hip.ptr(G_), d,
+        _hip.dtype_code(dt), _hip.ptr(mu_), _hip.ptr(Rs_), _hip.ptr(Os_), _hip.ptr(means), _hip.ptr(covs), _hip.stream_ptr()))
+    return means, covs
+
+
+def _intercast_per_series(m, mean, Sd, So, ts, lengths, target_ts, target_lengths):
+    """``intercast`` series by series (inputs outside the kernels' cover)."""
+    means, covs, s, k = [], [], 0, 0
+    for n, p in zip(lengths, target_lengths):
+        pm, pv = intercast(m, mean[s:s + n], (Sd[s:s + n], So[s:s + n - 1]), ts[s:s + n], target_ts[k:k + p],
+                           check_sorted=False)
+        means.append(pm)
+        covs.append(pv)
+        s, k = s + n, k + p
+    return torch.cat(means), torch.cat(covs)
+
+
+def predictive_posterior_batch(m, ts, xs, target_ts, lengths=None, target_lengths=None, observed=None, noise_var=None,
+                               check_sorted=True):
+    """``predictive_posterior`` of B independent series in one call: E[z(t) | x_b] and Cov[z(t) | x_b] at every target
+    of every series.  Inference only: runs under ``torch.no_grad``, the results carry no autograd graph.
+
+    Dense layout (``lengths=None``): ts[B, n], xs[B, n, obs_dim], target_ts[B, p] or [p] shared by all series; returns
+    (means [B, p, rank], covs [B, p, rank, rank]).  Ragged: ts[R], xs[R, obs_dim], host ``lengths``, target_ts[P] and
+    host ``target_lengths`` (how many targets each series has; zero is allowed); returns ([P, rank], [P, rank, rank])
+    in the order of target_ts.  ``observed`` and ``noise_var`` as in ``leg.insample_posterior_batch``; a series' end is
+    its own last row, observed or not, so a padded dense batch (tail rows False) predicts exactly as a per-series call
+    with the same mask would.
+
+    How: ``leg.insample_posterior_batch``'s one factorisation of the concatenated system, then ONE launch of
+    cgps_leg_intercast_seg -- a lane per target finds its series and interpolates or forecasts inside that series
+    alone; it never reads across a series boundary.  ``check_sorted=True`` asserts every series' targets strictly
+    increasing (as the reference does, models.py:471) with one device->host read for the whole batch; ``False`` reads
+    nothing, and after one ordinary call with the same lengths the call can be captured (``leg.Graphed``).  A repeated
+    call with the same lengths and target lengths copies nothing from the host.  Errors, NaN propagation with
+    ``cr.CHECK_POSITIVE_DEFINITE`` off and unsupported inputs: ``leg.insample_posterior_batch``."""
+    with torch.no_grad():
+        ts_f, xs_f, lens, observed, noise_var, dense, bn = leg._batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        tt, tlens, bp = _batch_targets(target_ts, target_lengths, lens, dense)
+        d, dt = m.N.shape[0], m.N.dtype
+        P = sum(tlens)
+        if not lens or P == 0:
+            shape = bp if dense else (0,)
+            return (torch.empty(shape + (d,), dtype=dt, device=ts_f.device),
+                    torch.empty(shape + (d, d), dtype=dt, device=ts_f.device))
+        tt = tt.to(ts_f.dtype)
+        G = m.G
+        if leg._posterior_batch_supported(ts_f, G):
+            tplan = leg._cached_batch_plan(tlens, G.device, make=_TargetPlan)
+            if check_sorted and P > 1:
+                assert bool(((tt[1:] - tt[:-1] > 0) | tplan.across).all())     # reference :471, per series
+            mean, Sd, So, plan = leg._insample_posterior_flat(m, ts_f, xs_f, lens, observed, noise_var)
+            pm, pv = _intercast_seg_hip(G, mean, Sd, So, ts_f, plan, tt, tplan)
+        else:
+            if check_sorted and P > 1:
+                across = _TargetPlan(tlens, tt.device).across
+                assert bool(((tt[1:] - tt[:-1] > 0) | across).all())
+            mean, Sd, So = leg._insample_posterior_per_series(m, ts_f, xs_f, lens, observed, noise_var)
+            pm, pv = _intercast_per_series(m, mean, Sd, So, ts_f, lens, tt, tlens)
+        if dense:
+            return pm.reshape(bp + (d,)), pv.reshape(bp + (d, d))
+        return pm, pv
+
+
+def make_predictions_batch(m, ts, xs, target_ts, lengths=None, target_lengths=None, observed=None, noise_var=None,
+                           check_sorted=True):
+    """``make_predictions`` of B independent series in one call: predicted observation mean [..., obs_dim] and covariance
+    [..., obs_dim, obs_dim] at every target of every series -- the B-image of the latent posterior, without observation
+    noise, as ``make_predictions`` gives it.  Arguments, layouts ([B, p, ...] dense, [P, ...] ragged), inference-only
+    results and errors: ``predictive_posterior_batch``."""
+    with torch.no_grad():
+        pm, pv = predictive_posterior_batch(m, ts, xs, target_ts, lengths, target_lengths, observed, noise_var, check_sorted)
+        return pm @ m.B.T, m.B @ pv @ m.B.T

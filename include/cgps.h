@@ -280,6 +280,23 @@ int cgps_peg_precision_adjoint_seg(const void* ts, const void* G, const unsigned
                                    int dtype, const void* gRs, const void* gOs, void* gG_partial, void* gtau,
                                    void* stream);
 
+/* Blocks of the POSTERIOR precision of several series concatenated, written once: what cgps_peg_precision_seg writes,
+ * with every row's observation term added to its diagonal block as the last operation before the store,
+ *   K_Rs[i] = Rs[i] + term_i,   Os and info exactly those of cgps_peg_precision_seg.
+ * source = CGPS_ROWS_PLAIN:    term_i = term[d][d] for every row (entries and rows are not read);
+ *          CGPS_ROWS_TABLE:    term_i = term[min(rows[i], entries - 1)], term[entries][d][d], 1 <= entries <= 256,
+ *                              rows = pattern[N] DEVICE bytes (no byte value reads outside the table);
+ *          CGPS_ROWS_WEIGHTED: term_i = sum_k w[i][k] term[k], term = basis[entries][d][d], 1 <= entries <= 64,
+ *                              rows = w[N][entries] in the dtype of the call (DEVICE memory); the sum over k is formed in
+ *                              registers (fused multiply-adds from k = 0 up) and added to the block once.
+ * Plain and table results are Rs + term_i with one rounded addition per element.  cut may be NULL: one series.
+ * A null pointer, N < 1, an unknown source or entries outside its range: CGPS_ERR_ARG before anything is launched;
+ * d outside 1..8 or an unknown dtype: CGPS_ERR_UNSUPPORTED. */
+enum { CGPS_ROWS_PLAIN = 0, CGPS_ROWS_TABLE = 1, CGPS_ROWS_WEIGHTED = 2 };
+int cgps_leg_posterior_blocks_seg(const void* ts, const void* G, const unsigned char* cut, int64_t N, int d, int dtype,
+                                  int source, const void* term, int entries, const void* rows, void* K_Rs, void* Os,
+                                  int* info, void* stream);
+
 /* Prediction glue of LEG models, the step AFTER the path (reference models.py:455-514 intercast with
  * forecast :394-408, interpolate :410-452 and gaussian_stitch model_utils.py:64-107, which the reference
  * runs as a Python loop over the targets): posterior mean and covariance of the latent at p target
@@ -290,6 +307,21 @@ int cgps_peg_precision_adjoint_seg(const void* ts, const void* G, const unsigned
 int cgps_leg_intercast(const void* ts, int64_t n, const void* target_ts, int64_t p, const void* G, int d, int dtype,
                        const void* ip_mean, const void* ip_cov_diag, const void* ip_cov_offdiag,
                        void* out_mean, void* out_cov, void* stream);
+
+/* cgps_leg_intercast for B series concatenated, all targets of all series in one launch.  ts, ip_mean[R][d],
+ * ip_cov_diag[R][d][d] and ip_cov_offdiag[R-1][d][d] are those of the concatenated batch (what cgps_inverse_blocks
+ * leaves for the block-diagonal system cgps_peg_precision_seg assembles); series b is rows row_offsets[b] ..
+ * row_offsets[b+1]-1 and its targets are target_ts[target_offsets[b] .. target_offsets[b+1]-1] (a series may have
+ * none).  Both offset arrays are int64 DEVICE memory of B + 1 entries; P = target_offsets[B] is the total number of
+ * targets and sizes the grid.  One lane per target: it finds its series by binary search in target_offsets and then
+ * does what cgps_leg_intercast does for that series alone (same branches, same arithmetic, bit for bit); it never reads
+ * a row of another series nor the off-diagonal block of a cut gap, whatever they hold.  out_mean[P][d],
+ * out_cov[P][d][d].  B < 0, P < 0 or a null pointer with B > 0 and P > 0: CGPS_ERR_ARG; B = 0 or P = 0: CGPS_OK,
+ * nothing launched; d outside 1..8 or an unknown dtype: CGPS_ERR_UNSUPPORTED.  No workspace, no info word. */
+int cgps_leg_intercast_seg(const void* ts, const int64_t* row_offsets, const void* target_ts,
+                           const int64_t* target_offsets, int64_t B, int64_t P, const void* G, int d, int dtype,
+                           const void* ip_mean, const void* ip_cov_diag, const void* ip_cov_offdiag,
+                           void* out_mean, void* out_cov, void* stream);
 
 /* ---- time-axis sharding (one shard per GPU / rank) -----------------------------------------
  * The reference has no distributed code; this is the multi-GPU form BASELINE.json asks for.
