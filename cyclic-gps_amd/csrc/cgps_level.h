@@ -361,4 +361,30 @@ __global__ __launch_bounds__(ADJ_THREADS) void mahal_logdet_adjoint_kernel(T* __
   }
 }
 
+// The same for B systems concatenated (cgps_mahal_logdet_adjoint_seg): Sd / So / w are those of the block-diagonal
+// concatenation (coupling blocks at the cuts zero), seg[i] names the system of row i (clamped to 0 .. B-1: no value
+// reads outside gm / gl) and row i takes ITS system's upstream gradients gm[seg[i]], gl[seg[i]].  So[i] between two
+// systems is written as 0: that entry of the caller's Os is not part of any system.
+template <typename T, int D>
+__global__ __launch_bounds__(ADJ_THREADS) void mahal_logdet_adjoint_seg_kernel(T* __restrict__ Sd, T* __restrict__ So,
+                                                                               const T* __restrict__ w, int64_t N,
+                                                                               const int* __restrict__ seg, int B,
+                                                                               const T* __restrict__ gm_p,
+                                                                               const T* __restrict__ gl_p) {
+  constexpr int DD = D * D;
+  const int64_t nd = N * DD, total = nd + (N - 1) * DD;
+  for (int64_t idx = (int64_t)blockIdx.x * ADJ_THREADS + threadIdx.x; idx < total;
+       idx += (int64_t)gridDim.x * ADJ_THREADS) {
+    const bool diag = idx < nd;
+    const int64_t j = diag ? idx : idx - nd;
+    const int64_t i = j / DD;
+    const int r = (int)(j - i * DD), a = r / D, b = r - a * D;
+    int s = seg[i];
+    s = s < 0 ? 0 : (s >= B ? B - 1 : s);
+    const T gm = gm_p[s], gl = gl_p[s];
+    if (diag) Sd[j] = gl * Sd[j] - gm * w[i * D + a] * w[i * D + b];
+    else So[j] = seg[i + 1] != seg[i] ? T(0) : T(2) * (gl * So[j] - gm * w[(i + 1) * D + a] * w[i * D + b]);
+  }
+}
+
 }  // namespace cgps

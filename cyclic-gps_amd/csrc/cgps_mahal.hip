@@ -5,6 +5,7 @@
 #include "cgps_tile.h"
 #include "cgps_boundary.h"
 #include "cgps_tile_leg_batch.h"
+#include "cgps_tile_batch.h"
 
 using namespace cgps_host;
 
@@ -122,6 +123,25 @@ int cgps_leg_loglik_batch(const void* ts, const int64_t* offsets, int64_t B, con
                                              max_rows, out4, info2, (hipStream_t)stream);
     if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch: not built for this block size (d = 8, fp64 d = 6)");
     return check_launch("LEG batched reduction");
+  });
+}
+
+int cgps_mahal_logdet_batch(const void* Rs, const void* Os, const void* x, const int64_t* offsets, int64_t B, int os_packed,
+                            int d, int dtype, int64_t max_rows, double* out2, int* info, void* stream) {
+  if (B < 0 || d < 1 || !Rs || !Os || !offsets || !out2 || !info)
+    return fail(CGPS_ERR_ARG, "cgps_mahal_logdet_batch: null pointer or B < 0");
+  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_mahal_logdet_batch: B = %lld systems, at most 2^31 - 1", (long long)B);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    if constexpr (!cgps::mahal_batch_supported<T, D>()) {
+      return fail(CGPS_ERR_UNSUPPORTED, "cgps_mahal_logdet_batch: not built for this block size (d = 8, fp64 d = 6): reduce each system with cgps_mahal_logdet");
+    } else {
+      if (B == 0) return (int)CGPS_OK;                           // nothing to do: the runtime is not touched
+      cgps::run_mahal_batch<T, D>((const T*)Rs, (const T*)Os, (const T*)x, offsets, B, os_packed != 0 ? 1 : 0, max_rows, out2,
+                                  info, (hipStream_t)stream);
+      return check_launch("batched tile reduction");
+    }
   });
 }
 

@@ -45,6 +45,8 @@ _SIGNATURES = {
     "cgps_logdet_factor": (_int, [_vp, _i64, _int, _int, _vp, _sz, _vp, _vp]),
     "cgps_inverse_blocks": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "cgps_mahal_logdet_adjoint": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "cgps_mahal_logdet_batch": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _i64, _vp, _vp, _vp]),
+    "cgps_mahal_logdet_adjoint_seg": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp]),
     "cgps_peg_precision": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "cgps_leg_mahal_logdet": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "cgps_leg_mahal_logdet_pair": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),

@@ -332,6 +332,272 @@ def _mahal_and_det(Rs, Os, x, levelwise):
 
 
 # ----------------------------------------------------------------------------
+# many independent systems at once (an addition to the reference's surface)
+# ----------------------------------------------------------------------------
+BATCH_MAX_ROWS = 4096
+"""Systems longer than this are reduced by ``cgps_mahal_logdet`` (several workgroups per system) instead of the one
+workgroup per system of ``cgps_mahal_logdet_batch``; their values go into their slots all the same."""
+
+
+class _MahalBatchPlan:
+    """What the lengths of a ragged batch fix on the host, as device tensors: row offsets, the system of every row and
+    the coupling blocks that lie between two systems.  Cached by ``leg._cached_batch_plan`` (caches of its own)."""
+    plans, captured = {}, {}
+
+    def __init__(self, lengths, device):
+        off = [0]
+        for n in lengths:
+            off.append(off[-1] + n)
+        B, R = len(lengths), off[-1]
+        self.offsets = torch.tensor(off, dtype=torch.int64).to(device, non_blocking=True)
+        self.seg = torch.repeat_interleave(torch.arange(B, dtype=torch.int32),
+                                           torch.tensor(lengths, dtype=torch.int64)).to(device, non_blocking=True)
+        self.cuts = torch.tensor(sorted({s - 1 for s in off[1:-1] if 0 < s < R}), dtype=torch.int64).to(device, non_blocking=True)
+
+
+class _BatchLayout:
+    """The two input layouts of mahal_and_det_batch behind one face.  Dense: B systems of n rows, Os[B, n-1] (the
+    kernel's os_packed = 1); offsets and row indices are made on the device, nothing is uploaded.  Ragged: the
+    concatenated arrays and host-side lengths; the entries of Os between two systems belong to nobody."""
+
+    def __init__(self, dense, lengths, d, dtype, shapes):
+        self.dense, self.lengths, self.d, self.dtype, self.shapes = dense, lengths, d, dtype, shapes
+        self.B, self.R = len(lengths), sum(lengths)
+        self.n = lengths[0] if dense and lengths else 0
+        self._plan = self._starts = None
+
+    def plan(self, dev):
+        if self._plan is None:
+            from . import leg            # (leg imports this module: not at import time)
+            self._plan = leg._cached_batch_plan(self.lengths, dev, make=_MahalBatchPlan)
+        return self._plan
+
+    def offsets(self, dev):
+        if self.dense:
+            return torch.arange(0, (self.B + 1) * self.n, self.n, dtype=torch.int64, device=dev)   # (n >= 1: R > 0)
+        return self.plan(dev).offsets
+
+    def seg(self, dev):
+        """int32 [R]: the system of each row"""
+        if self.dense:
+            return torch.arange(self.R, dtype=torch.int32, device=dev).div(self.n, rounding_mode="floor")
+        return self.plan(dev).seg
+
+    def start(self, b):
+        """(first row, first coupling block) of system b in the arrays handed to the kernel"""
+        if self.dense:
+            return b * self.n, b * (self.n - 1)
+        if self._starts is None:
+            self._starts = [0]
+            for n in self.lengths:
+                self._starts.append(self._starts[-1] + n)
+        return self._starts[b], self._starts[b]
+
+    def concatenated_Os(self, O):
+        """Os [R-1, d, d] of the block-diagonal concatenation: the caller's coupling blocks, zero between systems."""
+        d = self.d
+        if self.dense:
+            Oc = O.new_zeros(self.B, self.n, d, d)
+            Oc[:, :self.n - 1] = O.reshape(self.B, self.n - 1, d, d)
+            return Oc.reshape(self.R, d, d)[:self.R - 1]
+        Oc = O.clone()
+        cuts = self.plan(O.device).cuts
+        if cuts.numel():
+            Oc.index_fill_(0, cuts, 0)
+        return Oc
+
+    def caller_Os(self, So):
+        """The other way round, for a gradient [R-1, d, d] that is zero between systems."""
+        d = self.d
+        if self.dense:
+            pad = torch.cat([So, So.new_zeros(1, d, d)], dim=0).reshape(self.B, self.n, d, d)
+            return pad[:, :self.n - 1].contiguous()
+        return So
+
+
+def _batch_layout(Rs, Os, x, lengths):
+    """Checks the arguments of mahal_and_det_batch and describes them; raises before the library is touched."""
+    for name, t in (("Rs", Rs), ("Os", Os)) + ((("x", x),) if x is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a tensor" % name)
+    if Rs.dtype not in (torch.float32, torch.float64):
+        raise TypeError("cyclic reduction supports float32 / float64 blocks, got %s" % Rs.dtype)
+    if Os.dtype != Rs.dtype or (x is not None and x.dtype != Rs.dtype):
+        raise TypeError("Rs, Os and x must share one dtype, got %s, %s and %s"
+                        % (Rs.dtype, Os.dtype, None if x is None else x.dtype))
+    if lengths is None:
+        if Rs.dim() != 4 or Rs.shape[2] != Rs.shape[3]:
+            raise ValueError("dense layout wants Rs[B, n, d, d], got %s (pass lengths for the ragged layout)" % (tuple(Rs.shape),))
+        B, n, d = Rs.shape[0], Rs.shape[1], Rs.shape[2]
+        if tuple(Os.shape) != (B, max(n - 1, 0), d, d):
+            raise ValueError("dense layout wants Os[%d, %d, %d, %d], got %s" % (B, max(n - 1, 0), d, d, tuple(Os.shape)))
+        if x is not None and tuple(x.shape) != (B, n, d):
+            raise ValueError("dense layout wants x[%d, %d, %d], got %s" % (B, n, d, tuple(x.shape)))
+        lens, dense = [int(n)] * B, True
+    else:
+        if isinstance(lengths, torch.Tensor):
+            if lengths.is_cuda or lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError("lengths must be host data: a sequence or a 1-d CPU integer tensor")
+            lengths = lengths.tolist()
+        try:
+            lens = [int(n) for n in lengths]
+        except TypeError:
+            raise ValueError("lengths must be a flat sequence of integers")
+        if any(int(a) != a for a in lengths):
+            raise ValueError("lengths must be integers")
+        if Rs.dim() != 3 or Rs.shape[1] != Rs.shape[2]:
+            raise ValueError("ragged layout wants Rs[sum(lengths), d, d], got %s" % (tuple(Rs.shape),))
+        R, d = Rs.shape[0], Rs.shape[1]
+        bad = [b for b, n in enumerate(lens) if n < 0]
+        if bad:
+            raise ValueError("system %d has length %d" % (bad[0], lens[bad[0]]))
+        if sum(lens) != R:
+            raise ValueError("lengths sum to %d rows, Rs has %d" % (sum(lens), R))
+        if tuple(Os.shape) != (max(R - 1, 0), d, d):
+            raise ValueError("ragged layout wants Os[%d, %d, %d] (the concatenated system's), got %s"
+                             % (max(R - 1, 0), d, d, tuple(Os.shape)))
+        if x is not None and tuple(x.shape) != (R, d):
+            raise ValueError("ragged layout wants x[%d, %d], got %s" % (R, d, tuple(x.shape)))
+        dense = False
+    if not 1 <= d <= 8:
+        raise ValueError("block size d=%d outside 1..8" % d)
+    return _BatchLayout(dense, lens, int(d), Rs.dtype, (tuple(Rs.shape), tuple(Os.shape), None if x is None else tuple(x.shape)))
+
+
+def _aligned16(t):
+    """t, or a copy of it when its first byte is not on a 16-byte boundary (a slice of odd-sized blocks at an odd row:
+    the one-system kernels read such rows two at a time with 16-byte loads)."""
+    return t.clone() if t.numel() and t.data_ptr() % 16 else t
+
+
+def _capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def _mahal_batch_raw(R, O, v, lay):
+    """([B, 2] fp64 {mahal, logdet}, [B] int32 info) of staged, flattened operands: R [R, d, d], O the caller's coupling
+    blocks flattened to [., d, d], v [R, d] or None.  One launch of cgps_mahal_logdet_batch; systems it leaves out (longer
+    than BATCH_MAX_ROWS; every system at d = 8 and fp64 d = 6) go through cgps_mahal_logdet on the same stream, each into
+    its own slot.  Nothing is read on the host."""
+    dev, dt, d, B = R.device, R.dtype, lay.d, lay.B
+    out = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+    info = torch.zeros(B, dtype=torch.int32, device=dev)
+    if lay.R == 0:
+        return out, info
+    dtc = _hip.dtype_code(dt)
+    with torch.cuda.device(dev):
+        rc = _hip.lib().cgps_mahal_logdet_batch(
+            _hip.ptr(R), _hip.ptr(O if O.numel() else R),       # (one-row systems only: no coupling block is read)
+            _hip.ptr(v), _hip.ptr(lay.offsets(dev)), B, 1 if lay.dense else 0, d, dtc, BATCH_MAX_ROWS,
+            _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr())
+        if rc == 3:      # CGPS_ERR_UNSUPPORTED: a block size the batched kernel is not built for
+            singles = [b for b, n in enumerate(lay.lengths) if n >= 1]
+        else:
+            _hip.check(rc)
+            singles = [b for b, n in enumerate(lay.lengths) if n > BATCH_MAX_ROWS]
+        for b in singles:
+            n = lay.lengths[b]
+            s, so = lay.start(b)
+            Rb, Ob = _aligned16(R[s:s + n]), _aligned16(O[so:so + n - 1])
+            vb = _aligned16(v[s:s + n]) if v is not None else torch.zeros(n, d, dtype=dt, device=dev)
+            ws, nbytes = _hip.workspace(n, d, dt, _hip.OP_MAHAL_LOGDET, dev)
+            _hip.check(_hip.lib().cgps_mahal_logdet(
+                _hip.ptr(Rb), _hip.ptr(Ob), _hip.ptr(vb), n, d, dtc, _hip.ptr(ws), nbytes, _hip.ptr(out[b]),
+                _hip.ptr(info[b:b + 1]), _hip.stream_ptr()))
+    return out, info
+
+
+def _mahal_and_det_batch(Rs, Os, x, lay):
+    d = lay.d
+    R = _stage(Rs).reshape(-1, d, d)
+    O = _stage(Os).reshape(-1, d, d)
+    v = None if x is None else _stage(x).reshape(-1, d)
+    out, info = _mahal_batch_raw(R, O, v, lay)
+    if CHECK_POSITIVE_DEFINITE and lay.B and not _capturing():     # (a capture cannot read info: NaN marks the slot)
+        bad = info.cpu()
+        rows = torch.nonzero(bad).flatten().tolist()
+        if rows:
+            b = rows[0]
+            err = NotPSDError("batch: system %d: a block near its row %d is not positive definite" % (b, int(bad[b]) - 1))
+            err.system, err.row = b, int(bad[b]) - 1
+            raise err
+    res = _back(out.to(lay.dtype), Rs)
+    return res[:, 0].contiguous(), res[:, 1].contiguous()
+
+
+class _BatchMahalLogdetFn(torch.autograd.Function):
+    """Forward: the batched reduction (one launch).  Backward: the concatenated system of all systems, which is block
+    diagonal (the coupling blocks at the cuts set to zero): decompose_solve + inverse_blocks once, then one launch of
+    the per-system adjoint kernel with every system's own upstream gradients (cgps_mahal_logdet_adjoint_seg)."""
+
+    @staticmethod
+    def forward(ctx, Rs, Os, x, lay):
+        ctx.lay = lay
+        ctx.save_for_backward(Rs, Os, x)
+        return _mahal_and_det_batch(Rs.detach(), Os.detach(), None if x is None else x.detach(), lay)
+
+    @staticmethod
+    def backward(ctx, gm, gl):
+        Rs, Os, x = ctx.saved_tensors
+        lay, d = ctx.lay, ctx.lay.d
+        need_R, need_O, need_x = ctx.needs_input_grad[:3]
+        need_x = need_x and x is not None
+        if lay.R == 0:
+            z = lambda t, need: torch.zeros_like(t) if need else None   # noqa: E731
+            return z(Rs, need_R), z(Os, need_O), (z(x, need_x) if x is not None else None), None
+        R = _stage(Rs.detach()).reshape(-1, d, d)
+        dev, dt = R.device, R.dtype
+        Oc = lay.concatenated_Os(_stage(Os.detach()).reshape(-1, d, d))
+        g_m, g_l = _stage(gm.detach(), dt), _stage(gl.detach(), dt)
+        gR = gO = gx = None
+        with torch.cuda.device(dev):
+            if x is None:
+                dec, w = _decompose_raw(R, Oc), torch.zeros(lay.R, d, dtype=dt, device=dev)
+            else:
+                dec, w = decompose_solve(R, Oc, _stage(x.detach()).reshape(-1, d))
+            seg = lay.seg(dev)
+            if need_x:
+                gx = _back((2 * torch.index_select(g_m, 0, seg).unsqueeze(-1) * w).reshape(x.shape), x)
+            if need_R or need_O:
+                Sd, So = inverse_blocks(dec)
+                w = w.contiguous()
+                _hip.check(_hip.lib().cgps_mahal_logdet_adjoint_seg(
+                    _hip.ptr(Sd), _hip.ptr(So), _hip.ptr(w), _hip.ptr(seg), lay.R, lay.B, d, _hip.dtype_code(dt),
+                    _hip.ptr(g_m), _hip.ptr(g_l), _hip.stream_ptr()))
+                if need_R:
+                    gR = _back(Sd.reshape(Rs.shape), Rs)
+                if need_O:
+                    gO = _back(lay.caller_Os(So).reshape(Os.shape), Os)
+        return gR, gO, gx, None
+
+
+def mahal_and_det_batch(Rs, Os, x, lengths=None):
+    """``mahal_and_det`` of B independent systems in one launch -> (mahal [B], logdet [B]): what a Python loop of
+    ``mahal_and_det`` calls returns, each system reduced by one workgroup (cgps_mahal_logdet_batch).  An addition to the
+    reference's surface.
+
+    Dense layout (``lengths=None``): Rs [B, n, d, d], Os [B, n-1, d, d], x [B, n, d].  Nothing is uploaded from the host,
+    and the call can be captured in a HIP graph.  Ragged layout: the systems concatenated, Rs [R, d, d], Os [R-1, d, d],
+    x [R, d], with ``lengths`` a sequence or CPU integer tensor that sums to R; the entries of Os between two systems are
+    ignored whatever they hold, and a system of length 0 gives (0, 0).  The lengths' device tensors are built once and
+    cached (``leg._cached_batch_plan``: a capture needs one ordinary call with the same lengths first).
+    ``x=None`` gives the log-determinants alone; mahal is zeros.
+
+    Systems longer than ``BATCH_MAX_ROWS``, and every system at d = 8 and fp64 d = 6 (block sizes the batched kernel is
+    not built for), are reduced by ``cgps_mahal_logdet`` on the same stream into their own slots.  With
+    ``CHECK_POSITIVE_DEFINITE`` a system that is not positive definite raises ``NotPSDError`` naming it (``err.system``)
+    and its local row (``err.row``); without it (and inside a graph capture, which cannot read the info words) that
+    system's two values are NaN and every other slot is untouched.  CPU tensors are staged to the device and the results
+    returned on the CPU; there is no CPU fallback.  Differentiable in Rs, Os and x: the backward factors the concatenated
+    system once and weights every row with its own system's upstream gradients; the gradient of an ignored entry of
+    Os is exactly 0."""
+    lay = _batch_layout(Rs, Os, x, lengths)
+    if _needs_grad(Rs, Os, x):
+        return _BatchMahalLogdetFn.apply(Rs, Os, x, lay)
+    return _mahal_and_det_batch(Rs, Os, x, lay)
+
+
+# ----------------------------------------------------------------------------
 # operations on a stored factor
 # ----------------------------------------------------------------------------
 def _rhs(y, N, d, dt):

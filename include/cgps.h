@@ -162,6 +162,36 @@ int cgps_sample(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d
 int cgps_mahal_logdet_adjoint(void* Sd, void* So, const void* w, int64_t N, int d, int dtype,
                               const void* gm, const void* gl, void* stream);
 
+/* ---- many independent systems at once -------------------------------------------------------------
+ * cgps_mahal_logdet for B block-tridiagonal systems in ONE launch, each with values of its own (one series under many
+ * parameter sets, a mixture, blocks modified after the assembly: what a loop of mahal_and_det calls computes).
+ * System b is rows offsets[b] .. offsets[b+1]-1 of the concatenated Rs[R][d][d] and x[R][d] (NULL: the
+ * log-determinants alone, out2[b][0] = 0); offsets[B+1] is int64 DEVICE memory, non-decreasing, offsets[0] >= 0.
+ * Its coupling blocks start at block offsets[b] - (os_packed ? b : 0) of Os:
+ *   os_packed = 0: Os[R-1][d][d], the layout of the concatenated system; the entry between two systems is NEVER read,
+ *                  whatever it holds;
+ *   os_packed = 1: Os[B][n-1][d][d], the dense layout of B systems of n rows each.
+ * out2[b] = {x_b^T J_b^-1 x_b, log|J_b|} (device doubles); info[b]: 0, or 1 + a row of the system (local index) near
+ * a block that is not positive definite -- that system's two values are NaN then and every other system is
+ * unaffected.  One workgroup per system, sums in a fixed order: a system's values do not depend on its place in the
+ * batch.  A system with n_b < 1 or n_b > max_rows is skipped (nothing of its slot is written: the caller reduces a
+ * long one with cgps_mahal_logdet).  No workspace.
+ * CGPS_ERR_ARG: a null pointer (x excepted) or B < 0; CGPS_ERR_UNSUPPORTED: d outside 1..8, a bad dtype, and the
+ * block sizes this kernel is not built for (d = 8, fp64 d = 6: reduce each system with cgps_mahal_logdet); B = 0
+ * returns CGPS_OK and launches nothing. */
+int cgps_mahal_logdet_batch(const void* Rs, const void* Os, const void* x, const int64_t* offsets, int64_t B,
+                            int os_packed, int d, int dtype, int64_t max_rows, double* out2, int* info, void* stream);
+
+/* cgps_mahal_logdet_adjoint for B systems with upstream gradients of their own.  Sd[N][d][d], So[N-1][d][d] and
+ * w[N][d] are inverse_blocks / solve of the block-diagonal CONCATENATION of the systems (coupling blocks between
+ * systems zero); seg[N] (DEVICE int32) names the system of each row, non-decreasing, values outside 0 .. B-1 are
+ * clamped; gm[B], gl[B] (DEVICE arrays of the blocks' dtype): d loss / d mahal_b, d loss / d logdet_b.  In place:
+ *   Sd[i] <- gl[s] Sd[i] - gm[s] w_i w_i^T,  s = seg[i]
+ *   So[i] <- 2 (gl[s] So[i] - gm[s] w_i+1 w_i^T)  when rows i and i+1 belong to one system, 0 otherwise.
+ * No workspace. */
+int cgps_mahal_logdet_adjoint_seg(void* Sd, void* So, const void* w, const int* seg, int64_t N, int64_t B, int d,
+                                  int dtype, const void* gm, const void* gl, void* stream);
+
 /* ---- operand assembly for LEG models (the caller's step right before the path) ---------------
  * Blocks of the PEG prior precision from the time stamps and the generator G
  * (models.py:181-239: E_i = exp(-1/2 (t_{i+1}-t_i) G), two d x d solves per gap):
