@@ -242,9 +242,18 @@ __device__ __forceinline__ bool gap_terms(T dt, const T (&G)[D][D], bool want_ri
 // read, and every difference below is an `if constexpr`).  PEG_TERM_PLAIN: the one block term[d][d].  PEG_TERM_TABLE:
 // entry rows[i] (a byte) of term[entries][d][d], the index clamped to entries - 1 as leg_obs_block clamps it.
 // PEG_TERM_WEIGHTED: sum_k w[i][k] term[k] with w = rows as T[N][entries], summed over k in registers and added once.
+//
+// MODELS (cgps_peg_precision_models): the same N rows under gridDim.y generators.  blockIdx.y = k names the model: the
+// workgroup moves G, Rs and Os to model k's slices (G[M][d][d], rows k N .. (k+1) N - 1 of the concatenated Rs / Os) and
+// is the one-model workgroup from there on; ts and cut are every model's.  The last row of a model that is not the last
+// also writes the zero coupling block between two models, Os[(k+1) N - 1]; failures report the concatenated row.
 constexpr int PEG_TERM_NONE = 0, PEG_TERM_PLAIN = 1, PEG_TERM_TABLE = 2, PEG_TERM_WEIGHTED = 3;
 
-template <typename T, int D, int TERM = PEG_TERM_NONE>
+// the block sizes of cgps_leg_loglik_models, whose backward the models forms of the assembly serve
+template <typename T, int D>
+constexpr bool peg_models_supported() { return D <= 7 && !(D == 6 && sizeof(T) == 8); }
+
+template <typename T, int D, int TERM = PEG_TERM_NONE, bool MODELS = false>
 __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __restrict__ ts, const T* __restrict__ Gg,
                                                                     int64_t N, T* __restrict__ Rs, T* __restrict__ Os,
                                                                     int* __restrict__ info,
@@ -255,6 +264,12 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
   constexpr int DD = D * D;
   const int64_t i = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
   if (i >= N) return;
+  if constexpr (MODELS) {
+    const int64_t k = blockIdx.y;
+    Gg += k * DD;
+    Rs += k * N * DD;
+    Os += k * N * DD;
+  }
   T G[D][D];
 #pragma unroll
   for (int a = 0; a < D; ++a)
@@ -281,6 +296,15 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
 #pragma unroll
       for (int b = 0; b < D; ++b) { R[a][b] += c2[a][b]; bb[a][b] = -bb[a][b]; }
     store_block<T, D>(Os + i * DD, bb);
+  } else if constexpr (MODELS) {                   // a model's last row: the next model does not couple to it
+    if (blockIdx.y + 1 < gridDim.y) {
+      T z[D][D];
+#pragma unroll
+      for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int b = 0; b < D; ++b) z[a][b] = T(0);
+      store_block<T, D>(Os + i * DD, z);
+    }
   }
   if (i >= 1 && !(cut != nullptr && cut[i - 1])) { // the gap before it (unless it starts a series)
     T c1[D][D], c2[D][D], bb[D][D];
@@ -324,7 +348,11 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
       for (int b = 0; b < D; ++b) R[a][b] += S[a][b];
   }
   store_block<T, D>(Rs + i * DD, R);
-  if (!ok) report_fail(info, i);
+  if constexpr (MODELS) {
+    if (!ok) report_fail(info, (int64_t)blockIdx.y * N + i);
+  } else {
+    if (!ok) report_fail(info, i);
+  }
 }
 
 
@@ -625,13 +653,23 @@ __device__ __forceinline__ void mat_exp_frechet(T (&E)[D][D], T (&L)[D][D], T (&
   }
 }
 
-template <typename T, int D>
+// MODELS (cgps_peg_precision_adjoint_models): blockIdx.y names the model as in peg_precision_kernel; gG_partial and
+// gtau are [M][gridDim.x][d][d] and [M][N - 1].  The gap after a model's last row belongs to no workgroup.
+template <typename T, int D, bool MODELS = false>
 __global__ __launch_bounds__(LEG_THREADS) void peg_precision_adjoint_kernel(
     const T* __restrict__ ts, const T* __restrict__ Gg, int64_t N, const T* __restrict__ gRs, const T* __restrict__ gOs,
     T* __restrict__ gG_partial, T* __restrict__ gtau, const unsigned char* __restrict__ cut = nullptr) {
   constexpr int DD = D * D;
   __shared__ T red[DD];
   const int64_t i = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;      // the gap between rows i and i + 1
+  if constexpr (MODELS) {
+    const int64_t k = blockIdx.y;
+    Gg += k * DD;
+    gRs += k * N * DD;
+    gOs += k * N * DD;
+    gG_partial += k * (int64_t)gridDim.x * DD;
+    if (gtau != nullptr) gtau += k * (N - 1);
+  }
   T Gbar[D][D];
 #pragma unroll
   for (int a = 0; a < D; ++a)

@@ -70,6 +70,52 @@ int cgps_peg_precision_adjoint_seg(const void* ts, const void* G, const unsigned
   });
 }
 
+int cgps_peg_precision_models(const void* ts, const void* G, const unsigned char* cut, int64_t R, int64_t M, int d, int dtype,
+                              void* Rs, void* Os, int* info, void* stream) {
+  if (M < 1 || M > 65535) return fail(CGPS_ERR_ARG, "cgps_peg_precision_models: M = %lld models, outside 1..65535", (long long)M);
+  if (bad_common(R, d) || !ts || !G || !Rs || (M * R > 1 && !Os) || !info)
+    return fail(CGPS_ERR_ARG, "cgps_peg_precision_models: null pointer or R < 1");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    if constexpr (!cgps::peg_models_supported<T, D>()) {
+      return fail(CGPS_ERR_UNSUPPORTED, "cgps_peg_precision_models: not built for this block size (d = 8, fp64 d = 6)");
+    } else {
+      hipStream_t st = (hipStream_t)stream;
+      const int64_t nb = (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+      if (nb > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_peg_precision_models: R = %lld rows, too many for one launch", (long long)R);
+      (void)hipMemsetAsync(info, 0, sizeof(int), st);
+      hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D, cgps::PEG_TERM_NONE, true>), dim3((unsigned)nb, (unsigned)M),
+                         dim3(cgps::LEG_THREADS), 0, st, (const T*)ts, (const T*)G, R, (T*)Rs, (T*)Os, info, cut);
+      return check_launch("peg_precision_models");
+    }
+  });
+}
+
+int cgps_peg_precision_adjoint_models(const void* ts, const void* G, const unsigned char* cut, int64_t R, int64_t M, int d,
+                                      int dtype, const void* gRs, const void* gOs, void* gG_partial, void* gtau,
+                                      void* stream) {
+  if (M < 1 || M > 65535)
+    return fail(CGPS_ERR_ARG, "cgps_peg_precision_adjoint_models: M = %lld models, outside 1..65535", (long long)M);
+  if (bad_common(R, d) || R < 2 || !ts || !G || !gRs || !gOs || !gG_partial)
+    return fail(CGPS_ERR_ARG, "cgps_peg_precision_adjoint_models: null pointer or R < 2");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    if constexpr (!cgps::peg_models_supported<T, D>()) {
+      return fail(CGPS_ERR_UNSUPPORTED, "cgps_peg_precision_adjoint_models: not built for this block size (d = 8, fp64 d = 6)");
+    } else {
+      const int64_t nb = (R - 1 + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+      if (nb > 0x7fffffffLL)
+        return fail(CGPS_ERR_ARG, "cgps_peg_precision_adjoint_models: R = %lld rows, too many for one launch", (long long)R);
+      hipLaunchKernelGGL((cgps::peg_precision_adjoint_kernel<T, D, true>), dim3((unsigned)nb, (unsigned)M),
+                         dim3(cgps::LEG_THREADS), 0, (hipStream_t)stream, (const T*)ts, (const T*)G, R, (const T*)gRs,
+                         (const T*)gOs, (T*)gG_partial, (T*)gtau, cut);
+      return check_launch("peg_precision_adjoint_models");
+    }
+  });
+}
+
 int cgps_leg_intercast(const void* ts, int64_t n, const void* target_ts, int64_t p, const void* G, int d, int dtype,
                        const void* ip_mean, const void* ip_cov_diag, const void* ip_cov_offdiag, void* out_mean,
                        void* out_cov, void* stream) {

@@ -33,6 +33,10 @@
 // sum_k weights[(offsets[b] + r) Kb + k] basis[k] to the carried toRight term before leg_row assembles the row with no A
 // (leg_add_weighted_basis in cgps_tile_leg.h, and its note on that placement).  The prior-precision workgroup has a
 // null basis and reads neither basis nor weights.
+// ROWS = LEG_ROWS_MODELS (cgps_leg_loglik_models): M models over the same batch, grid (B, 2, M).  blockIdx.z = k names
+// the model: the workgroup moves G, A, v, q, out4 and info2 to model k's slices (G[M][d][d], A[M][d][d], v[M][R][d],
+// q[M][R] with R = model_rows, out4[M][B][4], info2[M][B][2]) and is a LEG_ROWS_PLAIN workgroup from there on.  k is
+// workgroup-uniform, so G[k] and A[k] still arrive through scalar loads.
 // LEG_ROWS_PLAIN reads neither argument, and every difference is an `if constexpr` on the kernel itself: each source's
 // instruction stream is the one it had before the others existed.  The TABLE and WEIGHTED kernels are instantiated
 // by the translation unit that calls run_leg_batch_obs / run_leg_batch_w (cgps_leg_obs.hip).
@@ -41,7 +45,7 @@
 namespace cgps {
 
 constexpr int LEG_BATCH_THREADS = 256;
-constexpr int LEG_ROWS_PLAIN = 0, LEG_ROWS_TABLE = 1, LEG_ROWS_WEIGHTED = 2;
+constexpr int LEG_ROWS_PLAIN = 0, LEG_ROWS_TABLE = 1, LEG_ROWS_WEIGHTED = 2, LEG_ROWS_MODELS = 3;
 
 template <typename T, int D>
 constexpr int leg_batch_lanes() { return TileCfg<T, D>::NG1; }       // 256, or 128 for 7 x 7 fp64 (LDS)
@@ -52,11 +56,21 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
                                                           const T* __restrict__ vg, const T* __restrict__ qg,
                                                           int64_t max_rows, double* __restrict__ out4,
                                                           int* __restrict__ info2, int entries,
-                                                          const unsigned char* __restrict__ pattern) {
+                                                          const unsigned char* __restrict__ pattern,
+                                                          int64_t model_rows = 0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   StageSmem<T, D, NT, NW> sm(smem);
   const int tid = threadIdx.x;
   const int64_t b = blockIdx.x;
+  if constexpr (ROWS == LEG_ROWS_MODELS) {                     // model k's slices (workgroup-uniform)
+    const int64_t k = blockIdx.z;
+    Gg += k * (D * D);
+    if (Ag != nullptr) Ag += k * (D * D);
+    if (vg != nullptr) vg += k * model_rows * D;
+    if (qg != nullptr) qg += k * model_rows;
+    out4 += k * (int64_t)gridDim.x * 4;
+    info2 += k * (int64_t)gridDim.x * 2;
+  }
   const bool prior = blockIdx.y == 1;
   const int64_t off = offsets[b];
   const int64_t n = offsets[b + 1] - off;
@@ -228,6 +242,30 @@ int run_leg_batch_w(const T* ts, const int64_t* offsets, int64_t B, const T* G, 
     });
     hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_WEIGHTED>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets,
                        G, basis, v, q, max_rows, out4, info2, Kb, reinterpret_cast<const unsigned char*>(weights));
+    return 0;
+  }
+}
+
+// M models over the same batch (LEG_ROWS_MODELS): grid (B, 2, M); M in 1..65535 is the caller's check
+template <typename T, int D>
+int run_leg_models(const T* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const T* G, const T* A, const T* v,
+                   const T* q, int64_t max_rows, double* out4, int* info2, hipStream_t st) {
+  if constexpr (!leg_batch_supported<T, D>()) {
+    return -2;
+  } else {
+    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
+    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
+    const size_t lds = leg_batch_lds_bytes<T, D>();
+    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
+    std::call_once(once[dev], [lds] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS>), dim3((unsigned)B, 2u, (unsigned)M), dim3(NW), lds, st, ts,
+                       offsets, G, A, v, q, max_rows, out4, info2, 0, (const unsigned char*)nullptr, R);
     return 0;
   }
 }

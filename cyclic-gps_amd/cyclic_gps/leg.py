@@ -844,6 +844,242 @@ def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None)
     return -0.5 * ((red[:, 3] - red[:, 0]) + (n * llt_det + red[:, 1] - red[:, 2]))
 
 
+# ---- many models over one batch ------------------------------------------------------------------------------------
+# The other axis of the batch: M parameter sets (the starts of a fit, a population of chains, a grid of length scales,
+# the components of a mixture) on the same B series.  Forward: grid (B, 2, M) of cgps_leg_loglik_models, one launch.
+# Backward: the block-diagonal system "model 0's batch, then model 1's batch, ..." of M R rows, assembled by
+# cgps_peg_precision_models from the one ts and the M generators, and its adjoint cgps_peg_precision_adjoint_models.
+MODELS_BACKWARD_MAX_ROWS = 1 << 22
+"""The backward of ``log_likelihood_models`` runs in chunks of whole models whose concatenated rows stay under this
+(a chunk always holds at least one model): about ten [rows, d, d] arrays are live at once, 0.84 GB each for a full
+chunk at d = 5 in fp64."""
+
+
+def _contract(a, b):
+    """a [..., p, q] times b [..., q, r] for a small q, as q outer products added up in ascending order with plain
+    elementwise multiplies and adds: every entry is rounded the same way whatever the other dimensions are, so a
+    model's operands do not depend on how many models or rows stand next to them (a batched GEMM may pick another
+    kernel, and another order of summation, for another batch size)."""
+    out = a[..., :, 0, None] * b[..., 0, None, :]
+    for j in range(1, a.shape[-1]):
+        out = out + a[..., :, j, None] * b[..., j, None, :]
+    return out
+
+
+def _spd_inverse_logdet(S):
+    """(S^-1, log|S|) of symmetric positive definite S [M, o, o] for a small o, by Gauss-Jordan elimination without
+    pivoting in elementwise operations over the models: as ``_contract``, nothing a model gets depends on its
+    neighbours (a batched factorisation may take another route for another batch size), and nothing is read on the
+    host.  Differentiable."""
+    M, o = S.shape[0], S.shape[1]
+    aug = torch.cat([S, torch.eye(o, dtype=S.dtype, device=S.device).expand(M, o, o)], -1)
+    logdet = None
+    for j in range(o):
+        piv = aug[:, j, j]
+        logdet = torch.log(piv) if logdet is None else logdet + torch.log(piv)
+        row = aug[:, j, :] / piv.unsqueeze(-1)
+        aug = aug - aug[:, :, j, None] * row.unsqueeze(1)        # clears column j everywhere, row j included
+        aug = torch.cat([aug[:, :j], row.unsqueeze(1), aug[:, j + 1:]], 1)
+    return aug[:, :, o:], logdet
+
+
+def _peg_precision_models(ts, G, cut):
+    """Blocks of the PEG precision of the same rows under G[m, d, d], model after model (cgps_peg_precision_models):
+    Rs [m R, d, d], Os [m R - 1, d, d] with zero blocks between two models.  No autograd graph."""
+    from . import _hip
+    m, d, R = G.shape[0], G.shape[1], ts.shape[0]
+    Rs = torch.empty(m * R, d, d, dtype=G.dtype, device=G.device)
+    Os = torch.empty(m * R - 1, d, d, dtype=G.dtype, device=G.device)
+    info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_peg_precision_models(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), R, m, d, _hip.dtype_code(G.dtype),
+                                                    _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
+    return Rs, Os
+
+
+def _peg_precision_adjoint_models(ts, G, cut, gRs, gOs, want_ts):
+    """(d loss / d G[m, d, d], d loss / d ts [R] or None) through cgps_peg_precision_adjoint_models: every model's
+    partial sums added per model, the models' gradients in ts added over the models."""
+    from . import _hip
+    m, d, R = G.shape[0], G.shape[1], ts.shape[0]
+    if R < 2:
+        return torch.zeros_like(G), (torch.zeros_like(ts) if want_ts else None)
+    part = torch.empty(m, (R - 1 + 63) // 64, d, d, dtype=G.dtype, device=G.device)
+    gtau = torch.empty(m, R - 1, dtype=G.dtype, device=G.device) if want_ts else None
+    _hip.check(_hip.lib().cgps_peg_precision_adjoint_models(
+        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), R, m, d, _hip.dtype_code(G.dtype), _hip.ptr(gRs.contiguous()),
+        _hip.ptr(gOs.contiguous()), _hip.ptr(part), _hip.ptr(gtau), _hip.stream_ptr()))
+    gts = None
+    if want_ts:
+        z = gtau.new_zeros(m, 1)
+        gts = (torch.cat([z, gtau], 1) - torch.cat([gtau, z], 1)).sum(0)
+    return part.sum(1), gts
+
+
+def leg_loglik_models_reductions(ts, G, A, v, q, plan):
+    """``leg_loglik_batch_reductions`` for M models over the same batch, no autograd graph: [M, B, 4] fp64 and [M, B, 2]
+    info words from one launch (cgps_leg_loglik_models; series longer than BATCH_MAX_ROWS through
+    cgps_leg_mahal_logdet_pair per model and series on the same stream).  ts [R]; G, A [M, d, d]; v [M, R, d];
+    q [M, R]; all in G's dtype, contiguous."""
+    from . import _hip
+    M, d, dt = G.shape[0], G.shape[1], G.dtype
+    out = torch.empty(M, plan.B, 4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(M, plan.B, 2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_loglik_models(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, plan.R, M, _hip.ptr(G),
+                                                 _hip.ptr(A), _hip.ptr(v), _hip.ptr(q), d, _hip.dtype_code(dt),
+                                                 BATCH_MAX_ROWS, _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    for b in plan.long:
+        for k in range(M):
+            s, e = plan.starts[b], plan.starts[b + 1]
+            o4, i2 = _leg_pair_raw(ts[s:e], G[k], A[k], v[k, s:e])
+            out[k, b, :3] = o4[[0, 1, 3]]
+            out[k, b, 3] = q[k, s:e].to(torch.float64).sum()
+            info[k, b] = i2
+    return out, info
+
+
+def _raise_models_not_pd(info):
+    bad = info.cpu()
+    hits = torch.nonzero(bad.amax(2)).tolist()
+    if hits:
+        k, b = hits[0]
+        code = int(bad[k, b, 0]) or int(bad[k, b, 1])
+        raise cr.NotPSDError("LEG models: model %d, series %d: a block near its row %d is not positive definite "
+                             "(or a time gap has zero length)" % (k, b, code - 1))
+
+
+class _LegModelsFn(torch.autograd.Function):
+    """Forward: the reductions of every (model, series) in one launch.  Backward: ``_LegBatchFn``'s on the concatenated
+    system of all models' batches, block-diagonal over models and series, in chunks of whole models."""
+
+    @staticmethod
+    def forward(ctx, ts, G, A, v, q, plan):
+        ctx.plan = plan
+        ctx.save_for_backward(ts, G, A, v)
+        out, info = leg_loglik_models_reductions(ts.detach(), G.detach(), A.detach(), v.detach(), q.detach(), plan)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            _raise_models_not_pd(info)
+        return out.to(G.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        ts, G, A, v = ctx.saved_tensors
+        plan = ctx.plan
+        need_ts, need_G, need_A, need_v, need_q = ctx.needs_input_grad[:5]
+        M, d, R = G.shape[0], G.shape[1], plan.R
+        gout = gout.to(G.dtype)
+
+        def rows(g, c):                                   # column c of a chunk's [m, B, 4], spread over the m R rows
+            return g[:, :, c].repeat_interleave(plan.lens, dim=1, output_size=R).reshape(-1)
+
+        gq = rows(gout, 3).view(M, R) if need_q else None
+        gts = torch.zeros_like(ts) if need_ts else None
+        gG = torch.empty_like(G) if need_G else None
+        gA = torch.empty_like(A) if need_A else None
+        gv = torch.empty_like(v) if need_v else None
+        if need_ts or need_G or need_A or need_v:
+            per = max(1, MODELS_BACKWARD_MAX_ROWS // R)
+            for k0 in range(0, M, per):
+                k1 = min(M, k0 + per)
+                m, g, Gc = k1 - k0, gout[k0:k1], G[k0:k1]
+                Rs, Os = _peg_precision_models(ts, Gc, plan.cut)
+                gm, gl = rows(g, 0), rows(g, 1)
+                dec, w = cr.decompose_solve((Rs.view(m, R, d, d) + A[k0:k1].unsqueeze(1)).view(m * R, d, d), Os,
+                                            v[k0:k1].reshape(m * R, d))
+                if need_v:
+                    gv[k0:k1] = (2 * gm.unsqueeze(-1) * w).view(m, R, d)
+                if need_ts or need_G or need_A:
+                    Sd, So = cr.inverse_blocks(dec)
+                    gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
+                    if need_A:
+                        gA[k0:k1] = gR.view(m, R, d, d).sum(1)
+                    if need_ts or need_G:
+                        # (the entries of gO between two models hold whatever the zero coupling gives: never read)
+                        gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
+                        if m * R > 1:        # (one row: its block is I whatever G and ts are)
+                            gs = rows(g, 2)
+                            Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
+                            gR = gR + gs.view(-1, 1, 1) * Sd0
+                            gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
+                        gGc, gtsc = _peg_precision_adjoint_models(ts, Gc, plan.cut, gR, gO, need_ts)
+                        if need_G:
+                            gG[k0:k1] = gGc
+                        if need_ts:
+                            gts = gts + gtsc                      # chunks in ascending order
+        return gts, gG, gA, gv, gq, None
+
+
+def _models_operands(ms):
+    """The models' matrices stacked: (N, R, B, Lambda) as [M, ...]; ValueError unless they share rank, obs_dim, dtype
+    and device."""
+    ms = list(ms)
+    if not ms:
+        raise ValueError("log_likelihood_models wants at least one model")
+    for k, m in enumerate(ms):
+        if not isinstance(m, LEGMatrices):
+            raise ValueError("model %d is not a LEGMatrices" % k)
+        for name in ("N", "R", "B", "Lambda"):
+            a, b = getattr(m, name), getattr(ms[0], name)
+            if tuple(a.shape) != tuple(b.shape) or a.dtype != b.dtype or a.device != b.device:
+                raise ValueError("model %d: %s is %s %s on %s, model 0 has %s %s on %s (the models must share rank, obs_dim, "
+                                 "dtype and device)" % (k, name, tuple(a.shape), a.dtype, a.device, tuple(b.shape), b.dtype,
+                                                        b.device))
+    m0 = ms[0]
+    d, o = m0.N.shape[0], m0.B.shape[0]
+    if (tuple(m0.N.shape) != (d, d) or tuple(m0.R.shape) != (d, d) or tuple(m0.B.shape) != (o, d)
+            or tuple(m0.Lambda.shape) != (o, o)):
+        raise ValueError("a model wants N [d, d], R [d, d], B [obs, d] and Lambda [obs, obs], got %s, %s, %s, %s"
+                         % tuple(tuple(t.shape) for t in (m0.N, m0.R, m0.B, m0.Lambda)))
+    if len({t.dtype for t in (m0.N, m0.R, m0.B, m0.Lambda)}) != 1 or len({t.device for t in (m0.N, m0.R, m0.B, m0.Lambda)}) != 1:
+        raise ValueError("a model's four matrices must share dtype and device")
+    return ms, tuple(torch.stack([getattr(m, name) for m in ms]) for name in ("N", "R", "B", "Lambda"))
+
+
+def log_likelihood_models(ms, ts, xs, lengths=None):
+    """log p(xs_b | ts_b) of M LEG models for the same B series, as an [M, B] tensor of the models' dtype: entry (k, b)
+    is ``log_likelihood(ms[k], series b)``.  What several starts of a fit, a population of chains, a grid of length
+    scales or the responsibilities of a mixture of LEG processes evaluate.
+
+    ``ms``: a non-empty sequence of ``LEGMatrices`` of one rank, obs_dim, dtype and device (ValueError otherwise, before
+    anything is launched).  ``ts`` / ``xs`` / ``lengths``: the two layouts of ``log_likelihood_batch``.  An empty batch
+    gives an [M, 0] tensor.  Differentiable in every model's N, R, B, Lambda, in xs and in ts, for any upstream
+    gradient and any subset of trainable tensors.  On the GPU one launch for all models and all series up to
+    BATCH_MAX_ROWS rows (cgps_leg_loglik_models), longer series per (model, series) through
+    cgps_leg_mahal_logdet_pair, and a backward through the concatenated system of all models' batches in chunks of
+    MODELS_BACKWARD_MAX_ROWS rows; a repeated call with the same lengths copies nothing from the host.  d = 8, fp64
+    d = 6 and CPU tensors take one ``log_likelihood_batch`` per model.  With ``cr.CHECK_POSITIVE_DEFINITE`` a system
+    that is not positive definite raises ``NotPSDError`` naming its model and series; without it that slot is NaN and
+    no other slot is affected."""
+    ms, (Nm, Rm, Bm, Lm) = _models_operands(ms)
+    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    M, d, o, dt = len(ms), Nm.shape[1], Bm.shape[1], Nm.dtype
+    if xs.shape[1] != o:
+        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
+    if not lengths:
+        return torch.empty(M, 0, dtype=dt, device=ts.device)
+    if not batch_supported(ts, Nm[0]):
+        outs = []
+        for k, m in enumerate(ms):
+            try:
+                outs.append(log_likelihood_batch(m, ts, xs, lengths))
+            except cr.NotPSDError as e:
+                raise cr.NotPSDError("LEG models: model %d: %s" % (k, e)) from None
+        return torch.stack(outs)
+    plan = _cached_batch_plan(lengths, Nm.device)
+    G = _contract(Nm, Nm.transpose(1, 2)) + (Rm - Rm.transpose(1, 2)) + _scaled_eye(d, 1e-5, dt, Nm.device)
+    LLT = _contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(o, 1e-9, dt, Nm.device)
+    Li, llt_det = _spd_inverse_logdet(LLT)
+    llt_det = llt_det + o * math.log(2 * math.pi)
+    xl = _contract(xs.unsqueeze(0), Li)                   # [M, R, obs]
+    v = _contract(xl, Bm).to(dt).contiguous()             # [M, R, d]
+    q = xl[..., 0] * xs[:, 0]
+    for c in range(1, o):
+        q = q + xl[..., c] * xs[:, c]
+    A = _contract(_contract(Bm.transpose(1, 2), Li), Bm).to(dt).contiguous()
+    red = _LegModelsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A, v, q.to(dt).contiguous(), plan)
+    n = plan.lens.to(dt)
+    return -0.5 * ((red[..., 3] - red[..., 0]) + (n * llt_det.unsqueeze(1) + red[..., 1] - red[..., 2]))
+
+
 # ---- missing observations ------------------------------------------------------------------------------------------
 # A row that observes the channels S only contributes B^T Li B to its diagonal block of the posterior precision, with
 # Li = (LLT[S, S])^-1 embedded in zeros (zero when S is empty); everything after the assembly -- factor, solve, selected

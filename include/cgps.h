@@ -310,6 +310,39 @@ int cgps_peg_precision_adjoint_seg(const void* ts, const void* G, const unsigned
                                    int dtype, const void* gRs, const void* gOs, void* gG_partial, void* gtau,
                                    void* stream);
 
+/* cgps_leg_loglik_batch for M models over the same batch of series, in ONE launch (several starts of a fit, a
+ * population of chains, a grid of length scales, the components of a mixture).  ts[R], offsets[B+1] (int64 DEVICE
+ * memory, offsets[B] = R) describe the batch once; model k brings G[k], A[k] of G[M][d][d], A[M][d][d] (A NULL: no
+ * diagonal term), v[k] of v[M][R][d] (NULL: zeros) and q[k] of q[M][R] (NULL: zeros).  Grid (B, 2, M): the workgroup of
+ * (series b, system, model k) does for (G[k], A[k], v[k], q[k]) what cgps_leg_loglik_batch does for its one model, and
+ *   out4[k][b][0..3], info2[k][b][0..1]
+ * are that call's out4[b], info2[b] bit for bit; every workgroup owns its slot (no records, counters or atomics on
+ * floating-point values).  A series of more than max_rows rows is skipped for every model (nothing written).
+ * M outside 1..65535, B < 0, R < 0 or a null ts, offsets, G, out4 or info2 with B > 0: CGPS_ERR_ARG before anything is
+ * launched; B = 0 returns CGPS_OK; CGPS_ERR_UNSUPPORTED for d = 8 and fp64 d = 6.  No workspace. */
+int cgps_leg_loglik_models(const void* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const void* G,
+                           const void* A, const void* v, const void* q, int d, int dtype, int64_t max_rows,
+                           double* out4, int* info2, void* stream);
+
+/* cgps_peg_precision_seg of the same R rows under M generators G[M][d][d]: the blocks of the block-diagonal system
+ * "model 0's batch, then model 1's batch, ...", Rs[M R][d][d] and Os[M R - 1][d][d].  ts[R] and cut[R-1] (NULL: one
+ * series) are read by every model and not tiled in memory; rows k R .. (k+1) R - 1 use G[k] and equal what
+ * cgps_peg_precision_seg writes for (ts, G[k], cut) bit for bit.  The coupling block between two models, Os[k R - 1],
+ * is written as zeros and nothing is evaluated for it.  info: 0 or 1 + a row of the concatenated system next to a
+ * singular gap.  M outside 1..65535, R < 1 or a null pointer: CGPS_ERR_ARG before anything is launched;
+ * CGPS_ERR_UNSUPPORTED for d = 8 and fp64 d = 6 (the block sizes cgps_leg_loglik_models is not built for). */
+int cgps_peg_precision_models(const void* ts, const void* G, const unsigned char* cut, int64_t R, int64_t M, int d,
+                              int dtype, void* Rs, void* Os, int* info, void* stream);
+
+/* Adjoint of cgps_peg_precision_models.  gRs[M R][d][d], gOs[M R - 1][d][d] (the entries k R - 1 between two models
+ * are never read).  No workgroup straddles two models: gG_partial[M][ceil((R-1)/64)][d][d] holds model k's shares
+ * (the caller adds them per model), gtau[M][R-1] (may be NULL) model k's d loss / d (t_{i+1} - t_i); a cut gap gets
+ * gtau = 0 and adds nothing.  Slice k equals cgps_peg_precision_adjoint_seg on that model's slices bit for bit.
+ * R >= 2, as cgps_peg_precision_adjoint_seg wants N >= 2; errors as cgps_peg_precision_models. */
+int cgps_peg_precision_adjoint_models(const void* ts, const void* G, const unsigned char* cut, int64_t R, int64_t M,
+                                      int d, int dtype, const void* gRs, const void* gOs, void* gG_partial,
+                                      void* gtau, void* stream);
+
 /* Blocks of the POSTERIOR precision of several series concatenated, written once: what cgps_peg_precision_seg writes,
  * with every row's observation term added to its diagonal block as the last operation before the store,
  *   K_Rs[i] = Rs[i] + term_i,   Os and info exactly those of cgps_peg_precision_seg.
