@@ -37,15 +37,31 @@
 // the model: the workgroup moves G, A, v, q, out4 and info2 to model k's slices (G[M][d][d], A[M][d][d], v[M][R][d],
 // q[M][R] with R = model_rows, out4[M][B][4], info2[M][B][2]) and is a LEG_ROWS_PLAIN workgroup from there on.  k is
 // workgroup-uniform, so G[k] and A[k] still arrive through scalar loads.
+// ROWS = LEG_ROWS_MODELS_TABLE (cgps_leg_loglik_models_obs) and LEG_ROWS_MODELS_WEIGHTED (cgps_leg_loglik_models_w): the
+// product of the two axes, grid (B, 2, M).  "Which model" (leg_rows_models) and "where a row's diagonal term comes
+// from" (leg_rows_source) are read off ROWS separately.  The model prologue moves one more slice: the table by
+// k entries d d (A_table[M][P][d][d]; `pattern`, one byte per row, describes the batch once and is read by every
+// model), or the basis by k entries d d and the weights by k model_rows entries (basis[M][Kb][d][d],
+// weights[M][R][Kb]: the weights hold the entries of each model's own Li).  From there on the workgroup is a
+// LEG_ROWS_TABLE / LEG_ROWS_WEIGHTED workgroup; the offsets are 64-bit products of workgroup-uniform values.
 // LEG_ROWS_PLAIN reads neither argument, and every difference is an `if constexpr` on the kernel itself: each source's
-// instruction stream is the one it had before the others existed.  The TABLE and WEIGHTED kernels are instantiated
-// by the translation unit that calls run_leg_batch_obs / run_leg_batch_w (cgps_leg_obs.hip).
+// instruction stream is the one it had before the others existed.  The TABLE and WEIGHTED kernels, with and without
+// models, are instantiated by the translation unit that calls run_leg_batch_obs / run_leg_batch_w / run_leg_models_obs /
+// run_leg_models_w (cgps_leg_obs.hip).
 #pragma once
 
 namespace cgps {
 
 constexpr int LEG_BATCH_THREADS = 256;
-constexpr int LEG_ROWS_PLAIN = 0, LEG_ROWS_TABLE = 1, LEG_ROWS_WEIGHTED = 2, LEG_ROWS_MODELS = 3;
+constexpr int LEG_ROWS_PLAIN = 0, LEG_ROWS_TABLE = 1, LEG_ROWS_WEIGHTED = 2, LEG_ROWS_MODELS = 3, LEG_ROWS_MODELS_TABLE = 4,
+              LEG_ROWS_MODELS_WEIGHTED = 5;
+
+constexpr bool leg_rows_models(int rows) { return rows >= LEG_ROWS_MODELS; }        // blockIdx.z names a model
+constexpr int leg_rows_source(int rows) {                                            // PLAIN, TABLE or WEIGHTED
+  return rows == LEG_ROWS_MODELS_TABLE ? LEG_ROWS_TABLE
+         : rows == LEG_ROWS_MODELS_WEIGHTED ? LEG_ROWS_WEIGHTED
+         : rows == LEG_ROWS_MODELS ? LEG_ROWS_PLAIN : rows;
+}
 
 template <typename T, int D>
 constexpr int leg_batch_lanes() { return TileCfg<T, D>::NG1; }       // 256, or 128 for 7 x 7 fp64 (LDS)
@@ -62,10 +78,16 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
   StageSmem<T, D, NT, NW> sm(smem);
   const int tid = threadIdx.x;
   const int64_t b = blockIdx.x;
-  if constexpr (ROWS == LEG_ROWS_MODELS) {                     // model k's slices (workgroup-uniform)
+  constexpr int SRC = leg_rows_source(ROWS);
+  if constexpr (leg_rows_models(ROWS)) {                       // model k's slices (workgroup-uniform)
     const int64_t k = blockIdx.z;
     Gg += k * (D * D);
-    if (Ag != nullptr) Ag += k * (D * D);
+    if constexpr (SRC == LEG_ROWS_PLAIN) {
+      if (Ag != nullptr) Ag += k * (D * D);
+    } else {                                                   // model k's table / basis; its weights (the bytes are shared)
+      Ag += k * (int64_t)entries * (D * D);
+      if constexpr (SRC == LEG_ROWS_WEIGHTED) pattern += k * model_rows * (int64_t)entries * (int64_t)sizeof(T);
+    }
     if (vg != nullptr) vg += k * model_rows * D;
     if (qg != nullptr) qg += k * model_rows;
     out4 += k * (int64_t)gridDim.x * 4;
@@ -79,8 +101,8 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
   const T* __restrict__ vb = (prior || vg == nullptr) ? nullptr : vg + off * D;
   const T* __restrict__ Ab = prior ? nullptr : Ag;
   // the series' own bytes / weights: what the rows below index is the local row plus the series' offset
-  const unsigned char* __restrict__ pb = ROWS == LEG_ROWS_TABLE ? pattern + off : nullptr;
-  const T* __restrict__ wb = ROWS == LEG_ROWS_WEIGHTED ? reinterpret_cast<const T*>(pattern) + off * (int64_t)entries : nullptr;
+  const unsigned char* __restrict__ pb = SRC == LEG_ROWS_TABLE ? pattern + off : nullptr;
+  const T* __restrict__ wb = SRC == LEG_ROWS_WEIGHTED ? reinterpret_cast<const T*>(pattern) + off * (int64_t)entries : nullptr;
   if (tid == 0) *sm.sfail = 0x7fffffff;
 
   const int64_t C = (n + NT - 1) / NT;                         // rows per lane
@@ -105,9 +127,9 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
       set_zero<T, D>(cR);
       set_zero<T, D>(cB);
     }
-    if constexpr (ROWS == LEG_ROWS_TABLE)
+    if constexpr (SRC == LEG_ROWS_TABLE)
       leg_row<T, D>(tsb, Gg, leg_obs_block<T, D>(Ab, pb, entries, r0), vb, r0, n, cR, cB, Rc, Cc, yc, fail);
-    else if constexpr (ROWS == LEG_ROWS_WEIGHTED) {
+    else if constexpr (SRC == LEG_ROWS_WEIGHTED) {
       leg_add_weighted_basis<T, D>(Ab, wb, entries, r0, cR);
       leg_row<T, D>(tsb, Gg, (const T*)nullptr, vb, r0, n, cR, cB, Rc, Cc, yc, fail);
     } else
@@ -116,9 +138,9 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
 #pragma unroll 1
   for (int j = 0; j < L - 1; ++j) {
     T Rn[D][D], On[D][D], yn[D];
-    if constexpr (ROWS == LEG_ROWS_TABLE)
+    if constexpr (SRC == LEG_ROWS_TABLE)
       leg_row<T, D>(tsb, Gg, leg_obs_block<T, D>(Ab, pb, entries, r0 + j + 1), vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
-    else if constexpr (ROWS == LEG_ROWS_WEIGHTED) {
+    else if constexpr (SRC == LEG_ROWS_WEIGHTED) {
       leg_add_weighted_basis<T, D>(Ab, wb, entries, r0 + j + 1, cR);
       leg_row<T, D>(tsb, Gg, (const T*)nullptr, vb, r0 + j + 1, n, cR, cB, Rn, On, yn, fail);
     } else
@@ -266,6 +288,58 @@ int run_leg_models(const T* ts, const int64_t* offsets, int64_t B, int64_t R, in
     });
     hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS>), dim3((unsigned)B, 2u, (unsigned)M), dim3(NW), lds, st, ts,
                        offsets, G, A, v, q, max_rows, out4, info2, 0, (const unsigned char*)nullptr, R);
+    return 0;
+  }
+}
+
+// M models over the same batch, rows that differ in what they observe (LEG_ROWS_MODELS_TABLE): table [M][P][d][d], the
+// pattern bytes once for the batch; M in 1..65535, entries in 1..256 and the non-null pointers are the caller's checks
+template <typename T, int D>
+int run_leg_models_obs(const T* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const T* G, const T* table,
+                       int entries, const unsigned char* pattern, const T* v, const T* q, int64_t max_rows, double* out4,
+                       int* info2, hipStream_t st) {
+  if constexpr (!leg_batch_supported<T, D>()) {
+    return -2;
+  } else {
+    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
+    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
+    const size_t lds = leg_batch_lds_bytes<T, D>();
+    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
+    std::call_once(once[dev], [lds] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_TABLE>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_TABLE>), dim3((unsigned)B, 2u, (unsigned)M), dim3(NW), lds,
+                       st, ts, offsets, G, table, v, q, max_rows, out4, info2, entries, pattern, R);
+    return 0;
+  }
+}
+
+// M models over the same batch, rows with noise of their own (LEG_ROWS_MODELS_WEIGHTED): basis [M][Kb][d][d], weights
+// [M][R][Kb]; M in 1..65535, Kb in 1..64 and the non-null pointers are the caller's checks
+template <typename T, int D>
+int run_leg_models_w(const T* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const T* G, const T* basis, int Kb,
+                     const T* weights, const T* v, const T* q, int64_t max_rows, double* out4, int* info2, hipStream_t st) {
+  if constexpr (!leg_batch_supported<T, D>()) {
+    return -2;
+  } else {
+    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
+    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
+    const size_t lds = leg_batch_lds_bytes<T, D>();
+    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
+    std::call_once(once[dev], [lds] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_WEIGHTED>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_WEIGHTED>), dim3((unsigned)B, 2u, (unsigned)M), dim3(NW),
+                       lds, st, ts, offsets, G, basis, v, q, max_rows, out4, info2, Kb,
+                       reinterpret_cast<const unsigned char*>(weights), R);
     return 0;
   }
 }

@@ -59,6 +59,8 @@ _SIGNATURES = {
     "cgps_peg_precision_seg": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "cgps_peg_precision_adjoint_seg": (_int, [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "cgps_leg_loglik_models": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _int, _i64, _vp, _vp, _vp]),
+    "cgps_leg_loglik_models_obs": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _i64, _vp, _vp, _vp]),
+    "cgps_leg_loglik_models_w": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _i64, _vp, _vp, _vp]),
     "cgps_peg_precision_models": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "cgps_peg_precision_adjoint_models": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "cgps_leg_intercast": (_int, [_vp, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1008,6 +1008,257 @@ class _LegModelsFn(torch.autograd.Function):
         return gts, gG, gA, gv, gq, None
 
 
+def leg_loglik_models_reductions_obs(ts, G, A_table, pattern, v, q, plan):
+    """``leg_loglik_models_reductions`` of series whose rows observe different channels, still ONE launch
+    (cgps_leg_loglik_models_obs): the mask belongs to the data, so ``pattern`` (uint8 [R] on the device, a byte >= P takes
+    the last entry) is shared by the models and every model brings a table of its own, A_table [M, P, d, d] with
+    1 <= P <= 256.  ts [R]; G [M, d, d]; v [M, R, d]; q [M, R]; all in G's dtype, contiguous.  Series longer than
+    BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_obs per model and series.  No autograd graph."""
+    from . import _hip
+    M, d, dt = G.shape[0], G.shape[1], G.dtype
+    if pattern.dtype != torch.uint8 or pattern.shape != (plan.R,) or not pattern.is_cuda:
+        raise ValueError("pattern must be a uint8 device tensor of shape [%d], got %s %s"
+                         % (plan.R, pattern.dtype, tuple(pattern.shape)))
+    if A_table.dim() != 4 or A_table.shape[0] != M or tuple(A_table.shape[2:]) != (d, d) or not 1 <= A_table.shape[1] <= 256:
+        raise ValueError("A_table must be [%d, P, %d, %d] with 1 <= P <= 256, got %s" % (M, d, d, tuple(A_table.shape)))
+    if tuple(v.shape) != (M, plan.R, d) or tuple(q.shape) != (M, plan.R):
+        raise ValueError("v must be [%d, %d, %d] and q [%d, %d], got %s and %s"
+                         % (M, plan.R, d, M, plan.R, tuple(v.shape), tuple(q.shape)))
+    if A_table.dtype != dt or not A_table.is_cuda:
+        raise ValueError("A_table must be a device tensor of G's dtype %s, got %s" % (dt, A_table.dtype))
+    pattern, A_table = pattern.contiguous(), A_table.contiguous()
+    out = torch.empty(M, plan.B, 4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(M, plan.B, 2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_loglik_models_obs(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, plan.R, M, _hip.ptr(G),
+                                                     _hip.ptr(A_table), A_table.shape[1], _hip.ptr(pattern), _hip.ptr(v),
+                                                     _hip.ptr(q), d, _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out),
+                                                     _hip.ptr(info), _hip.stream_ptr()))
+    for b in plan.long:
+        for k in range(M):
+            s, e = plan.starts[b], plan.starts[b + 1]
+            o4, i2 = _leg_pair_obs_raw(ts[s:e], G[k], A_table[k], pattern[s:e], v[k, s:e])
+            out[k, b, :3] = o4[[0, 1, 3]]
+            out[k, b, 3] = q[k, s:e].to(torch.float64).sum()
+            info[k, b] = i2
+    return out, info
+
+
+def leg_loglik_models_reductions_w(ts, G, basis, weights, v, q, plan):
+    """``leg_loglik_models_reductions`` of series whose rows each add a term of their own, still ONE launch
+    (cgps_leg_loglik_models_w): K of (model k, series b) = PEG precision(ts_b, G[k]) + blockdiag(sum_j weights[k, i, j]
+    basis[k, j]) over the series' rows.  basis [M, Kb, d, d] with 1 <= Kb <= 64 and weights [M, R, Kb] (the entries of
+    each model's own inverse noise covariance), device tensors of G's dtype.  ts [R]; G [M, d, d]; v [M, R, d]; q [M, R];
+    contiguous.  Series longer than BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_w per model and series.  No
+    autograd graph."""
+    from . import _hip
+    M, d, dt = G.shape[0], G.shape[1], G.dtype
+    if basis.dim() != 4 or basis.shape[0] != M or tuple(basis.shape[2:]) != (d, d) or not 1 <= basis.shape[1] <= 64:
+        raise ValueError("basis must be [%d, Kb, %d, %d] with 1 <= Kb <= 64, got %s" % (M, d, d, tuple(basis.shape)))
+    Kb = basis.shape[1]
+    if tuple(weights.shape) != (M, plan.R, Kb):
+        raise ValueError("weights must be [%d, %d, %d] (Kb weights per model and row of the batch), got %s"
+                         % (M, plan.R, Kb, tuple(weights.shape)))
+    if tuple(v.shape) != (M, plan.R, d) or tuple(q.shape) != (M, plan.R):
+        raise ValueError("v must be [%d, %d, %d] and q [%d, %d], got %s and %s"
+                         % (M, plan.R, d, M, plan.R, tuple(v.shape), tuple(q.shape)))
+    if basis.dtype != dt or weights.dtype != dt:
+        raise ValueError("basis and weights must have G's dtype %s, got %s and %s" % (dt, basis.dtype, weights.dtype))
+    if not (basis.is_cuda and weights.is_cuda):
+        raise ValueError("basis and weights must be device tensors")
+    basis, weights = basis.contiguous(), weights.contiguous()
+    out = torch.empty(M, plan.B, 4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(M, plan.B, 2, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_loglik_models_w(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, plan.R, M, _hip.ptr(G),
+                                                   _hip.ptr(basis), Kb, _hip.ptr(weights), _hip.ptr(v), _hip.ptr(q), d,
+                                                   _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out), _hip.ptr(info),
+                                                   _hip.stream_ptr()))
+    for b in plan.long:
+        for k in range(M):
+            s, e = plan.starts[b], plan.starts[b + 1]
+            o4, i2 = _leg_pair_w_raw(ts[s:e], G[k], basis[k], weights[k, s:e], v[k, s:e])
+            out[k, b, :3] = o4[[0, 1, 3]]
+            out[k, b, 3] = q[k, s:e].to(torch.float64).sum()
+            info[k, b] = i2
+    return out, info
+
+
+def _models_backward(ctx_needs, plan, ts, G, v, gout, diag_term, diag_grads):
+    """The chunked backward that ``_LegModelsObsFn`` and ``_LegModelsWFn`` share: ``_LegModelsFn``'s, with K's diagonal
+    Rs + diag_term(k0, k1) [m, R, d, d] and the rows' block gradients gR [m, R, d, d] of the chunk handed to
+    diag_grads(k0, k1, gR).  Returns (gts, gG, gv, gq)."""
+    need_ts, need_G, need_diag, need_v, need_q = ctx_needs
+    M, d, R = G.shape[0], G.shape[1], plan.R
+    gout = gout.to(G.dtype)
+
+    def rows(g, c):                                   # column c of a chunk's [m, B, 4], spread over the m R rows
+        return g[:, :, c].repeat_interleave(plan.lens, dim=1, output_size=R).reshape(-1)
+
+    gq = rows(gout, 3).view(M, R) if need_q else None
+    gts = torch.zeros_like(ts) if need_ts else None
+    gG = torch.empty_like(G) if need_G else None
+    gv = torch.empty_like(v) if need_v else None
+    if need_ts or need_G or need_diag or need_v:
+        per = max(1, MODELS_BACKWARD_MAX_ROWS // R)
+        for k0 in range(0, M, per):
+            k1 = min(M, k0 + per)
+            m, g, Gc = k1 - k0, gout[k0:k1], G[k0:k1]
+            Rs, Os = _peg_precision_models(ts, Gc, plan.cut)
+            gm, gl = rows(g, 0), rows(g, 1)
+            dec, w = cr.decompose_solve((Rs.view(m, R, d, d) + diag_term(k0, k1)).view(m * R, d, d), Os,
+                                        v[k0:k1].reshape(m * R, d))
+            if need_v:
+                gv[k0:k1] = (2 * gm.unsqueeze(-1) * w).view(m, R, d)
+            if need_ts or need_G or need_diag:
+                Sd, So = cr.inverse_blocks(dec)
+                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
+                if need_diag:
+                    diag_grads(k0, k1, gR.view(m, R, d, d))
+                if need_ts or need_G:
+                    # (the entries of gO between two models hold whatever the zero coupling gives: never read)
+                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
+                    if m * R > 1:        # (one row: its block is I whatever G and ts are)
+                        gs = rows(g, 2)
+                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
+                        gR = gR + gs.view(-1, 1, 1) * Sd0
+                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
+                    gGc, gtsc = _peg_precision_adjoint_models(ts, Gc, plan.cut, gR, gO, need_ts)
+                    if need_G:
+                        gG[k0:k1] = gGc
+                    if need_ts:
+                        gts = gts + gtsc                      # chunks in ascending order
+    return gts, gG, gv, gq
+
+
+class _LegModelsObsFn(torch.autograd.Function):
+    """``_LegModelsFn`` with a per-row observation pattern shared by the models and a table per model.  Forward:
+    cgps_leg_loglik_models_obs (one launch).  Backward: the same chunks of whole models with Rs + A_table[k][idx] as K's
+    diagonal; the gradient of A_table[k] is the per-pattern sum of model k's row gradients, a product with the one-hot
+    matrix of the pattern that all models share (no scatter: ``index_add_`` adds with atomics, in no fixed order)."""
+
+    @staticmethod
+    def forward(ctx, ts, G, A_table, v, q, pattern, plan):
+        ctx.plan = plan
+        ctx.save_for_backward(ts, G, A_table, v, pattern)
+        out, info = leg_loglik_models_reductions_obs(ts.detach(), G.detach(), A_table.detach(), pattern, v.detach(),
+                                                     q.detach(), plan)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            _raise_models_not_pd(info)
+        return out.to(G.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        ts, G, A_table, v, pattern = ctx.saved_tensors
+        plan = ctx.plan
+        P, d, R = A_table.shape[1], G.shape[1], plan.R
+        idx = pattern.long().clamp(max=P - 1)                    # the kernel's clamp
+        gA = torch.empty_like(A_table) if ctx.needs_input_grad[2] else None
+        codes = torch.arange(P, device=idx.device).unsqueeze(1)
+        step = max(1024, (1 << 24) // P)                         # rows per product: the one-hot matrix stays small
+
+        def diag_term(k0, k1):
+            return A_table[k0:k1][:, idx]
+
+        def diag_grads(k0, k1, gR):
+            acc = torch.zeros(k1 - k0, P, d * d, dtype=G.dtype, device=G.device)
+            for s in range(0, R, step):                          # (one product unless P * R > 2^24)
+                onehot = (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype)
+                acc = acc + torch.matmul(onehot, gR[:, s:s + step].reshape(k1 - k0, -1, d * d))
+            gA[k0:k1] = acc.view(k1 - k0, P, d, d)
+
+        gts, gG, gv, gq = _models_backward(ctx.needs_input_grad[:5], plan, ts, G, v, gout, diag_term, diag_grads)
+        return gts, gG, gA, gv, gq, None, None
+
+
+def _rows_product_models(a, b, rows=4096):
+    """``_rows_product`` per model: a [m, R, p] and b [m, R, q] give a^T b [m, p, q], the rows in chunks of ``rows`` added
+    up by one reduction in a fixed order, plus the product of the remainder."""
+    m, R = a.shape[0], a.shape[1]
+    C = R // rows
+    out = torch.bmm(a[:, C * rows:].transpose(1, 2), b[:, C * rows:])
+    if C:
+        out = out + torch.bmm(a[:, :C * rows].reshape(m * C, rows, -1).transpose(1, 2),
+                              b[:, :C * rows].reshape(m * C, rows, -1)).view(m, C, a.shape[2], b.shape[2]).sum(1)
+    return out
+
+
+class _LegModelsWFn(torch.autograd.Function):
+    """``_LegModelsFn`` with a weighted basis per row and model.  Forward: cgps_leg_loglik_models_w (one launch).
+    Backward: the same chunks of whole models with Rs + sum_j weights[k, i, j] basis[k, j] as K's diagonal; model k's
+    block gradients gR_i go to its basis as sum_i weights[k, i, j] gR_i and to its weights as <gR_i, basis[k, j]>, both
+    plain matrix products per model."""
+
+    @staticmethod
+    def forward(ctx, ts, G, basis, weights, v, q, plan):
+        ctx.plan = plan
+        ctx.save_for_backward(ts, G, basis, weights, v)
+        out, info = leg_loglik_models_reductions_w(ts.detach(), G.detach(), basis.detach(), weights.detach(), v.detach(),
+                                                   q.detach(), plan)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            _raise_models_not_pd(info)
+        return out.to(G.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        ts, G, basis, weights, v = ctx.saved_tensors
+        plan = ctx.plan
+        need_ts, need_G, need_b, need_w, need_v, need_q = ctx.needs_input_grad[:6]
+        Kb, d, R = basis.shape[1], G.shape[1], plan.R
+        gb = torch.empty_like(basis) if need_b else None
+        gw = torch.empty_like(weights) if need_w else None
+
+        def diag_term(k0, k1):
+            return torch.einsum("mrk,mkij->mrij", weights[k0:k1], basis[k0:k1])
+
+        def diag_grads(k0, k1, gR):
+            gR = gR.reshape(k1 - k0, R, d * d)
+            if need_b:
+                gb[k0:k1] = _rows_product_models(weights[k0:k1], gR).view(k1 - k0, Kb, d, d)
+            if need_w:
+                gw[k0:k1] = torch.bmm(gR, basis[k0:k1].reshape(k1 - k0, Kb, d * d).transpose(1, 2))
+
+        gts, gG, gv, gq = _models_backward((need_ts, need_G, need_b or need_w, need_v, need_q), plan, ts, G, v, gout,
+                                           diag_term, diag_grads)
+        return gts, gG, gb, gw, gv, gq, None
+
+
+def _models_pattern_tables(Bm, LLT, o, dt):
+    """``observation_tables`` for stacked models, elementwise over the models: (Li_table [M, P, o, o], A_table
+    [M, P, d, d], c_table [M, P]) for the P = 2^obs patterns."""
+    M = Bm.shape[0]
+    Mt = _pattern_mask_table(o, dt, Bm.device)                           # [P, o]
+    unobs = torch.diag_embed(1 - Mt)
+    W = Mt.unsqueeze(2) * LLT.unsqueeze(1) * Mt.unsqueeze(1) + unobs     # [M, P, o, o]
+    Wi, logdet_W = _spd_inverse_logdet(W.reshape(-1, o, o))
+    Li_table = Wi.view(M, -1, o, o) - unobs
+    A_table = _contract(_contract(Bm.transpose(1, 2).unsqueeze(1), Li_table), Bm.unsqueeze(1))
+    c_table = Mt.sum(1) * math.log(2 * math.pi) + logdet_W.view(M, -1)
+    return Li_table, A_table, c_table
+
+
+def _models_noise_rows(Bm, LLT, o, dt, observed, noise_var):
+    """``observation_weights`` for stacked models, elementwise over models and rows: (basis [M, Kb, d, d], weights
+    [M, R, Kb], Li_rows [M, R, o, o], c_rows [M, R]).  observed bool [R, o] or None; noise_var [R, o] or [R]."""
+    M = Bm.shape[0]
+    if noise_var.dim() == 1:
+        noise_var = noise_var.unsqueeze(-1).expand(-1, o)
+    s = noise_var.to(dt)
+    if observed is None:
+        Mt = torch.ones((), dtype=dt, device=Bm.device).expand(s.shape)
+    else:
+        s = torch.where(observed, s, torch.zeros((), dtype=dt, device=s.device))
+        Mt = observed.to(dt)
+    unobs = torch.diag_embed(1 - Mt)                                     # [R, o, o]
+    W = Mt.unsqueeze(2) * (LLT.unsqueeze(1) + torch.diag_embed(s)) * Mt.unsqueeze(1) + unobs     # [M, R, o, o]
+    Wi, logdet_W = _spd_inverse_logdet(W.reshape(-1, o, o))
+    Li_rows = Wi.view(M, -1, o, o) - unobs
+    c_rows = Mt.sum(1) * math.log(2 * math.pi) + logdet_W.view(M, -1)
+    ci, cj, same = _tril_pairs(o, Bm.device)
+    outer = Bm[:, ci].unsqueeze(3) * Bm[:, cj].unsqueeze(2)              # b_c b_c'^T per model
+    basis = torch.where(same, outer, outer + outer.transpose(2, 3))
+    weights = Li_rows[:, :, ci, cj]
+    return basis, weights, Li_rows, c_rows
+
+
 def _models_operands(ms):
     """The models' matrices stacked: (N, R, B, Lambda) as [M, ...]; ValueError unless they share rank, obs_dim, dtype
     and device."""
@@ -1078,6 +1329,74 @@ def log_likelihood_models(ms, ts, xs, lengths=None):
     red = _LegModelsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A, v, q.to(dt).contiguous(), plan)
     n = plan.lens.to(dt)
     return -0.5 * ((red[..., 3] - red[..., 0]) + (n * llt_det.unsqueeze(1) + red[..., 1] - red[..., 2]))
+
+
+def log_likelihood_models_observed(ms, ts, xs, lengths=None, observed=None, noise_var=None):
+    """``log_likelihood_models`` for data with missing observations and per-point noise: the [M, B] tensor whose entry
+    (k, b) is ``log_likelihood_batch(ms[k], ..., observed=, noise_var=)[b]``.  (An entry point of its own:
+    ``log_likelihood_models`` keeps its four arguments, and refuses these two keywords, as its callers and tests know it.)
+
+    ``ms``, ``ts`` / ``xs`` / ``lengths``: those of ``log_likelihood_models``.  ``observed`` and ``noise_var``: those of
+    ``log_likelihood_batch``, in the layout of xs, with the same checks.  The mask and the variances belong to the data,
+    so all models share them.  Unobserved entries of xs and noise_var are ignored whatever they hold (NaN included), a
+    row that observes nothing is marginalised out, a series that observes nothing gives 0, and a dense padded batch is
+    the mask whose tail rows are False.  Still one launch: with ``observed`` alone cgps_leg_loglik_models_obs (one
+    pattern byte per row for the batch, a table of 2^obs_dim diagonal terms per model), with ``noise_var``
+    cgps_leg_loglik_models_w (obs_dim (obs_dim + 1) / 2 weights per model and row).  Differentiable as
+    ``log_likelihood_models`` is, and in ``noise_var`` as well; the same fallbacks (d = 8, fp64 d = 6 and CPU tensors
+    take one ``log_likelihood_batch(observed=, noise_var=)`` per model) and errors; nothing read on the host when
+    ``cr.CHECK_POSITIVE_DEFINITE`` is off.  With both None the call is ``log_likelihood_models(ms, ts, xs, lengths)``."""
+    if observed is None and noise_var is None:
+        return log_likelihood_models(ms, ts, xs, lengths)
+    ms, (Nm, Rm, Bm, Lm) = _models_operands(ms)
+    dense = lengths is None
+    xs_shape = xs.shape
+    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    M, d, o, dt = len(ms), Nm.shape[1], Bm.shape[1], Nm.dtype
+    if observed is not None:
+        observed = _batch_observed(observed, xs_shape, dense)
+    if noise_var is not None:
+        noise_var = _batch_noise_var(noise_var, xs_shape, dense)
+    if xs.shape[1] != o:
+        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
+    if observed is not None:
+        observed = _observed_2d(observed, o)
+    if not lengths:
+        return torch.empty(M, 0, dtype=dt, device=ts.device)
+    if not batch_supported(ts, Nm[0]):
+        outs = []
+        for k, m in enumerate(ms):
+            try:
+                outs.append(log_likelihood_batch(m, ts, xs, lengths, observed, noise_var))
+            except cr.NotPSDError as e:
+                raise cr.NotPSDError("LEG models: model %d: %s" % (k, e)) from None
+        return torch.stack(outs)
+    if o > MAX_PATTERN_OBS:
+        raise ValueError("observation patterns are tabulated for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, o))
+    plan = _cached_batch_plan(lengths, Nm.device)
+    G = _contract(Nm, Nm.transpose(1, 2)) + (Rm - Rm.transpose(1, 2)) + _scaled_eye(d, 1e-5, dt, Nm.device)
+    LLT = _contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(o, 1e-9, dt, Nm.device)
+    xz = xs if observed is None else torch.where(observed, xs, torch.zeros((), dtype=xs.dtype, device=xs.device))
+    if noise_var is not None:
+        basis, weights, Li_rows, c = _models_noise_rows(Bm, LLT, o, dt, observed, noise_var)
+    else:
+        weights_c = 1 << torch.arange(o, device=observed.device)
+        pattern = (observed * weights_c).sum(1).to(torch.uint8)
+        idx = pattern.long()
+        Li_table, A_table, c_table = _models_pattern_tables(Bm, LLT, o, dt)
+        Li_rows, c = Li_table[:, idx], c_table[:, idx]
+    xl = _contract(xz.unsqueeze(0).unsqueeze(2), Li_rows).squeeze(2)        # x~^T Li per model and row: [M, R, obs]
+    v = _contract(xl, Bm).to(dt).contiguous()
+    q = xl[..., 0] * xz[:, 0]
+    for ch in range(1, o):
+        q = q + xl[..., ch] * xz[:, ch]
+    q = (q + c).to(dt).contiguous()                       # the observation constant rides in sum q
+    if noise_var is not None:
+        red = _LegModelsWFn.apply(ts.to(dt).contiguous(), G.contiguous(), basis.to(dt).contiguous(),
+                                  weights.to(dt).contiguous(), v, q, plan)
+    else:
+        red = _LegModelsObsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A_table.to(dt).contiguous(), v, q, pattern, plan)
+    return -0.5 * ((red[..., 3] - red[..., 0]) + (red[..., 1] - red[..., 2]))
 
 
 # ---- missing observations ------------------------------------------------------------------------------------------

@@ -324,6 +324,34 @@ int cgps_leg_loglik_models(const void* ts, const int64_t* offsets, int64_t B, in
                            const void* A, const void* v, const void* q, int d, int dtype, int64_t max_rows,
                            double* out4, int* info2, void* stream);
 
+/* cgps_leg_loglik_models for rows that do not all observe the same channels: cgps_leg_loglik_batch_obs for M models in
+ * ONE launch, grid (B, 2, M).  The mask belongs to the data: pattern[R] (DEVICE bytes, a byte >= P reads entry P - 1)
+ * describes the batch once and is read by every model; model k brings its own table, A_table[k] of A_table[M][P][d][d],
+ * 1 <= P <= 256, next to G[k], v[k] and q[k] (v and q built by the caller with the same per-row pattern).
+ *   out4[k][b][0..3], info2[k][b][0..1]
+ * are what cgps_leg_loglik_batch_obs returns in out4[b], info2[b] for (G[k], A_table[k], pattern, v[k], q[k]), bit for
+ * bit; the prior-precision system (out4[k][b][2]) reads neither table nor pattern.  Every workgroup owns its slot (no
+ * records, counters or atomics on floating-point values); a series of more than max_rows rows is skipped for every
+ * model.  M outside 1..65535, B < 0, R < 0, P outside 1..256 or a null ts, offsets, G, A_table, pattern, out4 or info2
+ * with B > 0: CGPS_ERR_ARG before anything is launched; B = 0 returns CGPS_OK; CGPS_ERR_UNSUPPORTED for d = 8 and fp64
+ * d = 6.  No workspace. */
+int cgps_leg_loglik_models_obs(const void* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const void* G,
+                               const void* A_table, int P, const unsigned char* pattern, const void* v, const void* q,
+                               int d, int dtype, int64_t max_rows, double* out4, int* info2, void* stream);
+
+/* cgps_leg_loglik_models for rows with a diagonal term of their own (per-observation noise variances):
+ * cgps_leg_loglik_batch_w for M models in ONE launch, grid (B, 2, M).  The weights are the entries of each model's own
+ * inverse noise covariance, so both operands are per model: basis[k] of basis[M][Kb][d][d], 1 <= Kb <= 64, and
+ * weights[k] of weights[M][R][Kb] (DEVICE memory, the dtype of the call).
+ *   out4[k][b][0..3], info2[k][b][0..1]
+ * are what cgps_leg_loglik_batch_w returns in out4[b], info2[b] for (G[k], basis[k], weights[k], v[k], q[k]), bit for
+ * bit; the prior-precision system reads neither basis nor weights.  Slots, max_rows, error codes: those of
+ * cgps_leg_loglik_models_obs with Kb outside 1..64 and a null basis or weights in the place of P, A_table and
+ * pattern.  No workspace. */
+int cgps_leg_loglik_models_w(const void* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const void* G,
+                             const void* basis, int Kb, const void* weights, const void* v, const void* q, int d,
+                             int dtype, int64_t max_rows, double* out4, int* info2, void* stream);
+
 /* cgps_peg_precision_seg of the same R rows under M generators G[M][d][d]: the blocks of the block-diagonal system
  * "model 0's batch, then model 1's batch, ...", Rs[M R][d][d] and Os[M R - 1][d][d].  ts[R] and cut[R-1] (NULL: one
  * series) are read by every model and not tiled in memory; rows k R .. (k+1) R - 1 use G[k] and equal what
