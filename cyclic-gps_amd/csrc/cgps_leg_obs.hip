@@ -54,76 +54,37 @@ int cgps_leg_mahal_logdet_pair_w(const void* ts, const void* G, const void* basi
 int cgps_leg_loglik_batch_obs(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* A_table, int P,
                               const unsigned char* pattern, const void* v, const void* q, int d, int dtype, int64_t max_rows,
                               double* out4, int* info2, void* stream) {
-  if (B < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !A_table || !pattern || !out4 || !info2)))
-    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_obs: null pointer or B < 0");
-  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_obs: B = %lld series, at most 2^31 - 1", (long long)B);
   if (P < 1 || P > 256) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_obs: P = %d table entries, outside 1..256", P);
-  return dispatch(dtype, d, [&](auto t, auto dc) {
-    using T = decltype(t);
-    constexpr int D = decltype(dc)::value;
-    const int rc = cgps::run_leg_batch_obs<T, D>((const T*)ts, offsets, B, (const T*)G, (const T*)A_table, P, pattern,
-                                                 (const T*)v, (const T*)q, max_rows, out4, info2, (hipStream_t)stream);
-    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch_obs: not built for this block size (d = 8, fp64 d = 6)");
-    if (B == 0) return (int)CGPS_OK;
-    return check_launch("LEG batched reduction (per-row observation pattern)");
-  });
+  return leg_rows_entry<cgps::LEG_ROWS_TABLE>("cgps_leg_loglik_batch_obs", "LEG batched reduction (per-row observation pattern)",
+                                              !A_table || !pattern, ts, offsets, B, 0, 1, G, A_table, P, pattern, v, q, d,
+                                              dtype, max_rows, out4, info2, stream);
 }
 
 int cgps_leg_loglik_batch_w(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* basis, int Kb,
                             const void* weights, const void* v, const void* q, int d, int dtype, int64_t max_rows, double* out4,
                             int* info2, void* stream) {
-  if (B < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !basis || !weights || !out4 || !info2)))
-    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_w: null pointer or B < 0");
-  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_w: B = %lld series, at most 2^31 - 1", (long long)B);
   if (Kb < 1 || Kb > 64) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch_w: Kb = %d basis blocks, outside 1..64", Kb);
-  return dispatch(dtype, d, [&](auto t, auto dc) {
-    using T = decltype(t);
-    constexpr int D = decltype(dc)::value;
-    const int rc = cgps::run_leg_batch_w<T, D>((const T*)ts, offsets, B, (const T*)G, (const T*)basis, Kb, (const T*)weights,
-                                               (const T*)v, (const T*)q, max_rows, out4, info2, (hipStream_t)stream);
-    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch_w: not built for this block size (d = 8, fp64 d = 6)");
-    if (B == 0) return (int)CGPS_OK;
-    return check_launch("LEG batched reduction (per-row weighted basis)");
-  });
+  return leg_rows_entry<cgps::LEG_ROWS_WEIGHTED>("cgps_leg_loglik_batch_w", "LEG batched reduction (per-row weighted basis)",
+                                                 !basis || !weights, ts, offsets, B, 0, 1, G, basis, Kb, weights, v, q, d,
+                                                 dtype, max_rows, out4, info2, stream);
 }
 
 int cgps_leg_loglik_models_obs(const void* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const void* G,
                                const void* A_table, int P, const unsigned char* pattern, const void* v, const void* q, int d,
                                int dtype, int64_t max_rows, double* out4, int* info2, void* stream) {
-  if (M < 1 || M > 65535) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_obs: M = %lld models, outside 1..65535", (long long)M);
-  if (B < 0 || R < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !A_table || !pattern || !out4 || !info2)))
-    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_obs: null pointer, B < 0 or R < 0");
-  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_obs: B = %lld series, at most 2^31 - 1", (long long)B);
   if (P < 1 || P > 256) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_obs: P = %d table entries, outside 1..256", P);
-  return dispatch(dtype, d, [&](auto t, auto dc) {
-    using T = decltype(t);
-    constexpr int D = decltype(dc)::value;
-    const int rc = cgps::run_leg_models_obs<T, D>((const T*)ts, offsets, B, R, M, (const T*)G, (const T*)A_table, P, pattern,
-                                                  (const T*)v, (const T*)q, max_rows, out4, info2, (hipStream_t)stream);
-    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_models_obs: not built for this block size (d = 8, fp64 d = 6)");
-    if (B == 0) return (int)CGPS_OK;
-    return check_launch("LEG batched reduction (models, per-row observation pattern)");
-  });
+  return leg_rows_entry<cgps::LEG_ROWS_MODELS_TABLE>(
+      "cgps_leg_loglik_models_obs", "LEG batched reduction (models, per-row observation pattern)", !A_table || !pattern, ts,
+      offsets, B, R, M, G, A_table, P, pattern, v, q, d, dtype, max_rows, out4, info2, stream);
 }
 
 int cgps_leg_loglik_models_w(const void* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const void* G,
                              const void* basis, int Kb, const void* weights, const void* v, const void* q, int d, int dtype,
                              int64_t max_rows, double* out4, int* info2, void* stream) {
-  if (M < 1 || M > 65535) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_w: M = %lld models, outside 1..65535", (long long)M);
-  if (B < 0 || R < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !basis || !weights || !out4 || !info2)))
-    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_w: null pointer, B < 0 or R < 0");
-  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_w: B = %lld series, at most 2^31 - 1", (long long)B);
   if (Kb < 1 || Kb > 64) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models_w: Kb = %d basis blocks, outside 1..64", Kb);
-  return dispatch(dtype, d, [&](auto t, auto dc) {
-    using T = decltype(t);
-    constexpr int D = decltype(dc)::value;
-    const int rc = cgps::run_leg_models_w<T, D>((const T*)ts, offsets, B, R, M, (const T*)G, (const T*)basis, Kb,
-                                                (const T*)weights, (const T*)v, (const T*)q, max_rows, out4, info2,
-                                                (hipStream_t)stream);
-    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_models_w: not built for this block size (d = 8, fp64 d = 6)");
-    if (B == 0) return (int)CGPS_OK;
-    return check_launch("LEG batched reduction (models, per-row weighted basis)");
-  });
+  return leg_rows_entry<cgps::LEG_ROWS_MODELS_WEIGHTED>(
+      "cgps_leg_loglik_models_w", "LEG batched reduction (models, per-row weighted basis)", !basis || !weights, ts, offsets, B,
+      R, M, G, basis, Kb, weights, v, q, d, dtype, max_rows, out4, info2, stream);
 }
 
 }  // extern "C"

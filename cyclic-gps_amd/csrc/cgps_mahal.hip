@@ -113,35 +113,15 @@ int cgps_leg_mahal_logdet_pair(const void* ts, const void* G, const void* A, con
 
 int cgps_leg_loglik_batch(const void* ts, const int64_t* offsets, int64_t B, const void* G, const void* A, const void* v,
                           const void* q, int d, int dtype, int64_t max_rows, double* out4, int* info2, void* stream) {
-  if (B < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !out4 || !info2)))
-    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch: null pointer or B < 0");
-  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_batch: B = %lld series, at most 2^31 - 1", (long long)B);
-  return dispatch(dtype, d, [&](auto t, auto dc) {
-    using T = decltype(t);
-    constexpr int D = decltype(dc)::value;
-    const int rc = cgps::run_leg_batch<T, D>((const T*)ts, offsets, B, (const T*)G, (const T*)A, (const T*)v, (const T*)q,
-                                             max_rows, out4, info2, (hipStream_t)stream);
-    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_batch: not built for this block size (d = 8, fp64 d = 6)");
-    return check_launch("LEG batched reduction");
-  });
+  return leg_rows_entry<cgps::LEG_ROWS_PLAIN>("cgps_leg_loglik_batch", "LEG batched reduction", false, ts, offsets, B, 0, 1, G, A,
+                                              0, nullptr, v, q, d, dtype, max_rows, out4, info2, stream);
 }
 
 int cgps_leg_loglik_models(const void* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const void* G, const void* A,
                            const void* v, const void* q, int d, int dtype, int64_t max_rows, double* out4, int* info2,
                            void* stream) {
-  if (M < 1 || M > 65535) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models: M = %lld models, outside 1..65535", (long long)M);
-  if (B < 0 || R < 0 || d < 1 || (B > 0 && (!ts || !offsets || !G || !out4 || !info2)))
-    return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models: null pointer, B < 0 or R < 0");
-  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_loglik_models: B = %lld series, at most 2^31 - 1", (long long)B);
-  return dispatch(dtype, d, [&](auto t, auto dc) {
-    using T = decltype(t);
-    constexpr int D = decltype(dc)::value;
-    const int rc = cgps::run_leg_models<T, D>((const T*)ts, offsets, B, R, M, (const T*)G, (const T*)A, (const T*)v,
-                                              (const T*)q, max_rows, out4, info2, (hipStream_t)stream);
-    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loglik_models: not built for this block size (d = 8, fp64 d = 6)");
-    if (B == 0) return (int)CGPS_OK;
-    return check_launch("LEG batched reduction (models)");
-  });
+  return leg_rows_entry<cgps::LEG_ROWS_MODELS>("cgps_leg_loglik_models", "LEG batched reduction (models)", false, ts, offsets, B, R,
+                                               M, G, A, 0, nullptr, v, q, d, dtype, max_rows, out4, info2, stream);
 }
 
 int cgps_mahal_logdet_batch(const void* Rs, const void* Os, const void* x, const int64_t* offsets, int64_t B, int os_packed,

@@ -1,8 +1,8 @@
 // Batched LEG log-likelihood reductions: many independent series in ONE launch (cgps_leg_loglik_batch,
 // cgps_leg_loglik_batch_obs for rows that differ in what they observe, and cgps_leg_loglik_batch_w for rows with noise
 // variances of their own).
-// Included from cgps_mahal.hip and from cgps_leg_obs.hip, after cgps_tile.h (the chunk walk, the in-LDS reduction and
-// the in-register assembly of cgps_tile_leg.h are reused as they are).
+// Included from cgps_mahal.hip and from cgps_leg_obs.hip, after cgps_host.h and cgps_tile.h (the chunk walk, the in-LDS
+// reduction and the in-register assembly of cgps_tile_leg.h are reused as they are).
 //
 // Series b is rows [offsets[b], offsets[b+1]) of the concatenated ts / v / q.  Its two systems
 //     K_b = PEG precision(ts_b, G) + blockdiag(A)        (posterior precision, right-hand side v_b)
@@ -45,9 +45,9 @@
 // weights[M][R][Kb]: the weights hold the entries of each model's own Li).  From there on the workgroup is a
 // LEG_ROWS_TABLE / LEG_ROWS_WEIGHTED workgroup; the offsets are 64-bit products of workgroup-uniform values.
 // LEG_ROWS_PLAIN reads neither argument, and every difference is an `if constexpr` on the kernel itself: each source's
-// instruction stream is the one it had before the others existed.  The TABLE and WEIGHTED kernels, with and without
-// models, are instantiated by the translation unit that calls run_leg_batch_obs / run_leg_batch_w / run_leg_models_obs /
-// run_leg_models_w (cgps_leg_obs.hip).
+// instruction stream is the one it had before the others existed.  One launcher (run_leg_rows) and one entry-point helper
+// (leg_rows_entry) serve all six; the TABLE and WEIGHTED kernels, with and without models, are instantiated by
+// cgps_leg_obs.hip, PLAIN and MODELS by cgps_mahal.hip.
 #pragma once
 
 namespace cgps {
@@ -194,154 +194,63 @@ constexpr bool leg_batch_supported() { return leg_source_supported<T, D>(); }
 template <typename T, int D>
 size_t leg_batch_lds_bytes() { return stage_lds_bytes<T, D>(leg_batch_lanes<T, D>(), LEG_BATCH_THREADS); }
 
-// -2: not built for this (d, dtype)
-template <typename T, int D>
-int run_leg_batch(const T* ts, const int64_t* offsets, int64_t B, const T* G, const T* A, const T* v, const T* q,
-                  int64_t max_rows, double* out4, int* info2, hipStream_t st) {
-  if constexpr (!leg_batch_supported<T, D>()) {
-    return -2;
-  } else {
-    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
-    const size_t lds = leg_batch_lds_bytes<T, D>();
-    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
-    std::call_once(once[dev], [lds] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    if (B == 0) return 0;
-    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets, G, A, v, q,
-                       max_rows, out4, info2, 0, (const unsigned char*)nullptr);
-    return 0;
-  }
-}
-
-// the per-row pattern form (LEG_ROWS_TABLE); entries in 1..256 and the non-null table and pattern are the caller's checks
-template <typename T, int D>
-int run_leg_batch_obs(const T* ts, const int64_t* offsets, int64_t B, const T* G, const T* table, int entries,
-                      const unsigned char* pattern, const T* v, const T* q, int64_t max_rows, double* out4, int* info2,
-                      hipStream_t st) {
+// The one launcher of the six forms.  -2: not built for this (d, dtype).  The arguments are the union of what the forms
+// take: A is the block, the table or the basis; `entries` and `pattern` are read by the TABLE and WEIGHTED sources (the
+// weights travel as bytes); M and model_rows by the models forms alone, whose grid is (B, 2, M).  The ranges of entries and
+// M and the non-null pointers are the caller's checks.
+template <typename T, int D, int ROWS>
+int run_leg_rows(const T* ts, const int64_t* offsets, int64_t B, int64_t M, int64_t model_rows, const T* G, const T* A,
+                 int entries, const unsigned char* pattern, const T* v, const T* q, int64_t max_rows, double* out4,
+                 int* info2, hipStream_t st) {
   if constexpr (!leg_batch_supported<T, D>()) {
     return -2;
   } else {
     if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
     constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
     const size_t lds = leg_batch_lds_bytes<T, D>();
-    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
+    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device (and to an instantiation)
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
     std::call_once(once[dev], [lds] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_TABLE>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, ROWS>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
-    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_TABLE>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets, G, table,
-                       v, q, max_rows, out4, info2, entries, pattern);
-    return 0;
-  }
-}
-
-// the per-row weighted-basis form (LEG_ROWS_WEIGHTED): weights [sum n_b][Kb] of the concatenated batch; Kb in 1..64 and
-// the non-null basis and weights are the caller's checks
-template <typename T, int D>
-int run_leg_batch_w(const T* ts, const int64_t* offsets, int64_t B, const T* G, const T* basis, int Kb, const T* weights,
-                    const T* v, const T* q, int64_t max_rows, double* out4, int* info2, hipStream_t st) {
-  if constexpr (!leg_batch_supported<T, D>()) {
-    return -2;
-  } else {
-    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
-    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
-    const size_t lds = leg_batch_lds_bytes<T, D>();
-    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
-    std::call_once(once[dev], [lds] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_WEIGHTED>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_WEIGHTED>), dim3((unsigned)B, 2u), dim3(NW), lds, st, ts, offsets,
-                       G, basis, v, q, max_rows, out4, info2, Kb, reinterpret_cast<const unsigned char*>(weights));
-    return 0;
-  }
-}
-
-// M models over the same batch (LEG_ROWS_MODELS): grid (B, 2, M); M in 1..65535 is the caller's check
-template <typename T, int D>
-int run_leg_models(const T* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const T* G, const T* A, const T* v,
-                   const T* q, int64_t max_rows, double* out4, int* info2, hipStream_t st) {
-  if constexpr (!leg_batch_supported<T, D>()) {
-    return -2;
-  } else {
-    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
-    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
-    const size_t lds = leg_batch_lds_bytes<T, D>();
-    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
-    std::call_once(once[dev], [lds] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS>), dim3((unsigned)B, 2u, (unsigned)M), dim3(NW), lds, st, ts,
-                       offsets, G, A, v, q, max_rows, out4, info2, 0, (const unsigned char*)nullptr, R);
-    return 0;
-  }
-}
-
-// M models over the same batch, rows that differ in what they observe (LEG_ROWS_MODELS_TABLE): table [M][P][d][d], the
-// pattern bytes once for the batch; M in 1..65535, entries in 1..256 and the non-null pointers are the caller's checks
-template <typename T, int D>
-int run_leg_models_obs(const T* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const T* G, const T* table,
-                       int entries, const unsigned char* pattern, const T* v, const T* q, int64_t max_rows, double* out4,
-                       int* info2, hipStream_t st) {
-  if constexpr (!leg_batch_supported<T, D>()) {
-    return -2;
-  } else {
-    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
-    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
-    const size_t lds = leg_batch_lds_bytes<T, D>();
-    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
-    std::call_once(once[dev], [lds] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_TABLE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_TABLE>), dim3((unsigned)B, 2u, (unsigned)M), dim3(NW), lds,
-                       st, ts, offsets, G, table, v, q, max_rows, out4, info2, entries, pattern, R);
-    return 0;
-  }
-}
-
-// M models over the same batch, rows with noise of their own (LEG_ROWS_MODELS_WEIGHTED): basis [M][Kb][d][d], weights
-// [M][R][Kb]; M in 1..65535, Kb in 1..64 and the non-null pointers are the caller's checks
-template <typename T, int D>
-int run_leg_models_w(const T* ts, const int64_t* offsets, int64_t B, int64_t R, int64_t M, const T* G, const T* basis, int Kb,
-                     const T* weights, const T* v, const T* q, int64_t max_rows, double* out4, int* info2, hipStream_t st) {
-  if constexpr (!leg_batch_supported<T, D>()) {
-    return -2;
-  } else {
-    if (B == 0) return 0;                                      // nothing to do: the runtime is not touched
-    constexpr int NT = leg_batch_lanes<T, D>(), NW = LEG_BATCH_THREADS;
-    const size_t lds = leg_batch_lds_bytes<T, D>();
-    static std::once_flag once[TILE_MAX_DEVICES];              // attributes belong to a device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= TILE_MAX_DEVICES) dev = 0;
-    std::call_once(once[dev], [lds] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_WEIGHTED>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, LEG_ROWS_MODELS_WEIGHTED>), dim3((unsigned)B, 2u, (unsigned)M), dim3(NW),
-                       lds, st, ts, offsets, G, basis, v, q, max_rows, out4, info2, Kb,
-                       reinterpret_cast<const unsigned char*>(weights), R);
+    const dim3 grid((unsigned)B, 2u, leg_rows_models(ROWS) ? (unsigned)M : 1u);
+    hipLaunchKernelGGL((leg_batch_kernel<T, D, NT, NW, ROWS>), grid, dim3(NW), lds, st, ts, offsets, G, A, v, q, max_rows, out4,
+                       info2, entries, pattern, model_rows);
     return 0;
   }
 }
 
 }  // namespace cgps
+
+namespace cgps_host {
+
+// What the six extern "C" entry points (cgps_leg_loglik_batch{,_obs,_w}, cgps_leg_loglik_models{,_obs,_w}) share: the
+// argument checks, the dispatch over dtype and d, and the launch.  `name` is the entry point's, `label` names its launch
+// in a HIP error; `missing` says that one of the pointers that this form alone requires is null (with B = 0 none is
+// looked at).  The plain forms pass entries = 0 and a null pattern, the one-model forms R = 0 and M = 1; the range of
+// P / Kb is the entry point's own check.
+template <int ROWS>
+int leg_rows_entry(const char* name, const char* label, bool missing, const void* ts, const int64_t* offsets, int64_t B,
+                   int64_t R, int64_t M, const void* G, const void* A, int entries, const void* pattern, const void* v,
+                   const void* q, int d, int dtype, int64_t max_rows, double* out4, int* info2, void* stream) {
+  constexpr bool MODELS = cgps::leg_rows_models(ROWS);
+  if (MODELS && (M < 1 || M > 65535)) return fail(CGPS_ERR_ARG, "%s: M = %lld models, outside 1..65535", name, (long long)M);
+  if (B < 0 || R < 0 || d < 1 || (B > 0 && (missing || !ts || !offsets || !G || !out4 || !info2)))
+    return fail(CGPS_ERR_ARG, MODELS ? "%s: null pointer, B < 0 or R < 0" : "%s: null pointer or B < 0", name);
+  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "%s: B = %lld series, at most 2^31 - 1", name, (long long)B);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int rc = cgps::run_leg_rows<T, D, ROWS>((const T*)ts, offsets, B, M, R, (const T*)G, (const T*)A, entries,
+                                                  (const unsigned char*)pattern, (const T*)v, (const T*)q, max_rows, out4,
+                                                  info2, (hipStream_t)stream);
+    if (rc == -2) return fail(CGPS_ERR_UNSUPPORTED, "%s: not built for this block size (d = 8, fp64 d = 6)", name);
+    if (B == 0) return (int)CGPS_OK;
+    return check_launch(label);
+  });
+}
+
+}  // namespace cgps_host

@@ -20,6 +20,7 @@ import os
 
 import torch
 
+from . import _hip
 from . import cyclic_reduction as cr
 
 
@@ -86,7 +87,6 @@ class LEGMatrices:
 def _peg_precision_hip(ts, G):
     """The same blocks from one HIP kernel (cgps_peg_precision, csrc/cgps_leg.h): one lane per block
     row, matrix exponential and the two small solves in registers.  No autograd graph."""
-    from . import _hip
     n, d = ts.shape[0], G.shape[0]
     ts = ts.to(G.dtype).contiguous()
     G = G.contiguous()
@@ -115,7 +115,6 @@ class _PegPrecisionFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gRs, gOs):
-        from . import _hip
         ts, G = ctx.saved_tensors
         n, d = ts.shape[0], G.shape[0]
         if n < 2:
@@ -181,7 +180,6 @@ def leg_mahal_and_det(ts, G, A=None, v=None):
     """(v^T J^-1 v, log|J|) of J = PEG precision(ts, G) + blockdiag(A) in ONE kernel launch that never writes the blocks
     of J to memory (cgps_leg_mahal_logdet, csrc/cgps_tile_leg.h): what `peg_precision` + `cr.mahal_and_det` compute
     (models.py:349-367).  A [d,d] or None; v [N,d] or None (zeros).  No autograd graph."""
-    from . import _hip
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
     ts = ts.to(dt).contiguous()
     G = G.contiguous()
@@ -204,18 +202,10 @@ def leg_loglik_reductions(ts, G, A, v):
     """The two reductions of a LEG log-likelihood in ONE launch (cgps_leg_mahal_logdet_pair): returns
     (v^T K^-1 v, log|K|, log|Sigma^-1|) with K = PEG precision(ts, G) + blockdiag(A), Sigma^-1 the PEG precision itself
     (models.py:349-367: decompose + det of Sigma^-1, mahal_and_det of K).  No autograd graph."""
-    from . import _hip
-    n, d, dt = ts.shape[0], G.shape[0], G.dtype
+    dt = G.dtype
     ts = ts.to(dt).contiguous()
     G, A, v = G.contiguous(), A.to(dt).contiguous(), v.to(dt).contiguous()
-    out, info = _leg_pair_raw(ts, G, A, v)
-    if cr.CHECK_POSITIVE_DEFINITE:
-        bad = info.tolist()
-        if bad[0] or bad[1]:
-            raise cr.NotPSDError("LEG system: a block near row %d is not positive definite (or a time gap has zero length)"
-                                 % ((bad[0] or bad[1]) - 1))
-    out = out.to(dt)
-    return out[0], out[1], out[3]
+    return _leg_pair_checked(ts, G, _hip.ROWS_PLAIN, A, None, v)
 
 
 # ---- many independent series at once ----------------------------------------------------------
@@ -330,43 +320,60 @@ def _cached_batch_plan(lengths, device, make=None):
     return plan
 
 
-def _leg_pair_raw(ts, G, A, v):
-    """cgps_leg_mahal_logdet_pair of one series: (out4 fp64, info2), nothing read on the host."""
-    from . import _hip
+def _leg_pair_raw(ts, G, source, term, rows, v):
+    """The pair of reductions of one series, (out4 fp64, info2), nothing read on the host.  ``source`` names where a
+    row's diagonal term comes from, as in ``_posterior_blocks_seg``: _hip.ROWS_PLAIN (term [d, d], rows None:
+    cgps_leg_mahal_logdet_pair), ROWS_TABLE (term [P, d, d], rows = pattern bytes [n]: cgps_leg_mahal_logdet_pair_obs) or
+    ROWS_WEIGHTED (term = basis [Kb, d, d], rows = weights [n, Kb]: cgps_leg_mahal_logdet_pair_w)."""
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
     ws = _hip.pair_workspace(n, d, dt, G.device)
     out = torch.empty(4, dtype=torch.float64, device=G.device)
     info = torch.zeros(2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A), _hip.ptr(v), n, d, _hip.dtype_code(dt),
-                                                     _hip.ptr(ws), ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    lib = _hip.lib()
+    fn = (lib.cgps_leg_mahal_logdet_pair, lib.cgps_leg_mahal_logdet_pair_obs, lib.cgps_leg_mahal_logdet_pair_w)[source]
+    per_row = () if source == _hip.ROWS_PLAIN else (term.shape[0], _hip.ptr(rows))
+    _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(term), *per_row, _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
+                  ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
     return out, info
+
+
+def _leg_pair_checked(ts, G, source, term, rows, v):
+    """``_leg_pair_raw`` as the one-series entry points hand it on: NotPSDError for a system that is not positive definite
+    (under ``cr.CHECK_POSITIVE_DEFINITE``), then (v^T K^-1 v, log|K|, log|Sigma^-1|) in G's dtype."""
+    out, info = _leg_pair_raw(ts, G, source, term, rows, v)
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = info.tolist()
+        if bad[0] or bad[1]:
+            raise cr.NotPSDError("LEG system: a block near row %d is not positive definite (or a time gap has zero length)"
+                                 % ((bad[0] or bad[1]) - 1))
+    out = out.to(G.dtype)
+    return out[0], out[1], out[3]
+
+
+def _check_pattern(pattern, n):
+    if pattern.dtype != torch.uint8 or pattern.shape != (n,) or not pattern.is_cuda:
+        raise ValueError("pattern must be a uint8 device tensor of shape [%d], got %s %s"
+                         % (n, pattern.dtype, tuple(pattern.shape)))
+
+
+def _check_basis_weights(basis, weights, dt):
+    if basis.dtype != dt or weights.dtype != dt:
+        raise ValueError("basis and weights must have G's dtype %s, got %s and %s" % (dt, basis.dtype, weights.dtype))
+    if not (basis.is_cuda and weights.is_cuda):
+        raise ValueError("basis and weights must be device tensors")
 
 
 def leg_loglik_reductions_obs(ts, G, A_table, pattern, v):
     """``leg_loglik_reductions`` of a series whose rows observe different channels, still ONE launch
     (cgps_leg_mahal_logdet_pair_obs): K = PEG precision(ts, G) + blockdiag(A_table[pattern[i]]).  A_table [P, d, d] with
     1 <= P <= 256, pattern uint8 [N] on the device (a byte >= P takes the last entry), v [N, d].  No autograd graph."""
-    from . import _hip
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
-    if pattern.dtype != torch.uint8 or pattern.shape != (n,) or not pattern.is_cuda:
-        raise ValueError("pattern must be a uint8 device tensor of shape [%d], got %s %s" % (n, pattern.dtype, tuple(pattern.shape)))
+    _check_pattern(pattern, n)
     if A_table.dim() != 3 or tuple(A_table.shape[1:]) != (d, d):
         raise ValueError("A_table must be [P, %d, %d], got %s" % (d, d, tuple(A_table.shape)))
     ts = ts.to(dt).contiguous()
     G, A_table, pattern, v = G.contiguous(), A_table.to(dt).contiguous(), pattern.contiguous(), v.to(dt).contiguous()
-    ws = _hip.pair_workspace(n, d, dt, G.device)
-    out = torch.empty(4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_obs(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A_table), A_table.shape[0],
-                                                         _hip.ptr(pattern), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
-                                                         ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    if cr.CHECK_POSITIVE_DEFINITE:
-        bad = info.tolist()
-        if bad[0] or bad[1]:
-            raise cr.NotPSDError("LEG system: a block near row %d is not positive definite (or a time gap has zero length)"
-                                 % ((bad[0] or bad[1]) - 1))
-    out = out.to(dt)
-    return out[0], out[1], out[3]
+    return _leg_pair_checked(ts, G, _hip.ROWS_TABLE, A_table, pattern, v)
 
 
 def leg_loglik_reductions_w(ts, G, basis, weights, v):
@@ -374,7 +381,6 @@ def leg_loglik_reductions_w(ts, G, basis, weights, v):
     (cgps_leg_mahal_logdet_pair_w): K = PEG precision(ts, G) + blockdiag(sum_k weights[i, k] basis[k]), the d x d terms
     formed in registers and never written.  basis [Kb, d, d] with 1 <= Kb <= 64 and weights [N, Kb], both device tensors
     of G's dtype (``observation_weights`` builds them); v [N, d].  No autograd graph."""
-    from . import _hip
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
     if basis.dim() != 3 or tuple(basis.shape[1:]) != (d, d) or not 1 <= basis.shape[0] <= 64:
         raise ValueError("basis must be [Kb, %d, %d] with 1 <= Kb <= 64, got %s" % (d, d, tuple(basis.shape)))
@@ -383,58 +389,50 @@ def leg_loglik_reductions_w(ts, G, basis, weights, v):
                          % (n, basis.shape[0], tuple(weights.shape)))
     if tuple(v.shape) != (n, d):
         raise ValueError("v must be [%d, %d], got %s" % (n, d, tuple(v.shape)))
-    if basis.dtype != dt or weights.dtype != dt:
-        raise ValueError("basis and weights must have G's dtype %s, got %s and %s" % (dt, basis.dtype, weights.dtype))
-    if not (basis.is_cuda and weights.is_cuda):
-        raise ValueError("basis and weights must be device tensors")
+    _check_basis_weights(basis, weights, dt)
     ts = ts.to(dt).contiguous()
     G, basis, weights, v = G.contiguous(), basis.contiguous(), weights.contiguous(), v.to(dt).contiguous()
-    ws = _hip.pair_workspace(n, d, dt, G.device)
-    out = torch.empty(4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_w(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(basis), basis.shape[0],
-                                                       _hip.ptr(weights), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
-                                                       ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    if cr.CHECK_POSITIVE_DEFINITE:
-        bad = info.tolist()
-        if bad[0] or bad[1]:
-            raise cr.NotPSDError("LEG system: a block near row %d is not positive definite (or a time gap has zero length)"
-                                 % ((bad[0] or bad[1]) - 1))
-    out = out.to(dt)
-    return out[0], out[1], out[3]
+    return _leg_pair_checked(ts, G, _hip.ROWS_WEIGHTED, basis, weights, v)
+
+
+def _leg_rows_reductions(ts, G, source, term, rows, v, q, plan):
+    """The reductions of a batch for one model (G [d, d]: [B, 4] fp64 and [B, 2] info words) or for M models (G
+    [M, d, d]: [M, B, 4] and [M, B, 2]) from one launch -- cgps_leg_loglik_batch / cgps_leg_loglik_models, with _obs or
+    _w for the other sources -- and the series longer than BATCH_MAX_ROWS through ``_leg_pair_raw`` per model and series
+    on the same stream.  (source, term, rows) as in ``_leg_pair_raw``; with M models term, v and q carry a leading model
+    axis, and so do the weights (the pattern bytes describe the batch once).  Checked, contiguous operands."""
+    models = G.dim() == 3
+    d, dt = G.shape[-1], G.dtype
+    lead, batch = ((G.shape[0],), (plan.R, G.shape[0])) if models else ((), ())
+    out = torch.empty(*lead, plan.B, 4, dtype=torch.float64, device=G.device)
+    info = torch.zeros(*lead, plan.B, 2, dtype=torch.int32, device=G.device)
+    fn = getattr(_hip.lib(), "cgps_leg_loglik_" + ("models" if models else "batch") + ("", "_obs", "_w")[source])
+    per_row = () if source == _hip.ROWS_PLAIN else (term.shape[-3], _hip.ptr(rows))
+    _hip.check(fn(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, *batch, _hip.ptr(G), _hip.ptr(term), *per_row, _hip.ptr(v),
+                  _hip.ptr(q), d, _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    if plan.long:
+        own_rows = source == _hip.ROWS_WEIGHTED               # a model's own weights; the pattern is every model's
+        if not models:                                        # one model: views with a model axis of length 1
+            G, term, v, q, out_m, info_m = (t.unsqueeze(0) for t in (G, term, v, q, out, info))
+            rows = rows.unsqueeze(0) if own_rows else rows
+        else:
+            out_m, info_m = out, info
+        for b in plan.long:
+            s, e = plan.starts[b], plan.starts[b + 1]
+            for k in range(G.shape[0]):
+                rows_k = None if rows is None else rows[k, s:e] if own_rows else rows[s:e]
+                o4, i2 = _leg_pair_raw(ts[s:e], G[k], source, term[k], rows_k, v[k, s:e])
+                out_m[k, b, :3] = o4[[0, 1, 3]]
+                out_m[k, b, 3] = q[k, s:e].to(torch.float64).sum()
+                info_m[k, b] = i2
+    return out, info
 
 
 def leg_loglik_batch_reductions(ts, G, A, v, q, plan):
     """The per-series reductions of a batch, no autograd graph: [B, 4] fp64 rows (v^T K^-1 v, log|K|, log|Sigma^-1|,
     sum q) and [B, 2] info words (cgps_leg_loglik_batch; series longer than BATCH_MAX_ROWS through
     cgps_leg_mahal_logdet_pair on the same stream).  ts, A, v, q in G's dtype, contiguous."""
-    from . import _hip
-    d, dt = G.shape[0], G.dtype
-    out = torch.empty(plan.B, 4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(plan.B, 2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_loglik_batch(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, _hip.ptr(G), _hip.ptr(A),
-                                                _hip.ptr(v), _hip.ptr(q), d, _hip.dtype_code(dt), BATCH_MAX_ROWS,
-                                                _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    for b in plan.long:
-        s, e = plan.starts[b], plan.starts[b + 1]
-        o4, i2 = _leg_pair_raw(ts[s:e], G, A, v[s:e])
-        out[b, :3] = o4[[0, 1, 3]]
-        out[b, 3] = q[s:e].to(torch.float64).sum()
-        info[b] = i2
-    return out, info
-
-
-def _leg_pair_obs_raw(ts, G, A_table, pattern, v):
-    """cgps_leg_mahal_logdet_pair_obs of one series: (out4 fp64, info2), nothing read on the host."""
-    from . import _hip
-    n, d, dt = ts.shape[0], G.shape[0], G.dtype
-    ws = _hip.pair_workspace(n, d, dt, G.device)
-    out = torch.empty(4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_obs(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(A_table), A_table.shape[0],
-                                                         _hip.ptr(pattern), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
-                                                         ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    return out, info
+    return _leg_rows_reductions(ts, G, _hip.ROWS_PLAIN, A, None, v, q, plan)
 
 
 def leg_loglik_batch_reductions_obs(ts, G, A_table, pattern, v, q, plan):
@@ -443,40 +441,11 @@ def leg_loglik_batch_reductions_obs(ts, G, A_table, pattern, v, q, plan):
     A_table [P, d, d] with 1 <= P <= 256, pattern uint8 [R] on the device, one byte per row of the concatenated batch
     (a byte >= P takes the last entry); series longer than BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_obs with
     their slice of the pattern.  ts, A_table, v, q in G's dtype, contiguous.  No autograd graph."""
-    from . import _hip
-    d, dt = G.shape[0], G.dtype
-    if pattern.dtype != torch.uint8 or pattern.shape != (plan.R,) or not pattern.is_cuda:
-        raise ValueError("pattern must be a uint8 device tensor of shape [%d], got %s %s"
-                         % (plan.R, pattern.dtype, tuple(pattern.shape)))
+    d = G.shape[0]
+    _check_pattern(pattern, plan.R)
     if A_table.dim() != 3 or tuple(A_table.shape[1:]) != (d, d):
         raise ValueError("A_table must be [P, %d, %d], got %s" % (d, d, tuple(A_table.shape)))
-    pattern = pattern.contiguous()
-    out = torch.empty(plan.B, 4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(plan.B, 2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_loglik_batch_obs(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, _hip.ptr(G),
-                                                    _hip.ptr(A_table), A_table.shape[0], _hip.ptr(pattern), _hip.ptr(v),
-                                                    _hip.ptr(q), d, _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out),
-                                                    _hip.ptr(info), _hip.stream_ptr()))
-    for b in plan.long:
-        s, e = plan.starts[b], plan.starts[b + 1]
-        o4, i2 = _leg_pair_obs_raw(ts[s:e], G, A_table, pattern[s:e], v[s:e])
-        out[b, :3] = o4[[0, 1, 3]]
-        out[b, 3] = q[s:e].to(torch.float64).sum()
-        info[b] = i2
-    return out, info
-
-
-def _leg_pair_w_raw(ts, G, basis, weights, v):
-    """cgps_leg_mahal_logdet_pair_w of one series: (out4 fp64, info2), nothing read on the host."""
-    from . import _hip
-    n, d, dt = ts.shape[0], G.shape[0], G.dtype
-    ws = _hip.pair_workspace(n, d, dt, G.device)
-    out = torch.empty(4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_mahal_logdet_pair_w(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(basis), basis.shape[0],
-                                                       _hip.ptr(weights), _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
-                                                       ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    return out, info
+    return _leg_rows_reductions(ts, G, _hip.ROWS_TABLE, A_table, pattern.contiguous(), v, q, plan)
 
 
 def leg_loglik_batch_reductions_w(ts, G, basis, weights, v, q, plan):
@@ -486,31 +455,14 @@ def leg_loglik_batch_reductions_w(ts, G, basis, weights, v, q, plan):
     [R, Kb], one row per row of the concatenated batch, both device tensors of G's dtype (``observation_weights`` builds
     them); series longer than BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_w with their slice of the weights.
     ts, v, q in G's dtype, contiguous.  No autograd graph."""
-    from . import _hip
     d, dt = G.shape[0], G.dtype
     if basis.dim() != 3 or tuple(basis.shape[1:]) != (d, d) or not 1 <= basis.shape[0] <= 64:
         raise ValueError("basis must be [Kb, %d, %d] with 1 <= Kb <= 64, got %s" % (d, d, tuple(basis.shape)))
     if tuple(weights.shape) != (plan.R, basis.shape[0]):
         raise ValueError("weights must be [%d, %d] (one row of Kb weights per row of the batch), got %s"
                          % (plan.R, basis.shape[0], tuple(weights.shape)))
-    if basis.dtype != dt or weights.dtype != dt:
-        raise ValueError("basis and weights must have G's dtype %s, got %s and %s" % (dt, basis.dtype, weights.dtype))
-    if not (basis.is_cuda and weights.is_cuda):
-        raise ValueError("basis and weights must be device tensors")
-    basis, weights = basis.contiguous(), weights.contiguous()
-    out = torch.empty(plan.B, 4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(plan.B, 2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_loglik_batch_w(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, _hip.ptr(G), _hip.ptr(basis),
-                                                  basis.shape[0], _hip.ptr(weights), _hip.ptr(v), _hip.ptr(q), d,
-                                                  _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out), _hip.ptr(info),
-                                                  _hip.stream_ptr()))
-    for b in plan.long:
-        s, e = plan.starts[b], plan.starts[b + 1]
-        o4, i2 = _leg_pair_w_raw(ts[s:e], G, basis, weights[s:e], v[s:e])
-        out[b, :3] = o4[[0, 1, 3]]
-        out[b, 3] = q[s:e].to(torch.float64).sum()
-        info[b] = i2
-    return out, info
+    _check_basis_weights(basis, weights, dt)
+    return _leg_rows_reductions(ts, G, _hip.ROWS_WEIGHTED, basis.contiguous(), weights.contiguous(), v, q, plan)
 
 
 def _raise_batch_not_pd(info):
@@ -525,7 +477,6 @@ def _raise_batch_not_pd(info):
 
 def _peg_precision_seg(ts, G, cut):
     """Blocks of the block-diagonal PEG precision of concatenated series (cgps_peg_precision_seg).  No autograd graph."""
-    from . import _hip
     n, d = ts.shape[0], G.shape[0]
     Rs = torch.empty(n, d, d, dtype=G.dtype, device=G.device)
     Os = torch.empty(max(n - 1, 0), d, d, dtype=G.dtype, device=G.device)
@@ -537,7 +488,6 @@ def _peg_precision_seg(ts, G, cut):
 
 def _peg_precision_adjoint_seg(ts, G, cut, gRs, gOs, want_ts):
     """(d loss / d G, d loss / d ts or None) through cgps_peg_precision_adjoint_seg."""
-    from . import _hip
     n, d = ts.shape[0], G.shape[0]
     if n < 2:
         return torch.zeros_like(G), (torch.zeros_like(ts) if want_ts else None)
@@ -553,109 +503,6 @@ def _peg_precision_adjoint_seg(ts, G, cut, gRs, gOs, want_ts):
     return part.sum(0), gts
 
 
-class _LegBatchFn(torch.autograd.Function):
-    """Forward: the batched reductions (one launch).  Backward: the concatenated system of all series, which is
-    block-diagonal (zero coupling between series): series-aware assembly, decompose_solve + inverse_blocks of K and
-    of Sigma^-1, block gradients weighted per row by the series' upstream gradients, series-aware adjoint."""
-
-    @staticmethod
-    def forward(ctx, ts, G, A, v, q, plan):
-        ctx.plan = plan
-        ctx.save_for_backward(ts, G, A, v)
-        out, info = leg_loglik_batch_reductions(ts.detach(), G.detach(), A.detach(), v.detach(), q.detach(), plan)
-        if cr.CHECK_POSITIVE_DEFINITE:
-            _raise_batch_not_pd(info)
-        return out.to(G.dtype)
-
-    @staticmethod
-    def backward(ctx, gout):
-        ts, G, A, v = ctx.saved_tensors
-        plan = ctx.plan
-        need_ts, need_G, need_A, need_v, need_q = ctx.needs_input_grad[:5]
-        gts = gG = gA = gv = gq = None
-        gout = gout.to(G.dtype)
-        if need_q:
-            gq = plan.per_row(gout[:, 3])
-        if need_ts or need_G or need_A or need_v:
-            Rs, Os = _peg_precision_seg(ts, G, plan.cut)
-            gm, gl = plan.per_row(gout[:, 0]), plan.per_row(gout[:, 1])
-            dec, w = cr.decompose_solve(Rs + A, Os, v)
-            if need_v:
-                gv = 2 * gm.unsqueeze(-1) * w
-            if need_ts or need_G or need_A:
-                Sd, So = cr.inverse_blocks(dec)
-                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
-                if need_A:
-                    gA = gR.sum(0)
-                if need_ts or need_G:
-                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
-                    if plan.R > 1:           # (one row: its block is I whatever G and ts are)
-                        gs = plan.per_row(gout[:, 2])
-                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
-                        gR = gR + gs.view(-1, 1, 1) * Sd0
-                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
-                    gG, gts = _peg_precision_adjoint_seg(ts, G, plan.cut, gR, gO, need_ts)
-                    if not need_G:
-                        gG = None
-        return gts, gG, gA, gv, gq, None
-
-
-class _LegBatchObsFn(torch.autograd.Function):
-    """``_LegBatchFn`` with a per-row observation pattern.  Forward: cgps_leg_loglik_batch_obs (one launch).  Backward:
-    the same concatenated, decoupled system with Rs + A_table[idx] as K's diagonal; the gradient of A_table is the
-    per-pattern sum of the rows' block gradients, taken as a matrix product with the one-hot matrix of the pattern
-    (no scatter: ``index_add_`` on the GPU adds with atomics, in no fixed order)."""
-
-    @staticmethod
-    def forward(ctx, ts, G, A_table, v, q, pattern, plan):
-        ctx.plan = plan
-        ctx.save_for_backward(ts, G, A_table, v, pattern)
-        out, info = leg_loglik_batch_reductions_obs(ts.detach(), G.detach(), A_table.detach(), pattern, v.detach(),
-                                                    q.detach(), plan)
-        if cr.CHECK_POSITIVE_DEFINITE:
-            _raise_batch_not_pd(info)
-        return out.to(G.dtype)
-
-    @staticmethod
-    def backward(ctx, gout):
-        ts, G, A_table, v, pattern = ctx.saved_tensors
-        plan = ctx.plan
-        need_ts, need_G, need_A, need_v, need_q = ctx.needs_input_grad[:5]
-        gts = gG = gA = gv = gq = None
-        gout = gout.to(G.dtype)
-        if need_q:
-            gq = plan.per_row(gout[:, 3])
-        if need_ts or need_G or need_A or need_v:
-            P, d = A_table.shape[0], G.shape[0]
-            idx = pattern.long().clamp(max=P - 1)                # the kernel's clamp
-            Rs, Os = _peg_precision_seg(ts, G, plan.cut)
-            gm, gl = plan.per_row(gout[:, 0]), plan.per_row(gout[:, 1])
-            dec, w = cr.decompose_solve(Rs + A_table[idx], Os, v)
-            if need_v:
-                gv = 2 * gm.unsqueeze(-1) * w
-            if need_ts or need_G or need_A:
-                Sd, So = cr.inverse_blocks(dec)
-                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
-                if need_A:
-                    codes = torch.arange(P, device=idx.device).unsqueeze(1)
-                    step = max(1024, (1 << 24) // P)             # rows per product: the one-hot matrix stays small
-                    gA = torch.zeros(P, d * d, dtype=G.dtype, device=G.device)
-                    for s in range(0, plan.R, step):             # (one product unless P * R > 2^24)
-                        gA = gA + (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype) @ gR[s:s + step].reshape(-1, d * d)
-                    gA = gA.reshape(P, d, d)
-                if need_ts or need_G:
-                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
-                    if plan.R > 1:           # (one row: its block is I whatever G and ts are)
-                        gs = plan.per_row(gout[:, 2])
-                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
-                        gR = gR + gs.view(-1, 1, 1) * Sd0
-                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
-                    gG, gts = _peg_precision_adjoint_seg(ts, G, plan.cut, gR, gO, need_ts)
-                    if not need_G:
-                        gG = None
-        return gts, gG, gA, gv, gq, None, None
-
-
 def _rows_product(a, b, rows=4096):
     """a^T b of two tall matrices a [R, p] and b [R, q] (contiguous) as batched products over chunks of ``rows`` rows,
     added up by one reduction in a fixed order, plus the product of the remainder.  One ``a.T @ b`` with R in the
@@ -669,44 +516,87 @@ def _rows_product(a, b, rows=4096):
     return out
 
 
-class _LegBatchWFn(torch.autograd.Function):
-    """``_LegBatchFn`` with a weighted basis per row.  Forward: cgps_leg_loglik_batch_w (one launch).  Backward: the same
-    concatenated, decoupled system with Rs + sum_k weights[i, k] basis[k] as K's diagonal; the rows' block gradients gR_i
-    go to the basis as sum_i weights[i, k] gR_i and to the weights as <gR_i, basis[k]>, both plain matrix products."""
+def _batch_diag(source, G, term, rows, need_term, need_rows):
+    """What a batch's backward has to know about where the rows' diagonal terms come from, as a pair of functions:
+    diag_term() is what K's diagonal adds to Rs, and diag_grads(gR) sends the rows' block gradients gR [R, d, d] back as
+    (d loss / d term, d loss / d rows).  (source, term, rows) as in ``_leg_pair_raw``."""
+    d = G.shape[0]
+    if source == _hip.ROWS_PLAIN:                                # the one block A, broadcast over the rows
+        return (lambda: term), (lambda gR: (gR.sum(0), None))
+    if source == _hip.ROWS_TABLE:
+        # row i adds A_table[idx[i]]; the gradient of A_table is the per-pattern sum of the rows' block gradients, taken as
+        # a matrix product with the one-hot matrix of the pattern (no scatter: ``index_add_`` on the GPU adds with atomics,
+        # in no fixed order)
+        P = term.shape[0]
+        idx = rows.long().clamp(max=P - 1)                       # the kernel's clamp
+
+        def table_grads(gR):
+            codes = torch.arange(P, device=idx.device).unsqueeze(1)
+            step = max(1024, (1 << 24) // P)                     # rows per product: the one-hot matrix stays small
+            gA = torch.zeros(P, d * d, dtype=G.dtype, device=G.device)
+            for s in range(0, gR.shape[0], step):                # (one product unless P * R > 2^24)
+                gA = gA + (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype) @ gR[s:s + step].reshape(-1, d * d)
+            return gA.reshape(P, d, d), None
+        return (lambda: term[idx]), table_grads
+    # row i adds sum_k weights[i, k] basis[k]; gR_i goes to the basis as sum_i weights[i, k] gR_i and to the weights as
+    # <gR_i, basis[k]>, both plain matrix products
+    Kb = term.shape[0]
+
+    def weighted_grads(gR):
+        gb = _rows_product(rows, gR.reshape(-1, d * d)).reshape(Kb, d, d) if need_term else None
+        gw = gR.reshape(-1, d * d) @ term.reshape(Kb, d * d).T if need_rows else None
+        return gb, gw
+    return (lambda: torch.einsum("nk,kij->nij", rows, term)), weighted_grads
+
+
+def _reductions_by_source(forms, ts, G, source, term, rows, v, q, plan):
+    """The public reductions of this source (``forms``: the plain, _obs and _w function), so that an autograd forward
+    checks its operands exactly as a direct call does."""
+    if rows is None:
+        return forms[source](ts, G, term, v, q, plan)
+    return forms[source](ts, G, term, rows, v, q, plan)
+
+
+class _LegBatchFn(torch.autograd.Function):
+    """``apply(ts, G, term, rows, v, q, source, plan)``, with (source, term, rows) as in ``_leg_pair_raw``.  Forward: the
+    batched reductions of that source (one launch).  Backward: the concatenated system of all series, which is
+    block-diagonal (zero coupling between series): series-aware assembly, decompose_solve + inverse_blocks of K (its
+    diagonal Rs + the source's term, ``_batch_diag``) and of Sigma^-1, block gradients weighted per row by the series'
+    upstream gradients, series-aware adjoint.  ``rows`` gets a gradient for the weighted source alone."""
 
     @staticmethod
-    def forward(ctx, ts, G, basis, weights, v, q, plan):
-        ctx.plan = plan
-        ctx.save_for_backward(ts, G, basis, weights, v)
-        out, info = leg_loglik_batch_reductions_w(ts.detach(), G.detach(), basis.detach(), weights.detach(), v.detach(),
-                                                  q.detach(), plan)
+    def forward(ctx, ts, G, term, rows, v, q, source, plan):
+        ctx.plan, ctx.source = plan, source
+        ctx.save_for_backward(ts, G, term, rows, v)
+        forms = (leg_loglik_batch_reductions, leg_loglik_batch_reductions_obs, leg_loglik_batch_reductions_w)
+        out, info = _reductions_by_source(forms, ts.detach(), G.detach(), source, term.detach(),
+                                          None if rows is None else rows.detach(), v.detach(), q.detach(), plan)
         if cr.CHECK_POSITIVE_DEFINITE:
             _raise_batch_not_pd(info)
         return out.to(G.dtype)
 
     @staticmethod
     def backward(ctx, gout):
-        ts, G, basis, weights, v = ctx.saved_tensors
+        ts, G, term, rows, v = ctx.saved_tensors
         plan = ctx.plan
-        need_ts, need_G, need_b, need_w, need_v, need_q = ctx.needs_input_grad[:6]
-        gts = gG = gb = gw = gv = gq = None
+        need_ts, need_G, need_term, need_rows, need_v, need_q = ctx.needs_input_grad[:6]
+        need_diag = need_term or need_rows
+        gts = gG = gterm = grows = gv = gq = None
         gout = gout.to(G.dtype)
         if need_q:
             gq = plan.per_row(gout[:, 3])
-        if need_ts or need_G or need_b or need_w or need_v:
-            Kb, d = basis.shape[0], G.shape[0]
+        if need_ts or need_G or need_diag or need_v:
+            diag_term, diag_grads = _batch_diag(ctx.source, G, term, rows, need_term, need_rows)
             Rs, Os = _peg_precision_seg(ts, G, plan.cut)
             gm, gl = plan.per_row(gout[:, 0]), plan.per_row(gout[:, 1])
-            dec, w = cr.decompose_solve(Rs + torch.einsum("nk,kij->nij", weights, basis), Os, v)
+            dec, w = cr.decompose_solve(Rs + diag_term(), Os, v)
             if need_v:
                 gv = 2 * gm.unsqueeze(-1) * w
-            if need_ts or need_G or need_b or need_w:
+            if need_ts or need_G or need_diag:
                 Sd, So = cr.inverse_blocks(dec)
                 gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
-                if need_b:
-                    gb = _rows_product(weights, gR.reshape(-1, d * d)).reshape(Kb, d, d)
-                if need_w:
-                    gw = gR.reshape(-1, d * d) @ basis.reshape(Kb, d * d).T
+                if need_diag:
+                    gterm, grows = diag_grads(gR)
                 if need_ts or need_G:
                     gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
                     if plan.R > 1:           # (one row: its block is I whatever G and ts are)
@@ -717,7 +607,7 @@ class _LegBatchWFn(torch.autograd.Function):
                     gG, gts = _peg_precision_adjoint_seg(ts, G, plan.cut, gR, gO, need_ts)
                     if not need_G:
                         gG = None
-        return gts, gG, gb, gw, gv, gq, None
+        return gts, gG, gterm, grows, gv, gq, None, None
 
 
 def _log_likelihood_per_series(m, ts, xs, lengths, observed=None, noise_var=None):
@@ -733,38 +623,27 @@ def _log_likelihood_per_series(m, ts, xs, lengths, observed=None, noise_var=None
     return torch.stack(outs)
 
 
-def _batch_observed(observed, xs_shape, dense):
-    """``observed`` in the layout of the batch's xs, flattened to the rows of the concatenated batch ([R, obs] or [R]);
-    raises ValueError before anything is launched."""
-    if not isinstance(observed, torch.Tensor) or observed.dtype != torch.bool:
-        raise ValueError("observed must be a bool tensor")
-    xs_shape = tuple(xs_shape)
-    if dense:
-        if tuple(observed.shape) not in (xs_shape, xs_shape[:2]):
-            raise ValueError("dense layout wants observed[B, n, obs_dim] or observed[B, n] like xs %s, got %s"
-                             % (xs_shape, tuple(observed.shape)))
-        return observed.reshape((xs_shape[0] * xs_shape[1],) + tuple(observed.shape[2:]))
-    if tuple(observed.shape) not in (xs_shape, xs_shape[:1]):
-        raise ValueError("ragged layout wants observed[sum(lengths), obs_dim] or observed[sum(lengths)] like xs %s, got %s"
-                         % (xs_shape, tuple(observed.shape)))
-    return observed
+_OBSERVED = ("observed", "a bool tensor", lambda dtype: dtype == torch.bool)
+_NOISE_VAR = ("noise_var", "a floating-point tensor", lambda dtype: dtype.is_floating_point)
 
 
-def _batch_noise_var(noise_var, xs_shape, dense):
-    """``noise_var`` in the layout of the batch's xs, flattened to the rows of the concatenated batch ([R, obs] or [R]);
-    raises ValueError before anything is launched."""
-    if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
-        raise ValueError("noise_var must be a floating-point tensor")
+def _batch_like_xs(t, spec, xs_shape, dense):
+    """``observed`` or ``noise_var`` (``spec``: its name, what it must be, and the test of its dtype) in the layout of the
+    batch's xs, flattened to the rows of the concatenated batch ([R, obs] or [R]); raises ValueError before anything is
+    launched."""
+    name, what, dtype_ok = spec
+    if not isinstance(t, torch.Tensor) or not dtype_ok(t.dtype):
+        raise ValueError("%s must be %s" % (name, what))
     xs_shape = tuple(xs_shape)
     if dense:
-        if tuple(noise_var.shape) not in (xs_shape, xs_shape[:2]):
-            raise ValueError("dense layout wants noise_var[B, n, obs_dim] or noise_var[B, n] like xs %s, got %s"
-                             % (xs_shape, tuple(noise_var.shape)))
-        return noise_var.reshape((xs_shape[0] * xs_shape[1],) + tuple(noise_var.shape[2:]))
-    if tuple(noise_var.shape) not in (xs_shape, xs_shape[:1]):
-        raise ValueError("ragged layout wants noise_var[sum(lengths), obs_dim] or noise_var[sum(lengths)] like xs %s, got %s"
-                         % (xs_shape, tuple(noise_var.shape)))
-    return noise_var
+        if tuple(t.shape) not in (xs_shape, xs_shape[:2]):
+            raise ValueError("dense layout wants %s[B, n, obs_dim] or %s[B, n] like xs %s, got %s"
+                             % (name, name, xs_shape, tuple(t.shape)))
+        return t.reshape((xs_shape[0] * xs_shape[1],) + tuple(t.shape[2:]))
+    if tuple(t.shape) not in (xs_shape, xs_shape[:1]):
+        raise ValueError("ragged layout wants %s[sum(lengths), obs_dim] or %s[sum(lengths)] like xs %s, got %s"
+                         % (name, name, xs_shape, tuple(t.shape)))
+    return t
 
 
 def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None):
@@ -803,9 +682,9 @@ def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None)
     ts, xs, lengths = _batch_layout(ts, xs, lengths)
     if observed is not None or noise_var is not None:
         if observed is not None:
-            observed = _batch_observed(observed, xs_shape, dense)
+            observed = _batch_like_xs(observed, _OBSERVED, xs_shape, dense)
         if noise_var is not None:
-            noise_var = _batch_noise_var(noise_var, xs_shape, dense)
+            noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
         if xs.shape[1] != m.B.shape[0]:
             raise ValueError("xs must have %d channels, got %s" % (m.B.shape[0], tuple(xs_shape)))
         if observed is not None:
@@ -821,27 +700,27 @@ def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None)
         basis, weights, c_rows, xl, xz = _noise_operands(m, ts, xs, observed, noise_var)
         v = (xl @ m.B).to(dt).contiguous()
         q = ((xl * xz).sum(-1) + c_rows).to(dt).contiguous()             # the observation constant rides in sum q
-        red = _LegBatchWFn.apply(ts.to(dt).contiguous(), G.contiguous(), basis.to(dt).contiguous(),
-                                 weights.to(dt).contiguous(), v, q, plan)
-        return -0.5 * ((red[:, 3] - red[:, 0]) + (red[:, 1] - red[:, 2]))
-    if observed is not None:
+        source, term, rows = _hip.ROWS_WEIGHTED, basis.to(dt).contiguous(), weights.to(dt).contiguous()
+    elif observed is not None:
         plan = _cached_batch_plan(lengths, G.device)
         pattern, idx, A_table, c_table, xl, xz = _observed_operands(m, ts, xs, observed)
         v = (xl @ m.B).to(dt).contiguous()
         q = ((xl * xz).sum(-1) + c_table[idx]).to(dt).contiguous()       # the observation constant rides in sum q
-        red = _LegBatchObsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A_table.to(dt).contiguous(), v, q, pattern, plan)
-        return -0.5 * ((red[:, 3] - red[:, 0]) + (red[:, 1] - red[:, 2]))
-    plan = _BatchPlan(lengths, G.device)
-    LLT = m.LLT
-    Li = m.inv_of(LLT)
-    xl = xs @ Li
-    v = (xl @ m.B).to(dt).contiguous()
-    q = (xl * xs).sum(-1).to(dt).contiguous()
-    A = (m.B.T @ Li @ m.B).to(dt).contiguous()
-    red = _LegBatchFn.apply(ts.to(dt).contiguous(), G.contiguous(), A, v, q, plan)
-    llt_det = torch.log(2 * math.pi * LLT[0, 0]) if LLT.shape[0] == 1 else torch.logdet(2 * math.pi * LLT)
-    n = plan.lens.to(dt)
-    return -0.5 * ((red[:, 3] - red[:, 0]) + (n * llt_det + red[:, 1] - red[:, 2]))
+        source, term, rows = _hip.ROWS_TABLE, A_table.to(dt).contiguous(), pattern
+    else:
+        plan = _BatchPlan(lengths, G.device)
+        LLT = m.LLT
+        Li = m.inv_of(LLT)
+        xl = xs @ Li
+        v = (xl @ m.B).to(dt).contiguous()
+        q = (xl * xs).sum(-1).to(dt).contiguous()
+        source, term, rows = _hip.ROWS_PLAIN, (m.B.T @ Li @ m.B).to(dt).contiguous(), None
+    red = _LegBatchFn.apply(ts.to(dt).contiguous(), G.contiguous(), term, rows, v, q, source, plan)
+    if source == _hip.ROWS_PLAIN:
+        llt_det = torch.log(2 * math.pi * LLT[0, 0]) if LLT.shape[0] == 1 else torch.logdet(2 * math.pi * LLT)
+        n = plan.lens.to(dt)
+        return -0.5 * ((red[:, 3] - red[:, 0]) + (n * llt_det + red[:, 1] - red[:, 2]))
+    return -0.5 * ((red[:, 3] - red[:, 0]) + (red[:, 1] - red[:, 2]))
 
 
 # ---- many models over one batch ------------------------------------------------------------------------------------
@@ -886,7 +765,6 @@ def _spd_inverse_logdet(S):
 def _peg_precision_models(ts, G, cut):
     """Blocks of the PEG precision of the same rows under G[m, d, d], model after model (cgps_peg_precision_models):
     Rs [m R, d, d], Os [m R - 1, d, d] with zero blocks between two models.  No autograd graph."""
-    from . import _hip
     m, d, R = G.shape[0], G.shape[1], ts.shape[0]
     Rs = torch.empty(m * R, d, d, dtype=G.dtype, device=G.device)
     Os = torch.empty(m * R - 1, d, d, dtype=G.dtype, device=G.device)
@@ -899,7 +777,6 @@ def _peg_precision_models(ts, G, cut):
 def _peg_precision_adjoint_models(ts, G, cut, gRs, gOs, want_ts):
     """(d loss / d G[m, d, d], d loss / d ts [R] or None) through cgps_peg_precision_adjoint_models: every model's
     partial sums added per model, the models' gradients in ts added over the models."""
-    from . import _hip
     m, d, R = G.shape[0], G.shape[1], ts.shape[0]
     if R < 2:
         return torch.zeros_like(G), (torch.zeros_like(ts) if want_ts else None)
@@ -915,26 +792,53 @@ def _peg_precision_adjoint_models(ts, G, cut, gRs, gOs, want_ts):
     return part.sum(1), gts
 
 
+def _check_models_rhs(v, q, M, R, d):
+    if tuple(v.shape) != (M, R, d) or tuple(q.shape) != (M, R):
+        raise ValueError("v must be [%d, %d, %d] and q [%d, %d], got %s and %s"
+                         % (M, R, d, M, R, tuple(v.shape), tuple(q.shape)))
+
+
 def leg_loglik_models_reductions(ts, G, A, v, q, plan):
     """``leg_loglik_batch_reductions`` for M models over the same batch, no autograd graph: [M, B, 4] fp64 and [M, B, 2]
     info words from one launch (cgps_leg_loglik_models; series longer than BATCH_MAX_ROWS through
     cgps_leg_mahal_logdet_pair per model and series on the same stream).  ts [R]; G, A [M, d, d]; v [M, R, d];
     q [M, R]; all in G's dtype, contiguous."""
-    from . import _hip
+    return _leg_rows_reductions(ts, G, _hip.ROWS_PLAIN, A, None, v, q, plan)
+
+
+def leg_loglik_models_reductions_obs(ts, G, A_table, pattern, v, q, plan):
+    """``leg_loglik_models_reductions`` of series whose rows observe different channels, still ONE launch
+    (cgps_leg_loglik_models_obs): the mask belongs to the data, so ``pattern`` (uint8 [R] on the device, a byte >= P takes
+    the last entry) is shared by the models and every model brings a table of its own, A_table [M, P, d, d] with
+    1 <= P <= 256.  ts [R]; G [M, d, d]; v [M, R, d]; q [M, R]; all in G's dtype, contiguous.  Series longer than
+    BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_obs per model and series.  No autograd graph."""
     M, d, dt = G.shape[0], G.shape[1], G.dtype
-    out = torch.empty(M, plan.B, 4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(M, plan.B, 2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_loglik_models(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, plan.R, M, _hip.ptr(G),
-                                                 _hip.ptr(A), _hip.ptr(v), _hip.ptr(q), d, _hip.dtype_code(dt),
-                                                 BATCH_MAX_ROWS, _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    for b in plan.long:
-        for k in range(M):
-            s, e = plan.starts[b], plan.starts[b + 1]
-            o4, i2 = _leg_pair_raw(ts[s:e], G[k], A[k], v[k, s:e])
-            out[k, b, :3] = o4[[0, 1, 3]]
-            out[k, b, 3] = q[k, s:e].to(torch.float64).sum()
-            info[k, b] = i2
-    return out, info
+    _check_pattern(pattern, plan.R)
+    if A_table.dim() != 4 or A_table.shape[0] != M or tuple(A_table.shape[2:]) != (d, d) or not 1 <= A_table.shape[1] <= 256:
+        raise ValueError("A_table must be [%d, P, %d, %d] with 1 <= P <= 256, got %s" % (M, d, d, tuple(A_table.shape)))
+    _check_models_rhs(v, q, M, plan.R, d)
+    if A_table.dtype != dt or not A_table.is_cuda:
+        raise ValueError("A_table must be a device tensor of G's dtype %s, got %s" % (dt, A_table.dtype))
+    return _leg_rows_reductions(ts, G, _hip.ROWS_TABLE, A_table.contiguous(), pattern.contiguous(), v, q, plan)
+
+
+def leg_loglik_models_reductions_w(ts, G, basis, weights, v, q, plan):
+    """``leg_loglik_models_reductions`` of series whose rows each add a term of their own, still ONE launch
+    (cgps_leg_loglik_models_w): K of (model k, series b) = PEG precision(ts_b, G[k]) + blockdiag(sum_j weights[k, i, j]
+    basis[k, j]) over the series' rows.  basis [M, Kb, d, d] with 1 <= Kb <= 64 and weights [M, R, Kb] (the entries of
+    each model's own inverse noise covariance), device tensors of G's dtype.  ts [R]; G [M, d, d]; v [M, R, d]; q [M, R];
+    contiguous.  Series longer than BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_w per model and series.  No
+    autograd graph."""
+    M, d, dt = G.shape[0], G.shape[1], G.dtype
+    if basis.dim() != 4 or basis.shape[0] != M or tuple(basis.shape[2:]) != (d, d) or not 1 <= basis.shape[1] <= 64:
+        raise ValueError("basis must be [%d, Kb, %d, %d] with 1 <= Kb <= 64, got %s" % (M, d, d, tuple(basis.shape)))
+    Kb = basis.shape[1]
+    if tuple(weights.shape) != (M, plan.R, Kb):
+        raise ValueError("weights must be [%d, %d, %d] (Kb weights per model and row of the batch), got %s"
+                         % (M, plan.R, Kb, tuple(weights.shape)))
+    _check_models_rhs(v, q, M, plan.R, d)
+    _check_basis_weights(basis, weights, dt)
+    return _leg_rows_reductions(ts, G, _hip.ROWS_WEIGHTED, basis.contiguous(), weights.contiguous(), v, q, plan)
 
 
 def _raise_models_not_pd(info):
@@ -945,228 +849,6 @@ def _raise_models_not_pd(info):
         code = int(bad[k, b, 0]) or int(bad[k, b, 1])
         raise cr.NotPSDError("LEG models: model %d, series %d: a block near its row %d is not positive definite "
                              "(or a time gap has zero length)" % (k, b, code - 1))
-
-
-class _LegModelsFn(torch.autograd.Function):
-    """Forward: the reductions of every (model, series) in one launch.  Backward: ``_LegBatchFn``'s on the concatenated
-    system of all models' batches, block-diagonal over models and series, in chunks of whole models."""
-
-    @staticmethod
-    def forward(ctx, ts, G, A, v, q, plan):
-        ctx.plan = plan
-        ctx.save_for_backward(ts, G, A, v)
-        out, info = leg_loglik_models_reductions(ts.detach(), G.detach(), A.detach(), v.detach(), q.detach(), plan)
-        if cr.CHECK_POSITIVE_DEFINITE:
-            _raise_models_not_pd(info)
-        return out.to(G.dtype)
-
-    @staticmethod
-    def backward(ctx, gout):
-        ts, G, A, v = ctx.saved_tensors
-        plan = ctx.plan
-        need_ts, need_G, need_A, need_v, need_q = ctx.needs_input_grad[:5]
-        M, d, R = G.shape[0], G.shape[1], plan.R
-        gout = gout.to(G.dtype)
-
-        def rows(g, c):                                   # column c of a chunk's [m, B, 4], spread over the m R rows
-            return g[:, :, c].repeat_interleave(plan.lens, dim=1, output_size=R).reshape(-1)
-
-        gq = rows(gout, 3).view(M, R) if need_q else None
-        gts = torch.zeros_like(ts) if need_ts else None
-        gG = torch.empty_like(G) if need_G else None
-        gA = torch.empty_like(A) if need_A else None
-        gv = torch.empty_like(v) if need_v else None
-        if need_ts or need_G or need_A or need_v:
-            per = max(1, MODELS_BACKWARD_MAX_ROWS // R)
-            for k0 in range(0, M, per):
-                k1 = min(M, k0 + per)
-                m, g, Gc = k1 - k0, gout[k0:k1], G[k0:k1]
-                Rs, Os = _peg_precision_models(ts, Gc, plan.cut)
-                gm, gl = rows(g, 0), rows(g, 1)
-                dec, w = cr.decompose_solve((Rs.view(m, R, d, d) + A[k0:k1].unsqueeze(1)).view(m * R, d, d), Os,
-                                            v[k0:k1].reshape(m * R, d))
-                if need_v:
-                    gv[k0:k1] = (2 * gm.unsqueeze(-1) * w).view(m, R, d)
-                if need_ts or need_G or need_A:
-                    Sd, So = cr.inverse_blocks(dec)
-                    gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
-                    if need_A:
-                        gA[k0:k1] = gR.view(m, R, d, d).sum(1)
-                    if need_ts or need_G:
-                        # (the entries of gO between two models hold whatever the zero coupling gives: never read)
-                        gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
-                        if m * R > 1:        # (one row: its block is I whatever G and ts are)
-                            gs = rows(g, 2)
-                            Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
-                            gR = gR + gs.view(-1, 1, 1) * Sd0
-                            gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
-                        gGc, gtsc = _peg_precision_adjoint_models(ts, Gc, plan.cut, gR, gO, need_ts)
-                        if need_G:
-                            gG[k0:k1] = gGc
-                        if need_ts:
-                            gts = gts + gtsc                      # chunks in ascending order
-        return gts, gG, gA, gv, gq, None
-
-
-def leg_loglik_models_reductions_obs(ts, G, A_table, pattern, v, q, plan):
-    """``leg_loglik_models_reductions`` of series whose rows observe different channels, still ONE launch
-    (cgps_leg_loglik_models_obs): the mask belongs to the data, so ``pattern`` (uint8 [R] on the device, a byte >= P takes
-    the last entry) is shared by the models and every model brings a table of its own, A_table [M, P, d, d] with
-    1 <= P <= 256.  ts [R]; G [M, d, d]; v [M, R, d]; q [M, R]; all in G's dtype, contiguous.  Series longer than
-    BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_obs per model and series.  No autograd graph."""
-    from . import _hip
-    M, d, dt = G.shape[0], G.shape[1], G.dtype
-    if pattern.dtype != torch.uint8 or pattern.shape != (plan.R,) or not pattern.is_cuda:
-        raise ValueError("pattern must be a uint8 device tensor of shape [%d], got %s %s"
-                         % (plan.R, pattern.dtype, tuple(pattern.shape)))
-    if A_table.dim() != 4 or A_table.shape[0] != M or tuple(A_table.shape[2:]) != (d, d) or not 1 <= A_table.shape[1] <= 256:
-        raise ValueError("A_table must be [%d, P, %d, %d] with 1 <= P <= 256, got %s" % (M, d, d, tuple(A_table.shape)))
-    if tuple(v.shape) != (M, plan.R, d) or tuple(q.shape) != (M, plan.R):
-        raise ValueError("v must be [%d, %d, %d] and q [%d, %d], got %s and %s"
-                         % (M, plan.R, d, M, plan.R, tuple(v.shape), tuple(q.shape)))
-    if A_table.dtype != dt or not A_table.is_cuda:
-        raise ValueError("A_table must be a device tensor of G's dtype %s, got %s" % (dt, A_table.dtype))
-    pattern, A_table = pattern.contiguous(), A_table.contiguous()
-    out = torch.empty(M, plan.B, 4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(M, plan.B, 2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_loglik_models_obs(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, plan.R, M, _hip.ptr(G),
-                                                     _hip.ptr(A_table), A_table.shape[1], _hip.ptr(pattern), _hip.ptr(v),
-                                                     _hip.ptr(q), d, _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out),
-                                                     _hip.ptr(info), _hip.stream_ptr()))
-    for b in plan.long:
-        for k in range(M):
-            s, e = plan.starts[b], plan.starts[b + 1]
-            o4, i2 = _leg_pair_obs_raw(ts[s:e], G[k], A_table[k], pattern[s:e], v[k, s:e])
-            out[k, b, :3] = o4[[0, 1, 3]]
-            out[k, b, 3] = q[k, s:e].to(torch.float64).sum()
-            info[k, b] = i2
-    return out, info
-
-
-def leg_loglik_models_reductions_w(ts, G, basis, weights, v, q, plan):
-    """``leg_loglik_models_reductions`` of series whose rows each add a term of their own, still ONE launch
-    (cgps_leg_loglik_models_w): K of (model k, series b) = PEG precision(ts_b, G[k]) + blockdiag(sum_j weights[k, i, j]
-    basis[k, j]) over the series' rows.  basis [M, Kb, d, d] with 1 <= Kb <= 64 and weights [M, R, Kb] (the entries of
-    each model's own inverse noise covariance), device tensors of G's dtype.  ts [R]; G [M, d, d]; v [M, R, d]; q [M, R];
-    contiguous.  Series longer than BATCH_MAX_ROWS through cgps_leg_mahal_logdet_pair_w per model and series.  No
-    autograd graph."""
-    from . import _hip
-    M, d, dt = G.shape[0], G.shape[1], G.dtype
-    if basis.dim() != 4 or basis.shape[0] != M or tuple(basis.shape[2:]) != (d, d) or not 1 <= basis.shape[1] <= 64:
-        raise ValueError("basis must be [%d, Kb, %d, %d] with 1 <= Kb <= 64, got %s" % (M, d, d, tuple(basis.shape)))
-    Kb = basis.shape[1]
-    if tuple(weights.shape) != (M, plan.R, Kb):
-        raise ValueError("weights must be [%d, %d, %d] (Kb weights per model and row of the batch), got %s"
-                         % (M, plan.R, Kb, tuple(weights.shape)))
-    if tuple(v.shape) != (M, plan.R, d) or tuple(q.shape) != (M, plan.R):
-        raise ValueError("v must be [%d, %d, %d] and q [%d, %d], got %s and %s"
-                         % (M, plan.R, d, M, plan.R, tuple(v.shape), tuple(q.shape)))
-    if basis.dtype != dt or weights.dtype != dt:
-        raise ValueError("basis and weights must have G's dtype %s, got %s and %s" % (dt, basis.dtype, weights.dtype))
-    if not (basis.is_cuda and weights.is_cuda):
-        raise ValueError("basis and weights must be device tensors")
-    basis, weights = basis.contiguous(), weights.contiguous()
-    out = torch.empty(M, plan.B, 4, dtype=torch.float64, device=G.device)
-    info = torch.zeros(M, plan.B, 2, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_loglik_models_w(_hip.ptr(ts), _hip.ptr(plan.offsets), plan.B, plan.R, M, _hip.ptr(G),
-                                                   _hip.ptr(basis), Kb, _hip.ptr(weights), _hip.ptr(v), _hip.ptr(q), d,
-                                                   _hip.dtype_code(dt), BATCH_MAX_ROWS, _hip.ptr(out), _hip.ptr(info),
-                                                   _hip.stream_ptr()))
-    for b in plan.long:
-        for k in range(M):
-            s, e = plan.starts[b], plan.starts[b + 1]
-            o4, i2 = _leg_pair_w_raw(ts[s:e], G[k], basis[k], weights[k, s:e], v[k, s:e])
-            out[k, b, :3] = o4[[0, 1, 3]]
-            out[k, b, 3] = q[k, s:e].to(torch.float64).sum()
-            info[k, b] = i2
-    return out, info
-
-
-def _models_backward(ctx_needs, plan, ts, G, v, gout, diag_term, diag_grads):
-    """The chunked backward that ``_LegModelsObsFn`` and ``_LegModelsWFn`` share: ``_LegModelsFn``'s, with K's diagonal
-    Rs + diag_term(k0, k1) [m, R, d, d] and the rows' block gradients gR [m, R, d, d] of the chunk handed to
-    diag_grads(k0, k1, gR).  Returns (gts, gG, gv, gq)."""
-    need_ts, need_G, need_diag, need_v, need_q = ctx_needs
-    M, d, R = G.shape[0], G.shape[1], plan.R
-    gout = gout.to(G.dtype)
-
-    def rows(g, c):                                   # column c of a chunk's [m, B, 4], spread over the m R rows
-        return g[:, :, c].repeat_interleave(plan.lens, dim=1, output_size=R).reshape(-1)
-
-    gq = rows(gout, 3).view(M, R) if need_q else None
-    gts = torch.zeros_like(ts) if need_ts else None
-    gG = torch.empty_like(G) if need_G else None
-    gv = torch.empty_like(v) if need_v else None
-    if need_ts or need_G or need_diag or need_v:
-        per = max(1, MODELS_BACKWARD_MAX_ROWS // R)
-        for k0 in range(0, M, per):
-            k1 = min(M, k0 + per)
-            m, g, Gc = k1 - k0, gout[k0:k1], G[k0:k1]
-            Rs, Os = _peg_precision_models(ts, Gc, plan.cut)
-            gm, gl = rows(g, 0), rows(g, 1)
-            dec, w = cr.decompose_solve((Rs.view(m, R, d, d) + diag_term(k0, k1)).view(m * R, d, d), Os,
-                                        v[k0:k1].reshape(m * R, d))
-            if need_v:
-                gv[k0:k1] = (2 * gm.unsqueeze(-1) * w).view(m, R, d)
-            if need_ts or need_G or need_diag:
-                Sd, So = cr.inverse_blocks(dec)
-                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
-                if need_diag:
-                    diag_grads(k0, k1, gR.view(m, R, d, d))
-                if need_ts or need_G:
-                    # (the entries of gO between two models hold whatever the zero coupling gives: never read)
-                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
-                    if m * R > 1:        # (one row: its block is I whatever G and ts are)
-                        gs = rows(g, 2)
-                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
-                        gR = gR + gs.view(-1, 1, 1) * Sd0
-                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
-                    gGc, gtsc = _peg_precision_adjoint_models(ts, Gc, plan.cut, gR, gO, need_ts)
-                    if need_G:
-                        gG[k0:k1] = gGc
-                    if need_ts:
-                        gts = gts + gtsc                      # chunks in ascending order
-    return gts, gG, gv, gq
-
-
-class _LegModelsObsFn(torch.autograd.Function):
-    """``_LegModelsFn`` with a per-row observation pattern shared by the models and a table per model.  Forward:
-    cgps_leg_loglik_models_obs (one launch).  Backward: the same chunks of whole models with Rs + A_table[k][idx] as K's
-    diagonal; the gradient of A_table[k] is the per-pattern sum of model k's row gradients, a product with the one-hot
-    matrix of the pattern that all models share (no scatter: ``index_add_`` adds with atomics, in no fixed order)."""
-
-    @staticmethod
-    def forward(ctx, ts, G, A_table, v, q, pattern, plan):
-        ctx.plan = plan
-        ctx.save_for_backward(ts, G, A_table, v, pattern)
-        out, info = leg_loglik_models_reductions_obs(ts.detach(), G.detach(), A_table.detach(), pattern, v.detach(),
-                                                     q.detach(), plan)
-        if cr.CHECK_POSITIVE_DEFINITE:
-            _raise_models_not_pd(info)
-        return out.to(G.dtype)
-
-    @staticmethod
-    def backward(ctx, gout):
-        ts, G, A_table, v, pattern = ctx.saved_tensors
-        plan = ctx.plan
-        P, d, R = A_table.shape[1], G.shape[1], plan.R
-        idx = pattern.long().clamp(max=P - 1)                    # the kernel's clamp
-        gA = torch.empty_like(A_table) if ctx.needs_input_grad[2] else None
-        codes = torch.arange(P, device=idx.device).unsqueeze(1)
-        step = max(1024, (1 << 24) // P)                         # rows per product: the one-hot matrix stays small
-
-        def diag_term(k0, k1):
-            return A_table[k0:k1][:, idx]
-
-        def diag_grads(k0, k1, gR):
-            acc = torch.zeros(k1 - k0, P, d * d, dtype=G.dtype, device=G.device)
-            for s in range(0, R, step):                          # (one product unless P * R > 2^24)
-                onehot = (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype)
-                acc = acc + torch.matmul(onehot, gR[:, s:s + step].reshape(k1 - k0, -1, d * d))
-            gA[k0:k1] = acc.view(k1 - k0, P, d, d)
-
-        gts, gG, gv, gq = _models_backward(ctx.needs_input_grad[:5], plan, ts, G, v, gout, diag_term, diag_grads)
-        return gts, gG, gA, gv, gq, None, None
 
 
 def _rows_product_models(a, b, rows=4096):
@@ -1181,44 +863,114 @@ def _rows_product_models(a, b, rows=4096):
     return out
 
 
-class _LegModelsWFn(torch.autograd.Function):
-    """``_LegModelsFn`` with a weighted basis per row and model.  Forward: cgps_leg_loglik_models_w (one launch).
-    Backward: the same chunks of whole models with Rs + sum_j weights[k, i, j] basis[k, j] as K's diagonal; model k's
-    block gradients gR_i go to its basis as sum_i weights[k, i, j] gR_i and to its weights as <gR_i, basis[k, j]>, both
-    plain matrix products per model."""
+def _models_diag(source, G, term, rows, R, need_term, need_rows):
+    """``_batch_diag`` for the chunked backward over whole models: diag_term(k0, k1) is what K's diagonal adds to
+    Rs [m, R, d, d] for the models k0 .. k1 - 1, diag_grads(k0, k1, gR) files the chunk's block gradients gR [m, R, d, d]
+    into the third and fourth value, d loss / d term and d loss / d rows (None where not wanted)."""
+    d = G.shape[1]
+    gterm = torch.empty_like(term) if need_term else None
+    if source == _hip.ROWS_PLAIN:                                # model k's one block, broadcast over its rows
+        def plain_grads(k0, k1, gR):
+            gterm[k0:k1] = gR.sum(1)
+        return (lambda k0, k1: term[k0:k1].unsqueeze(1)), plain_grads, gterm, None
+    if source == _hip.ROWS_TABLE:
+        # row i of model k adds A_table[k][idx[i]]; the gradient of A_table[k] is the per-pattern sum of model k's row
+        # gradients, a product with the one-hot matrix of the pattern that all models share (no scatter: ``index_add_``
+        # adds with atomics, in no fixed order)
+        P = term.shape[1]
+        idx = rows.long().clamp(max=P - 1)                       # the kernel's clamp
+        codes = torch.arange(P, device=idx.device).unsqueeze(1)
+        step = max(1024, (1 << 24) // P)                         # rows per product: the one-hot matrix stays small
+
+        def table_grads(k0, k1, gR):
+            acc = torch.zeros(k1 - k0, P, d * d, dtype=G.dtype, device=G.device)
+            for s in range(0, R, step):                          # (one product unless P * R > 2^24)
+                onehot = (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype)
+                acc = acc + torch.matmul(onehot, gR[:, s:s + step].reshape(k1 - k0, -1, d * d))
+            gterm[k0:k1] = acc.view(k1 - k0, P, d, d)
+        return (lambda k0, k1: term[k0:k1][:, idx]), table_grads, gterm, None
+    # row i of model k adds sum_j weights[k, i, j] basis[k, j]; model k's gR_i go to its basis as sum_i weights[k, i, j]
+    # gR_i and to its weights as <gR_i, basis[k, j]>, both plain matrix products per model
+    Kb = term.shape[1]
+    grows = torch.empty_like(rows) if need_rows else None
+
+    def weighted_grads(k0, k1, gR):
+        gR = gR.reshape(k1 - k0, R, d * d)
+        if need_term:
+            gterm[k0:k1] = _rows_product_models(rows[k0:k1], gR).view(k1 - k0, Kb, d, d)
+        if need_rows:
+            grows[k0:k1] = torch.bmm(gR, term[k0:k1].reshape(k1 - k0, Kb, d * d).transpose(1, 2))
+    return (lambda k0, k1: torch.einsum("mrk,mkij->mrij", rows[k0:k1], term[k0:k1])), weighted_grads, gterm, grows
+
+
+def _models_backward(needs, plan, source, ts, G, term, rows, v, gout):
+    """``_LegBatchFn``'s backward on the concatenated system of all models' batches, block-diagonal over models and series,
+    in chunks of whole models (MODELS_BACKWARD_MAX_ROWS).  K's diagonal is Rs + the source's term (``_models_diag``).
+    Returns (gts, gG, gterm, grows, gv, gq) for ``needs``, the six needs_input_grad of those inputs."""
+    need_ts, need_G, need_term, need_rows, need_v, need_q = needs
+    need_diag = need_term or need_rows
+    M, d, R = G.shape[0], G.shape[1], plan.R
+    gout = gout.to(G.dtype)
+    diag_term, diag_grads, gterm, grows = _models_diag(source, G, term, rows, R, need_term, need_rows)
+
+    def spread(g, c):                                 # column c of a chunk's [m, B, 4], spread over the m R rows
+        return g[:, :, c].repeat_interleave(plan.lens, dim=1, output_size=R).reshape(-1)
+
+    gq = spread(gout, 3).view(M, R) if need_q else None
+    gts = torch.zeros_like(ts) if need_ts else None
+    gG = torch.empty_like(G) if need_G else None
+    gv = torch.empty_like(v) if need_v else None
+    if need_ts or need_G or need_diag or need_v:
+        per = max(1, MODELS_BACKWARD_MAX_ROWS // R)
+        for k0 in range(0, M, per):
+            k1 = min(M, k0 + per)
+            m, g, Gc = k1 - k0, gout[k0:k1], G[k0:k1]
+            Rs, Os = _peg_precision_models(ts, Gc, plan.cut)
+            gm, gl = spread(g, 0), spread(g, 1)
+            dec, w = cr.decompose_solve((Rs.view(m, R, d, d) + diag_term(k0, k1)).view(m * R, d, d), Os,
+                                        v[k0:k1].reshape(m * R, d))
+            if need_v:
+                gv[k0:k1] = (2 * gm.unsqueeze(-1) * w).view(m, R, d)
+            if need_ts or need_G or need_diag:
+                Sd, So = cr.inverse_blocks(dec)
+                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
+                if need_diag:
+                    diag_grads(k0, k1, gR.view(m, R, d, d))
+                if need_ts or need_G:
+                    # (the entries of gO between two models hold whatever the zero coupling gives: never read)
+                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
+                    if m * R > 1:        # (one row: its block is I whatever G and ts are)
+                        gs = spread(g, 2)
+                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
+                        gR = gR + gs.view(-1, 1, 1) * Sd0
+                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
+                    gGc, gtsc = _peg_precision_adjoint_models(ts, Gc, plan.cut, gR, gO, need_ts)
+                    if need_G:
+                        gG[k0:k1] = gGc
+                    if need_ts:
+                        gts = gts + gtsc                      # chunks in ascending order
+    return gts, gG, gterm, grows, gv, gq
+
+
+class _LegModelsFn(torch.autograd.Function):
+    """``_LegBatchFn`` for M models over one batch, called the same way with a leading model axis on G, term, v, q and on
+    the weights.  Forward: the reductions of every (model, series) in one launch.  Backward: ``_models_backward``."""
 
     @staticmethod
-    def forward(ctx, ts, G, basis, weights, v, q, plan):
-        ctx.plan = plan
-        ctx.save_for_backward(ts, G, basis, weights, v)
-        out, info = leg_loglik_models_reductions_w(ts.detach(), G.detach(), basis.detach(), weights.detach(), v.detach(),
-                                                   q.detach(), plan)
+    def forward(ctx, ts, G, term, rows, v, q, source, plan):
+        ctx.plan, ctx.source = plan, source
+        ctx.save_for_backward(ts, G, term, rows, v)
+        forms = (leg_loglik_models_reductions, leg_loglik_models_reductions_obs, leg_loglik_models_reductions_w)
+        out, info = _reductions_by_source(forms, ts.detach(), G.detach(), source, term.detach(),
+                                          None if rows is None else rows.detach(), v.detach(), q.detach(), plan)
         if cr.CHECK_POSITIVE_DEFINITE:
             _raise_models_not_pd(info)
         return out.to(G.dtype)
 
     @staticmethod
     def backward(ctx, gout):
-        ts, G, basis, weights, v = ctx.saved_tensors
-        plan = ctx.plan
-        need_ts, need_G, need_b, need_w, need_v, need_q = ctx.needs_input_grad[:6]
-        Kb, d, R = basis.shape[1], G.shape[1], plan.R
-        gb = torch.empty_like(basis) if need_b else None
-        gw = torch.empty_like(weights) if need_w else None
-
-        def diag_term(k0, k1):
-            return torch.einsum("mrk,mkij->mrij", weights[k0:k1], basis[k0:k1])
-
-        def diag_grads(k0, k1, gR):
-            gR = gR.reshape(k1 - k0, R, d * d)
-            if need_b:
-                gb[k0:k1] = _rows_product_models(weights[k0:k1], gR).view(k1 - k0, Kb, d, d)
-            if need_w:
-                gw[k0:k1] = torch.bmm(gR, basis[k0:k1].reshape(k1 - k0, Kb, d * d).transpose(1, 2))
-
-        gts, gG, gv, gq = _models_backward((need_ts, need_G, need_b or need_w, need_v, need_q), plan, ts, G, v, gout,
-                                           diag_term, diag_grads)
-        return gts, gG, gb, gw, gv, gq, None
+        ts, G, term, rows, v = ctx.saved_tensors
+        return _models_backward(ctx.needs_input_grad[:6], ctx.plan, ctx.source, ts, G, term, rows, v, gout) + (None, None)
 
 
 def _models_pattern_tables(Bm, LLT, o, dt):
@@ -1285,6 +1037,43 @@ def _models_operands(ms):
     return ms, tuple(torch.stack([getattr(m, name) for m in ms]) for name in ("N", "R", "B", "Lambda"))
 
 
+def _models_setup(ms, ts, xs, lengths, observed=None, noise_var=None):
+    """What ``log_likelihood_models`` and ``log_likelihood_models_observed`` do first: the stacked matrices, the layout and
+    its checks, and the two ways a call ends early -- an empty batch, and the block sizes and devices without a batched
+    kernel, which take one ``log_likelihood_batch`` per model.  Returns (result, None) then, and otherwise
+    (None, (ts, xs, observed, noise_var, plan, Bm, G, LLT)) with xs [R, obs], observed [R, obs] or None, noise_var [R, obs],
+    [R] or None, and the models' G [M, d, d] and LLT [M, obs, obs]."""
+    ms, (Nm, Rm, Bm, Lm) = _models_operands(ms)
+    dense = lengths is None
+    xs_shape = xs.shape
+    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    M, d, o, dt = len(ms), Nm.shape[1], Bm.shape[1], Nm.dtype
+    if observed is not None:
+        observed = _batch_like_xs(observed, _OBSERVED, xs_shape, dense)
+    if noise_var is not None:
+        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
+    if xs.shape[1] != o:
+        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
+    if observed is not None:
+        observed = _observed_2d(observed, o)
+    if not lengths:
+        return torch.empty(M, 0, dtype=dt, device=ts.device), None
+    if not batch_supported(ts, Nm[0]):
+        outs = []
+        for k, m in enumerate(ms):
+            try:
+                outs.append(log_likelihood_batch(m, ts, xs, lengths, observed, noise_var))
+            except cr.NotPSDError as e:
+                raise cr.NotPSDError("LEG models: model %d: %s" % (k, e)) from None
+        return torch.stack(outs), None
+    if (observed is not None or noise_var is not None) and o > MAX_PATTERN_OBS:
+        raise ValueError("observation patterns are tabulated for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, o))
+    plan = _cached_batch_plan(lengths, Nm.device)
+    G = _contract(Nm, Nm.transpose(1, 2)) + (Rm - Rm.transpose(1, 2)) + _scaled_eye(d, 1e-5, dt, Nm.device)
+    LLT = _contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(o, 1e-9, dt, Nm.device)
+    return None, (ts, xs, observed, noise_var, plan, Bm, G, LLT)
+
+
 def log_likelihood_models(ms, ts, xs, lengths=None):
     """log p(xs_b | ts_b) of M LEG models for the same B series, as an [M, B] tensor of the models' dtype: entry (k, b)
     is ``log_likelihood(ms[k], series b)``.  What several starts of a fit, a population of chains, a grid of length
@@ -1300,24 +1089,11 @@ def log_likelihood_models(ms, ts, xs, lengths=None):
     d = 6 and CPU tensors take one ``log_likelihood_batch`` per model.  With ``cr.CHECK_POSITIVE_DEFINITE`` a system
     that is not positive definite raises ``NotPSDError`` naming its model and series; without it that slot is NaN and
     no other slot is affected."""
-    ms, (Nm, Rm, Bm, Lm) = _models_operands(ms)
-    ts, xs, lengths = _batch_layout(ts, xs, lengths)
-    M, d, o, dt = len(ms), Nm.shape[1], Bm.shape[1], Nm.dtype
-    if xs.shape[1] != o:
-        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
-    if not lengths:
-        return torch.empty(M, 0, dtype=dt, device=ts.device)
-    if not batch_supported(ts, Nm[0]):
-        outs = []
-        for k, m in enumerate(ms):
-            try:
-                outs.append(log_likelihood_batch(m, ts, xs, lengths))
-            except cr.NotPSDError as e:
-                raise cr.NotPSDError("LEG models: model %d: %s" % (k, e)) from None
-        return torch.stack(outs)
-    plan = _cached_batch_plan(lengths, Nm.device)
-    G = _contract(Nm, Nm.transpose(1, 2)) + (Rm - Rm.transpose(1, 2)) + _scaled_eye(d, 1e-5, dt, Nm.device)
-    LLT = _contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(o, 1e-9, dt, Nm.device)
+    out, operands = _models_setup(ms, ts, xs, lengths)
+    if operands is None:
+        return out
+    ts, xs, _, _, plan, Bm, G, LLT = operands
+    o, dt = Bm.shape[1], Bm.dtype
     Li, llt_det = _spd_inverse_logdet(LLT)
     llt_det = llt_det + o * math.log(2 * math.pi)
     xl = _contract(xs.unsqueeze(0), Li)                   # [M, R, obs]
@@ -1326,7 +1102,7 @@ def log_likelihood_models(ms, ts, xs, lengths=None):
     for c in range(1, o):
         q = q + xl[..., c] * xs[:, c]
     A = _contract(_contract(Bm.transpose(1, 2), Li), Bm).to(dt).contiguous()
-    red = _LegModelsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A, v, q.to(dt).contiguous(), plan)
+    red = _LegModelsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A, None, v, q.to(dt).contiguous(), _hip.ROWS_PLAIN, plan)
     n = plan.lens.to(dt)
     return -0.5 * ((red[..., 3] - red[..., 0]) + (n * llt_det.unsqueeze(1) + red[..., 1] - red[..., 2]))
 
@@ -1348,34 +1124,11 @@ def log_likelihood_models_observed(ms, ts, xs, lengths=None, observed=None, nois
     ``cr.CHECK_POSITIVE_DEFINITE`` is off.  With both None the call is ``log_likelihood_models(ms, ts, xs, lengths)``."""
     if observed is None and noise_var is None:
         return log_likelihood_models(ms, ts, xs, lengths)
-    ms, (Nm, Rm, Bm, Lm) = _models_operands(ms)
-    dense = lengths is None
-    xs_shape = xs.shape
-    ts, xs, lengths = _batch_layout(ts, xs, lengths)
-    M, d, o, dt = len(ms), Nm.shape[1], Bm.shape[1], Nm.dtype
-    if observed is not None:
-        observed = _batch_observed(observed, xs_shape, dense)
-    if noise_var is not None:
-        noise_var = _batch_noise_var(noise_var, xs_shape, dense)
-    if xs.shape[1] != o:
-        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
-    if observed is not None:
-        observed = _observed_2d(observed, o)
-    if not lengths:
-        return torch.empty(M, 0, dtype=dt, device=ts.device)
-    if not batch_supported(ts, Nm[0]):
-        outs = []
-        for k, m in enumerate(ms):
-            try:
-                outs.append(log_likelihood_batch(m, ts, xs, lengths, observed, noise_var))
-            except cr.NotPSDError as e:
-                raise cr.NotPSDError("LEG models: model %d: %s" % (k, e)) from None
-        return torch.stack(outs)
-    if o > MAX_PATTERN_OBS:
-        raise ValueError("observation patterns are tabulated for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, o))
-    plan = _cached_batch_plan(lengths, Nm.device)
-    G = _contract(Nm, Nm.transpose(1, 2)) + (Rm - Rm.transpose(1, 2)) + _scaled_eye(d, 1e-5, dt, Nm.device)
-    LLT = _contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(o, 1e-9, dt, Nm.device)
+    out, operands = _models_setup(ms, ts, xs, lengths, observed, noise_var)
+    if operands is None:
+        return out
+    ts, xs, observed, noise_var, plan, Bm, G, LLT = operands
+    o, dt = Bm.shape[1], Bm.dtype
     xz = xs if observed is None else torch.where(observed, xs, torch.zeros((), dtype=xs.dtype, device=xs.device))
     if noise_var is not None:
         basis, weights, Li_rows, c = _models_noise_rows(Bm, LLT, o, dt, observed, noise_var)
@@ -1392,10 +1145,10 @@ def log_likelihood_models_observed(ms, ts, xs, lengths=None, observed=None, nois
         q = q + xl[..., ch] * xz[:, ch]
     q = (q + c).to(dt).contiguous()                       # the observation constant rides in sum q
     if noise_var is not None:
-        red = _LegModelsWFn.apply(ts.to(dt).contiguous(), G.contiguous(), basis.to(dt).contiguous(),
-                                  weights.to(dt).contiguous(), v, q, plan)
+        source, term, rows = _hip.ROWS_WEIGHTED, basis.to(dt).contiguous(), weights.to(dt).contiguous()
     else:
-        red = _LegModelsObsFn.apply(ts.to(dt).contiguous(), G.contiguous(), A_table.to(dt).contiguous(), v, q, pattern, plan)
+        source, term, rows = _hip.ROWS_TABLE, A_table.to(dt).contiguous(), pattern
+    red = _LegModelsFn.apply(ts.to(dt).contiguous(), G.contiguous(), term, rows, v, q, source, plan)
     return -0.5 * ((red[..., 3] - red[..., 0]) + (red[..., 1] - red[..., 2]))
 
 
@@ -1814,9 +1567,9 @@ def _batch_posterior_args(m, ts, xs, lengths, observed, noise_var):
     if xs.shape[1] != m.B.shape[0]:
         raise ValueError("xs must have %d channels, got %s" % (m.B.shape[0], xs_shape))
     if observed is not None:
-        observed = _observed_2d(_batch_observed(observed, xs_shape, dense), xs.shape[1])
+        observed = _observed_2d(_batch_like_xs(observed, _OBSERVED, xs_shape, dense), xs.shape[1])
     if noise_var is not None:
-        noise_var = _batch_noise_var(noise_var, xs_shape, dense)
+        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
         if noise_var.dim() == 2 and noise_var.shape[1] != xs.shape[1]:
             raise ValueError("noise_var must have %d channels, got %s" % (xs.shape[1], tuple(noise_var.shape)))
     return ts, xs, lengths, observed, noise_var, dense, (xs_shape[:2] if dense else None)
@@ -1839,7 +1592,6 @@ def _posterior_blocks_seg(ts, G, cut, source, term, rows=None):
     (cgps_leg_posterior_blocks_seg): K's diagonal blocks are written once.  source: _hip.ROWS_PLAIN (term [d, d]),
     ROWS_TABLE (term [entries, d, d], rows = pattern bytes [n]) or ROWS_WEIGHTED (term = basis [Kb, d, d], rows = weights
     [n, Kb]); cut may be None (one series).  Contiguous operands of G's dtype.  No autograd graph."""
-    from . import _hip
     n, d = ts.shape[0], G.shape[0]
     entries = 0 if source == _hip.ROWS_PLAIN else term.shape[0]
     K_Rs = torch.empty(n, d, d, dtype=G.dtype, device=G.device)
@@ -1857,7 +1609,6 @@ def _posterior_system_batch(m, ts, xs, observed, noise_var, plan):
     added inside it (cgps_leg_posterior_blocks_seg).  CGPS_LEG_BLOCKS_COMPOSED=1 takes the composition it replaces
     instead -- cgps_peg_precision_seg, then the gather or einsum and the add as torch passes -- for A/B timing.  With
     ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series."""
-    from . import _hip
     G = m.G
     dt = G.dtype
     if noise_var is not None:
