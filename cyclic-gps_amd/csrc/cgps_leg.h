@@ -247,6 +247,10 @@ __device__ __forceinline__ bool gap_terms(T dt, const T (&G)[D][D], bool want_ri
 // workgroup moves G, Rs and Os to model k's slices (G[M][d][d], rows k N .. (k+1) N - 1 of the concatenated Rs / Os) and
 // is the one-model workgroup from there on; ts and cut are every model's.  The last row of a model that is not the last
 // also writes the zero coupling block between two models, Os[(k+1) N - 1]; failures report the concatenated row.
+//
+// MODELS with a TERM (cgps_leg_posterior_blocks_models): the term is per model as well -- term[M][d][d] (PLAIN),
+// term[M][entries][d][d] (TABLE, WEIGHTED) and the weights w[M][N][entries] -- and the workgroup moves to model k's slices
+// of those too; the pattern bytes of the table source belong to the data and stay every model's.
 constexpr int PEG_TERM_NONE = 0, PEG_TERM_PLAIN = 1, PEG_TERM_TABLE = 2, PEG_TERM_WEIGHTED = 3;
 
 // the block sizes of cgps_leg_loglik_models, whose backward the models forms of the assembly serve
@@ -269,6 +273,8 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
     Gg += k * DD;
     Rs += k * N * DD;
     Os += k * N * DD;
+    if constexpr (TERM == PEG_TERM_PLAIN) term += k * DD;                              // term[M][d][d]
+    else if constexpr (TERM != PEG_TERM_NONE) term += k * (int64_t)entries * DD;       // term[M][entries][d][d]
   }
   T G[D][D];
 #pragma unroll
@@ -327,7 +333,9 @@ __global__ __launch_bounds__(LEG_THREADS) void peg_precision_kernel(const T* __r
 #pragma unroll
       for (int b = 0; b < D; ++b) R[a][b] += A[a][b];
   } else if constexpr (TERM == PEG_TERM_WEIGHTED) {
-    const T* __restrict__ w = static_cast<const T*>(rows) + i * (int64_t)entries;
+    int64_t wi = i;
+    if constexpr (MODELS) wi += (int64_t)blockIdx.y * N;                               // w[M][N][entries]
+    const T* __restrict__ w = static_cast<const T*>(rows) + wi * (int64_t)entries;
     T S[D][D];
 #pragma unroll
     for (int a = 0; a < D; ++a)
@@ -567,7 +575,11 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_kernel(const T* __r
 // (and of Co, whose entry at a series' last row is the cut gap and is never read), its targets are
 // tt[toff[b] .. toff[b+1]-1].  One lane per target: it finds its series as the one b with toff[b] <= k < toff[b+1]
 // (binary search; series without targets are stepped over), then works on that series' slices alone.
-template <typename T, int D>
+//
+// MODELS (cgps_leg_intercast_models): the same rows and targets under gridDim.y models.  blockIdx.y names the model: the
+// workgroup moves G, mu, Pd, Co (R = roff[B] rows per model; Co's entry between two models is a series' last and never
+// read) and both outputs (p targets per model) to that model's slices and is the one-model workgroup from there on.
+template <typename T, int D, bool MODELS = false>
 __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_seg_kernel(
     const T* __restrict__ ts, const int64_t* __restrict__ roff, const T* __restrict__ tt,
     const int64_t* __restrict__ toff, int64_t B, int64_t p, const T* __restrict__ Gg, const T* __restrict__ mu,
@@ -575,6 +587,15 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_intercast_seg_kernel(
   constexpr int DD = D * D;
   const int64_t k = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
   if (k >= p) return;
+  if constexpr (MODELS) {
+    const int64_t m = blockIdx.y, R = roff[B];
+    Gg += m * DD;
+    mu += m * R * D;
+    Pd += m * R * DD;
+    Co += m * R * DD;
+    out_mean += m * p * D;
+    out_cov += m * p * DD;
+  }
   int64_t lo = 0, hi = B;                          // first b with toff[b + 1] > k
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;

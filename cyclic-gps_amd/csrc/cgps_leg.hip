@@ -190,4 +190,66 @@ int cgps_leg_posterior_blocks_seg(const void* ts, const void* G, const unsigned 
   });
 }
 
+int cgps_leg_posterior_blocks_models(const void* ts, const void* G, const unsigned char* cut, int64_t R, int64_t M, int d,
+                                     int dtype, int source, const void* term, int entries, const void* rows, void* K_Rs,
+                                     void* Os, int* info, void* stream) {
+  if (M < 1 || M > 65535)
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_models: M = %lld models, outside 1..65535", (long long)M);
+  if (bad_common(R, d) || !ts || !G || !term || !K_Rs || (M * R > 1 && !Os) || !info)
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_models: null pointer or R < 1");
+  if (source < CGPS_ROWS_PLAIN || source > CGPS_ROWS_WEIGHTED)
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_models: source = %d, outside 0..2", source);
+  if (source != CGPS_ROWS_PLAIN && !rows) return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_models: null pattern or weights");
+  if (source == CGPS_ROWS_TABLE && (entries < 1 || entries > 256))
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_models: %d table entries, outside 1..256", entries);
+  if (source == CGPS_ROWS_WEIGHTED && (entries < 1 || entries > 64))
+    return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_models: Kb = %d basis blocks, outside 1..64", entries);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nb = (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+    if (nb > 0x7fffffffLL)
+      return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_models: R = %lld rows, too many for one launch", (long long)R);
+    (void)hipMemsetAsync(info, 0, sizeof(int), st);
+    const dim3 grid((unsigned)nb, (unsigned)M), block(cgps::LEG_THREADS);
+    if (source == CGPS_ROWS_PLAIN)
+      hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D, cgps::PEG_TERM_PLAIN, true>), grid, block, 0, st, (const T*)ts,
+                         (const T*)G, R, (T*)K_Rs, (T*)Os, info, cut, (const T*)term, rows, entries);
+    else if (source == CGPS_ROWS_TABLE)
+      hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D, cgps::PEG_TERM_TABLE, true>), grid, block, 0, st, (const T*)ts,
+                         (const T*)G, R, (T*)K_Rs, (T*)Os, info, cut, (const T*)term, rows, entries);
+    else
+      hipLaunchKernelGGL((cgps::peg_precision_kernel<T, D, cgps::PEG_TERM_WEIGHTED, true>), grid, block, 0, st, (const T*)ts,
+                         (const T*)G, R, (T*)K_Rs, (T*)Os, info, cut, (const T*)term, rows, entries);
+    return check_launch("leg_posterior_blocks_models");
+  });
+}
+
+int cgps_leg_intercast_models(const void* ts, const int64_t* row_offsets, const void* target_ts, const int64_t* target_offsets,
+                              int64_t B, int64_t P, int64_t M, const void* G, int d, int dtype, const void* ip_mean,
+                              const void* ip_cov_diag, const void* ip_cov_offdiag, void* out_mean, void* out_cov,
+                              void* stream) {
+  if (M < 1 || M > 65535)
+    return fail(CGPS_ERR_ARG, "cgps_leg_intercast_models: M = %lld models, outside 1..65535", (long long)M);
+  if (B < 0 || P < 0) return fail(CGPS_ERR_ARG, "cgps_leg_intercast_models: B < 0 or P < 0");
+  if (B == 0 || P == 0) return CGPS_OK;
+  // (ip_cov_offdiag may be null: one model on a batch of one one-row series has no off-diagonal block)
+  if (!ts || !row_offsets || !target_ts || !target_offsets || !G || !ip_mean || !ip_cov_diag || !out_mean || !out_cov)
+    return fail(CGPS_ERR_ARG, "cgps_leg_intercast_models: null pointer");
+  if (B > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_intercast_models: B = %lld series, at most 2^31 - 1", (long long)B);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    const int64_t nb = (P + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+    if (nb > 0x7fffffffLL)
+      return fail(CGPS_ERR_ARG, "cgps_leg_intercast_models: P = %lld targets, too many for one launch", (long long)P);
+    hipLaunchKernelGGL((cgps::leg_intercast_seg_kernel<T, D, true>), dim3((unsigned)nb, (unsigned)M), dim3(cgps::LEG_THREADS),
+                       0, (hipStream_t)stream, (const T*)ts, row_offsets, (const T*)target_ts, target_offsets, B, P,
+                       (const T*)G, (const T*)ip_mean, (const T*)ip_cov_diag, (const T*)ip_cov_offdiag, (T*)out_mean,
+                       (T*)out_cov);
+    return check_launch("leg_intercast_models");
+  });
+}
+
 }  // extern "C"

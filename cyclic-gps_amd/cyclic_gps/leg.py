@@ -1746,6 +1746,227 @@ def _dense_posterior(mean, Sd, So, B, n):
     return mean.reshape(B, n, d), (Sd.reshape(B, n, d, d), So)
 
 
+# ---- the posterior of many models over one batch -----------------------------------------------------------------
+# The models axis of the posterior: the system "model 0's batch, then model 1's batch, ..." that the backward of
+# ``log_likelihood_models`` already reduces is block-diagonal over models and series, so one factorisation and one
+# selected inverse of it are the posterior of every (model, series).  cgps_leg_posterior_blocks_models assembles it with
+# every model's own row terms, cgps_leg_intercast_models (predict.py) predicts from it.
+MODELS_POSTERIOR_MAX_ROWS = MODELS_BACKWARD_MAX_ROWS
+"""``insample_posterior_models`` and the predictions built on it run in chunks of whole models whose concatenated rows
+stay under this (a chunk always holds at least one model).  Live per row of a chunk: K's two block arrays [rows, d, d],
+the factor's three packed arrays of about the same size together with the reduction's workspace, the two covariance
+arrays [rows, d, d], and v and the mean [rows, d] -- about eight [rows, d, d] arrays, 0.84 GB each for a full chunk at
+d = 5 in fp64; with ``noise_var`` the weights [rows, obs_dim (obs_dim + 1) / 2] of all models as well."""
+
+
+def _posterior_blocks_models(ts, G, cut, source, term, rows=None):
+    """``_posterior_blocks_seg`` for the same rows under G[m, d, d] (cgps_leg_posterior_blocks_models): (K_Rs [m R, d, d],
+    Os [m R - 1, d, d] with zero blocks between two models, info).  source: _hip.ROWS_PLAIN (term [m, d, d]), ROWS_TABLE
+    (term [m, entries, d, d], rows = pattern bytes [R] shared by the models) or ROWS_WEIGHTED (term = basis [m, Kb, d, d],
+    rows = weights [m, R, Kb]).  Contiguous operands of G's dtype.  No autograd graph."""
+    m, d, R = G.shape[0], G.shape[1], ts.shape[0]
+    entries = 0 if source == _hip.ROWS_PLAIN else term.shape[1]
+    K_Rs = torch.empty(m * R, d, d, dtype=G.dtype, device=G.device)
+    Os = torch.empty(max(m * R - 1, 0), d, d, dtype=G.dtype, device=G.device)
+    info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    _hip.check(_hip.lib().cgps_leg_posterior_blocks_models(
+        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), R, m, d, _hip.dtype_code(G.dtype), source, _hip.ptr(term), entries,
+        _hip.ptr(rows), _hip.ptr(K_Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
+    return K_Rs, Os, info
+
+
+def _models_posterior_args(ms, ts, xs, lengths, observed, noise_var):
+    """Everything the posterior and prediction calls over many models check before they launch anything, with the
+    ValueErrors of ``log_likelihood_models_observed``: (ms, (N, R, B, Lambda) stacked, ts [R], xs [R, obs], lengths,
+    observed [R, obs] or None, noise_var [R, obs] / [R] or None, dense, (B, n) of the dense layout or None)."""
+    ms, mats = _models_operands(ms)
+    dense = lengths is None
+    xs_shape = tuple(xs.shape) if isinstance(xs, torch.Tensor) else ()
+    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    o = mats[2].shape[1]
+    if observed is not None:
+        observed = _batch_like_xs(observed, _OBSERVED, xs_shape, dense)
+    if noise_var is not None:
+        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
+    if xs.shape[1] != o:
+        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
+    if observed is not None:
+        observed = _observed_2d(observed, o)
+    if (lengths and _posterior_batch_supported(ts, mats[0][0]) and (observed is not None or noise_var is not None)
+            and o > MAX_PATTERN_OBS):
+        raise ValueError("observation patterns are tabulated for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, o))
+    return ms, mats, ts, xs, lengths, observed, noise_var, dense, (xs_shape[:2] if dense else None)
+
+
+def _models_posterior_operands(mats, xs, observed, noise_var):
+    """The stacked operands of the posterior systems, built as ``log_likelihood_models`` and
+    ``log_likelihood_models_observed`` build them (elementwise over the models: a model's operands do not depend on its
+    neighbours): (G [M, d, d], source, term, rows, v [M, R, d]), contiguous and of the models' dtype."""
+    Nm, Rm, Bm, Lm = mats
+    d, o, dt = Nm.shape[1], Bm.shape[1], Nm.dtype
+    G = _contract(Nm, Nm.transpose(1, 2)) + (Rm - Rm.transpose(1, 2)) + _scaled_eye(d, 1e-5, dt, Nm.device)
+    LLT = _contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(o, 1e-9, dt, Nm.device)
+    if observed is None and noise_var is None:
+        Li, _ = _spd_inverse_logdet(LLT)
+        xl = _contract(xs.unsqueeze(0), Li)                                     # [M, R, obs]
+        source, term, rows = _hip.ROWS_PLAIN, _contract(_contract(Bm.transpose(1, 2), Li), Bm).to(dt).contiguous(), None
+    else:
+        xz = xs if observed is None else torch.where(observed, xs, torch.zeros((), dtype=xs.dtype, device=xs.device))
+        if noise_var is not None:
+            basis, weights, Li_rows, _ = _models_noise_rows(Bm, LLT, o, dt, observed, noise_var)
+            source, term, rows = _hip.ROWS_WEIGHTED, basis.to(dt).contiguous(), weights.to(dt).contiguous()
+        else:
+            pattern = (observed * (1 << torch.arange(o, device=observed.device))).sum(1).to(torch.uint8)
+            Li_table, A_table, _ = _models_pattern_tables(Bm, LLT, o, dt)
+            Li_rows = Li_table[:, pattern.long()]
+            source, term, rows = _hip.ROWS_TABLE, A_table.to(dt).contiguous(), pattern
+        xl = _contract(xz.unsqueeze(0).unsqueeze(2), Li_rows).squeeze(2)        # x~^T Li per model and row
+    return G.contiguous(), source, term, rows, _contract(xl, Bm).to(dt).contiguous()
+
+
+def _models_series_ends(plan, m):
+    """Device int64 [m B - 1]: the entries of the off-diagonal array of m models' concatenated batches that lie between two
+    series or two models.  Computed on the device from the plan's offsets (nothing copied from the host) and kept."""
+    kept = plan.__dict__.setdefault("_models_ends", {})
+    idx = kept.get(m)
+    if idx is None:
+        ends = plan.offsets[1:] - 1
+        idx = kept[m] = (torch.arange(m, device=ends.device).unsqueeze(1) * plan.R + ends).reshape(-1)[:-1].contiguous()
+    return idx
+
+
+def _models_row(plan, row):
+    """(model of the chunk, series, local row) of a row of the concatenated system of several models' batches."""
+    b, r = _series_of_row(plan, row % plan.R)
+    return row // plan.R, b, r
+
+
+def _failed_model_series(plan, m, K_Rs, K_Os, row):
+    """(model of the chunk, series, local row) of a factorisation that failed near ``row`` of the concatenated system.
+    The factor's info word is the SMALLEST row whose pivot was not positive, and once a block has failed its NaN climbs the
+    levels of the concatenated reduction through the zero couplings (0 * NaN) and fails pivots of earlier series and
+    models too: the word can name a row in front of the one that broke.  So, on this path only, every (model, series) is
+    reduced on its own (``cr.mahal_and_det_batch``: one workgroup per system, systems never meet) and the first that
+    fails is named; if none does there, ``row`` is mapped through k = row // R and ``_series_of_row``."""
+    try:
+        cr.mahal_and_det_batch(K_Rs, K_Os, None, lengths=list(plan.lengths) * m)
+    except cr.NotPSDError as e:
+        system = getattr(e, "system", None)
+        if system is not None:
+            return system // plan.B, system % plan.B, e.row
+    return _models_row(plan, row)
+
+
+def _posterior_models_chunks(plan, ts, G, source, term, rows, v):
+    """The posterior of every model in chunks of whole models (MODELS_POSTERIOR_MAX_ROWS): yields (k0, k1, mean [m R, d],
+    cov_diag [m R, d, d], cov_off [m R - 1, d, d]) of the models k0 .. k1 - 1, the entries of cov_off between two series
+    or two models exactly zero.  One assembly launch, one ``cr.decompose_solve`` and one ``cr.inverse_blocks`` per chunk."""
+    M, d, R = G.shape[0], G.shape[1], plan.R
+    per = max(1, MODELS_POSTERIOR_MAX_ROWS // R)
+    for k0 in range(0, M, per):
+        k1 = min(M, k0 + per)
+        m = k1 - k0
+        K_Rs, K_Os, info = _posterior_blocks_models(ts, G[k0:k1], plan.cut, source, term[k0:k1],
+                                                    rows if source != _hip.ROWS_WEIGHTED else rows[k0:k1])
+        if cr.CHECK_POSITIVE_DEFINITE:
+            bad = int(info.item())
+            if bad:
+                k, b, r = _models_row(plan, bad - 1)
+                raise cr.NotPSDError("LEG models: model %d, series %d: the time gap next to its row %d gives a singular PEG "
+                                     "block (zero-length gap?)" % (k0 + k, b, r))
+        try:
+            dec, mean = cr.decompose_solve(K_Rs, K_Os, v[k0:k1].reshape(m * R, d))
+        except cr.NotPSDError as e:
+            row = getattr(e, "row", None)
+            if row is None:
+                raise
+            k, b, r = _failed_model_series(plan, m, K_Rs, K_Os, row)
+            raise cr.NotPSDError("LEG models: model %d, series %d: a block near its row %d is not positive definite"
+                                 % (k0 + k, b, r)) from None
+        del K_Rs, K_Os
+        Sd, So = cr.inverse_blocks(dec)
+        del dec
+        if m * R > 1:
+            So.index_fill_(0, _models_series_ends(plan, m), 0)   # (zero up to its sign or a failed model's NaN: exactly zero)
+        yield k0, k1, mean, Sd, So
+
+
+def _posterior_models_per_model(ms, each):
+    """What inputs outside ``_posterior_batch_supported`` get: ``each(model)`` -- one batched call -- per model, a
+    NotPSDError prefixed with the model."""
+    outs = []
+    for k, m in enumerate(ms):
+        try:
+            outs.append(each(m))
+        except cr.NotPSDError as e:
+            raise cr.NotPSDError("LEG models: model %d: %s" % (k, e)) from None
+    return outs
+
+
+def insample_posterior_models(ms, ts, xs, lengths=None, observed=None, noise_var=None):
+    """``insample_posterior_batch`` of M LEG models for the same B series in one call: slot k of every result is
+    ``insample_posterior_batch(ms[k], ...)``.  What the posterior under every chain of a population, under every start of
+    a fit that survived, or under the components of a mixture needs.  Inference only: the call runs under
+    ``torch.no_grad`` and nothing it returns carries an autograd graph.
+
+    ``ms``, ``ts`` / ``xs`` / ``lengths``, ``observed`` and ``noise_var``: exactly those of
+    ``log_likelihood_models_observed``, with its ValueErrors, raised before anything is launched; the mask and the
+    variances belong to the data and are shared by all models.  Dense (``lengths=None``): mean [M, B, n, d], (cov_diag
+    [M, B, n, d, d], cov_off [M, B, n-1, d, d]).  Ragged: mean [M, R, d], (cov_diag [M, R, d, d], cov_off [M, R-1, d, d]),
+    the entry of cov_off at a series boundary exactly zero.  An empty batch gives empty tensors with leading dimension M.
+
+    How: the stacked operands of ``log_likelihood_models*`` (elementwise over the models), ONE
+    cgps_leg_posterior_blocks_models for the blocks of the system "model 0's batch, then model 1's batch, ..." with
+    every model's own row terms, ONE ``cr.decompose_solve`` and ONE ``cr.inverse_blocks`` on its M R rows (DESIGN.md
+    4.18); more than MODELS_POSTERIOR_MAX_ROWS rows go in chunks of whole models.  Every rank 1..8, both precisions.  A
+    repeated call with the same lengths copies nothing from the host (``_cached_batch_plan``); with
+    ``cr.CHECK_POSITIVE_DEFINITE`` off nothing is read on the host either.  Not capturable in a HIP graph.
+
+    Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a block that is not positive definite, or a zero-length gap, raises
+    ``cr.NotPSDError`` naming the model, the series and its local row.  With the check off the failed model's results are
+    NaN, and the NaN CAN REACH NEIGHBOURING SERIES AND MODELS OF THE SAME CHUNK: the concatenated reduction multiplies a
+    neighbour's blocks by the zero coupling, and 0 * NaN = NaN (as in ``insample_posterior_batch``).
+
+    CPU tensors, or a rank or dtype outside the kernels', take one ``insample_posterior_batch`` per model; a
+    NotPSDError from it is prefixed with the model."""
+    with torch.no_grad():
+        ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
+                                                                                          noise_var)
+        M, d, dt = len(ms), mats[0].shape[1], mats[0].dtype
+        if not lengths:
+            e = lambda *shape: torch.empty(shape, dtype=dt, device=ts.device)      # noqa: E731
+            if dense:
+                return e(M, 0, bn[1], d), (e(M, 0, bn[1], d, d), e(M, 0, max(bn[1] - 1, 0), d, d))
+            return e(M, 0, d), (e(M, 0, d, d), e(M, 0, d, d))
+        R = sum(lengths)
+        if not _posterior_batch_supported(ts, mats[0][0]):
+            outs = _posterior_models_per_model(ms, lambda m: _posterior_flat(m, ts, xs, lengths, observed, noise_var))
+            mean, Sd, So = (torch.stack([o[j] for o in outs]) for j in range(3))
+            if dense:
+                B, n = bn
+                So = torch.stack([_dense_posterior(o[0], o[1], o[2], B, n)[1][1] for o in outs])
+                return mean.reshape(M, B, n, d), (Sd.reshape(M, B, n, d, d), So)
+            return mean, (Sd, So)
+        plan = _cached_batch_plan(lengths, mats[0].device)
+        G, source, term, rows, v = _models_posterior_operands(mats, xs, observed, noise_var)
+        mean = torch.empty(M, R, d, dtype=dt, device=G.device)
+        Sd = torch.empty(M, R, d, d, dtype=dt, device=G.device)
+        # (a model's R - 1 entries; the one between two models is dropped.  Dense: the ones between two series as well)
+        off_shape, off_strides = ((R - 1, d, d), (d * d, d, 1))
+        if dense:
+            B, n = bn
+            off_shape, off_strides = ((B, n - 1, d, d), (n * d * d, d * d, d, 1))
+        So = torch.empty((M,) + off_shape, dtype=dt, device=G.device)
+        for k0, k1, mean_c, Sd_c, So_c in _posterior_models_chunks(plan, ts.to(dt).contiguous(), G, source, term, rows, v):
+            mean[k0:k1] = mean_c.view(k1 - k0, R, d)
+            Sd[k0:k1] = Sd_c.view(k1 - k0, R, d, d)
+            if So.numel():
+                So[k0:k1] = So_c.as_strided((k1 - k0,) + off_shape, (R * d * d,) + off_strides, So_c.storage_offset())
+        if dense:
+            return mean.view(M, B, n, d), (Sd.view(M, B, n, d, d), So)
+        return mean, (Sd, So)
+
+
 # ---- drawing from the process -----------------------------------------------------------------------
 def sample_observations(m, z, seed, stream=1):
     """Observations of latent paths z [n, rank, S]: x = B z + Lambda eps' [n, obs, S], eps' =

@@ -320,3 +320,122 @@ def make_predictions_batch(m, ts, xs, target_ts, lengths=None, target_lengths=No
     with torch.no_grad():
         pm, pv = predictive_posterior_batch(m, ts, xs, target_ts, lengths, target_lengths, observed, noise_var, check_sorted)
         return pm @ m.B.T, m.B @ pv @ m.B.T
+
+
+# ---- many models over one batch --------------------------------------------------------------------------------
+def _intercast_models_hip(G, ip_mean, Rs, Os, ts, plan, target_ts, tplan, means, covs):
+    """All targets of all series under the models G[m, d, d] in one HIP kernel (cgps_leg_intercast_models): grid
+    (target blocks, m), model k on its slices of the concatenated posterior ip_mean [m R, d], Rs [m R, d, d], Os
+    [m R - 1, d, d], its predictions written into means[k] [m, P, d] and covs[k] [m, P, d, d] (contiguous)."""
+    from . import _hip
+    d, P = G.shape[1], tplan.P
+    _hip.check(_hip.lib().cgps_leg_intercast_models(
+        _hip.ptr(ts), _hip.ptr(plan.offsets), _hip.ptr(target_ts), _hip.ptr(tplan.offsets), plan.B, P, G.shape[0], _hip.ptr(G),
+        d, _hip.dtype_code(G.dtype), _hip.ptr(ip_mean), _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(means), _hip.ptr(covs),
+        _hip.stream_ptr()))
+
+
+def _predictive_posterior_models_flat(ms, ts, xs, target_ts, lengths, target_lengths, observed, noise_var, check_sorted):
+    """(means [M, P, rank], covs [M, P, rank, rank], B stacked [M, obs, rank], shape of the dense targets (B, p) or None)
+    of the validated call: the predictions in the order of the flattened targets."""
+    ms, mats, ts_f, xs_f, lens, observed, noise_var, dense, _ = leg._models_posterior_args(ms, ts, xs, lengths, observed,
+                                                                                           noise_var)
+    tt, tlens, bp = _batch_targets(target_ts, target_lengths, lens, dense)
+    M, d, dt, dev = len(ms), mats[0].shape[1], mats[0].dtype, ts_f.device
+    P = sum(tlens)
+    if not lens or P == 0:
+        return torch.empty(M, P, d, dtype=dt, device=dev), torch.empty(M, P, d, d, dtype=dt, device=dev), mats[2], bp
+    tt = tt.to(ts_f.dtype)
+    if not leg._posterior_batch_supported(ts_f, mats[0][0]):
+        outs = leg._posterior_models_per_model(ms, lambda m: predictive_posterior_batch(
+            m, ts_f, xs_f, tt, lens, tlens, observed, noise_var, check_sorted))
+        return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs]), mats[2], bp
+    tplan = leg._cached_batch_plan(tlens, mats[0].device, make=_TargetPlan)
+    if check_sorted and P > 1:
+        assert bool(((tt[1:] - tt[:-1] > 0) | tplan.across).all())             # reference :471, per series
+    plan = leg._cached_batch_plan(lens, mats[0].device)
+    G, source, term, rows, v = leg._models_posterior_operands(mats, xs_f, observed, noise_var)
+    ts_c, tt_c = ts_f.to(dt).contiguous(), tt.to(dt).contiguous()
+    pm = torch.empty(M, P, d, dtype=dt, device=G.device)
+    pv = torch.empty(M, P, d, d, dtype=dt, device=G.device)
+    for k0, k1, mean, Sd, So in leg._posterior_models_chunks(plan, ts_c, G, source, term, rows, v):
+        _intercast_models_hip(G[k0:k1], mean, Sd, So, ts_c, plan, tt_c, tplan, pm[k0:k1], pv[k0:k1])
+    return pm, pv, mats[2], bp
+
+
+def predictive_posterior_models(ms, ts, xs, target_ts, lengths=None, target_lengths=None, observed=None, noise_var=None,
+                                check_sorted=True):
+    """``predictive_posterior_batch`` of M LEG models for the same B series and the same targets in one call: slot k is
+    ``predictive_posterior_batch(ms[k], ...)``.  Inference only: runs under ``torch.no_grad``.
+
+    ``ms``, the layouts, ``observed`` and ``noise_var``: those of ``leg.insample_posterior_models`` (all models share the
+    data, the mask and the variances).  Targets, ``target_lengths`` and ``check_sorted``: those of
+    ``predictive_posterior_batch``; the targets are shared by all models.  Dense returns (means [M, B, p, rank], covs
+    [M, B, p, rank, rank]), ragged ([M, P, rank], [M, P, rank, rank]) in the order of target_ts.
+
+    How: ``leg.insample_posterior_models``'s one factorisation of the concatenated system of all models' batches, then
+    ONE launch of cgps_leg_intercast_models, grid (target blocks, M): model k's workgroups read its slices of the
+    posterior and never a row of another model or series.  More than ``leg.MODELS_POSTERIOR_MAX_ROWS`` rows go in chunks
+    of whole models, each with its own factorisation and launch.  A repeated call with the same lengths and target
+    lengths copies nothing from the host.  Errors, NaN propagation with ``cr.CHECK_POSITIVE_DEFINITE`` off and
+    unsupported inputs (one ``predictive_posterior_batch`` per model): ``leg.insample_posterior_models``."""
+    with torch.no_grad():
+        pm, pv, _, bp = _predictive_posterior_models_flat(ms, ts, xs, target_ts, lengths, target_lengths, observed, noise_var,
+                                                          check_sorted)
+        if bp is not None:
+            M, d = pm.shape[0], pm.shape[-1]
+            return pm.reshape((M,) + bp + (d,)), pv.reshape((M,) + bp + (d, d))
+        return pm, pv
+
+
+def make_predictions_models(ms, ts, xs, target_ts, lengths=None, target_lengths=None, observed=None, noise_var=None,
+                            check_sorted=True):
+    """``make_predictions_batch`` of M LEG models for the same B series and targets in one call: predicted observation
+    mean [M, ..., obs_dim] and covariance [M, ..., obs_dim, obs_dim], every model's latent posterior mapped through its own
+    B, without observation noise.  Arguments, layouts ([M, B, p, ...] dense, [M, P, ...] ragged), inference-only results
+    and errors: ``predictive_posterior_models``.  ``combine_predictions`` turns the M predictions into one."""
+    with torch.no_grad():
+        pm, pv, Bm, bp = _predictive_posterior_models_flat(ms, ts, xs, target_ts, lengths, target_lengths, observed,
+                                                           noise_var, check_sorted)
+        # B C B^T without a product broadcast over the targets (M P tiny matrix products): C B^T as one product per model
+        # over all its targets' rows, then the obs_dim x obs_dim result as rank sums of elementwise products
+        (M, P, d), o = pm.shape, Bm.shape[1]
+        Bt = Bm.transpose(1, 2).contiguous()
+        om = torch.bmm(pm, Bt)
+        half = torch.bmm(pv.reshape(M, P * d, d), Bt).view(M, P, 1, d, o)                # C B^T: [M, P, 1, d, obs]
+        Bl = Bm.unsqueeze(1).unsqueeze(-1)                                               # [M, 1, obs, d, 1]
+        ov = Bl[:, :, :, 0] * half[:, :, :, 0]
+        for j in range(1, d):
+            ov = ov + Bl[:, :, :, j] * half[:, :, :, j]
+        if bp is not None:
+            return om.reshape((M,) + bp + (o,)), ov.reshape((M,) + bp + (o, o))
+        return om, ov
+
+
+def combine_predictions(means, covs, weights):
+    """The moment-matched mixture of M predictions: mean sum_k w_k mu_k and covariance sum_k w_k (C_k + mu_k mu_k^T) -
+    mu mu^T, for means [M, ..., c] and covs [M, ..., c, c] as ``make_predictions_models`` and
+    ``predictive_posterior_models`` return them.  ``weights``: [M] -- one weight per model -- or [M, B] matching the
+    second dimension of means (one per model and series of the dense layout; per model and target of the ragged one):
+    responsibilities, or softmaxed log-likelihoods from ``leg.log_likelihood_models``.  The weights are NOT normalised
+    for the caller.  The sum over k runs in ascending order with plain multiplies and adds, so a slot does not depend on
+    the other series.  Pure torch, any device; ValueError when the shapes do not agree."""
+    for name, t in (("means", means), ("covs", covs), ("weights", weights)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a tensor" % name)
+    if means.dim() < 2 or means.shape[0] < 1:
+        raise ValueError("means must be [M, ..., c] with M >= 1, got %s" % (tuple(means.shape),))
+    if tuple(covs.shape) != tuple(means.shape) + (means.shape[-1],):
+        raise ValueError("covs must be %s for means %s, got %s"
+                         % (tuple(means.shape) + (means.shape[-1],), tuple(means.shape), tuple(covs.shape)))
+    if weights.dim() not in (1, 2) or weights.dim() > means.dim() - 1 or tuple(weights.shape) != tuple(means.shape[:weights.dim()]):
+        raise ValueError("weights must be [M] or [M, B] matching the leading dimensions of means %s, got %s"
+                         % (tuple(means.shape), tuple(weights.shape)))
+    w = weights.to(means.dtype).reshape(tuple(weights.shape) + (1,) * (means.dim() - weights.dim()))
+    mu, second = None, None
+    for k in range(means.shape[0]):
+        mk, wk = means[k], w[k]
+        sk = covs[k] + mk.unsqueeze(-1) * mk.unsqueeze(-2)
+        mu = wk * mk if mu is None else mu + wk * mk
+        second = wk.unsqueeze(-1) * sk if second is None else second + wk.unsqueeze(-1) * sk
+    return mu, second - mu.unsqueeze(-1) * mu.unsqueeze(-2)

@@ -388,6 +388,25 @@ int cgps_leg_posterior_blocks_seg(const void* ts, const void* G, const unsigned 
                                   int source, const void* term, int entries, const void* rows, void* K_Rs, void* Os,
                                   int* info, void* stream);
 
+/* cgps_leg_posterior_blocks_seg of the same R rows under M models: the blocks of the block-diagonal POSTERIOR system
+ * "model 0's batch, then model 1's batch, ...", K_Rs[M R][d][d] and Os[M R - 1][d][d], written once in ONE launch
+ * (grid (ceil(R / 64), M)).  It is to cgps_leg_posterior_blocks_seg what cgps_peg_precision_models is to
+ * cgps_peg_precision_seg.  ts[R], cut[R-1] (NULL: one series) and, for the table source, the pattern bytes rows[R]
+ * belong to the data: they are read by every model and not tiled in memory.  Model k uses G[k] of G[M][d][d] and
+ * source = CGPS_ROWS_PLAIN:    term[k] of term[M][d][d];
+ *          CGPS_ROWS_TABLE:    term[k] of term[M][entries][d][d], 1 <= entries <= 256, rows = pattern[R] shared;
+ *          CGPS_ROWS_WEIGHTED: term[k] of basis[M][entries][d][d], 1 <= entries <= 64, and rows[k] of w[M][R][entries]
+ *                              (the weights are the entries of each model's own inverse noise covariance).
+ * Rows k R .. (k+1) R - 1 of K_Rs and the same R - 1 entries of Os equal what cgps_leg_posterior_blocks_seg writes for
+ * (ts, G[k], cut, source, term[k], rows or rows[k]) bit for bit.  The coupling block between two models, Os[k R - 1], is
+ * written as zeros and nothing is evaluated for it.  info: 0 or 1 + a row of the concatenated system next to a singular
+ * gap.  Built for every d in 1..8 in both precisions, as cgps_leg_posterior_blocks_seg is (not the restricted set of
+ * cgps_peg_precision_models).  A null pointer, R < 1, M outside 1..65535, an unknown source or entries outside its
+ * range: CGPS_ERR_ARG before anything is launched; d outside 1..8 or an unknown dtype: CGPS_ERR_UNSUPPORTED. */
+int cgps_leg_posterior_blocks_models(const void* ts, const void* G, const unsigned char* cut, int64_t R, int64_t M, int d,
+                                     int dtype, int source, const void* term, int entries, const void* rows, void* K_Rs,
+                                     void* Os, int* info, void* stream);
+
 /* Prediction glue of LEG models, the step AFTER the path (reference models.py:455-514 intercast with
  * forecast :394-408, interpolate :410-452 and gaussian_stitch model_utils.py:64-107, which the reference
  * runs as a Python loop over the targets): posterior mean and covariance of the latent at p target
@@ -413,6 +432,20 @@ int cgps_leg_intercast_seg(const void* ts, const int64_t* row_offsets, const voi
                            const int64_t* target_offsets, int64_t B, int64_t P, const void* G, int d, int dtype,
                            const void* ip_mean, const void* ip_cov_diag, const void* ip_cov_offdiag,
                            void* out_mean, void* out_cov, void* stream);
+
+/* cgps_leg_intercast_seg under M models, all targets of all series of all models in ONE launch, grid
+ * (ceil(P / 64), M).  ts[R], row_offsets[B+1], target_ts[P] and target_offsets[B+1] describe the batch and its targets
+ * once and are shared by the models (R = row_offsets[B]); model k brings G[k] of G[M][d][d] and its slices of the
+ * posterior of the concatenated system "model 0's batch, then model 1's batch, ...": rows k R .. (k+1) R - 1 of
+ * ip_mean[M R][d] and ip_cov_diag[M R][d][d], the R - 1 entries from k R of ip_cov_offdiag[M R - 1][d][d], and gets
+ * out_mean[k] of out_mean[M][P][d], out_cov[k] of out_cov[M][P][d][d].  Slice k equals cgps_leg_intercast_seg on model
+ * k's slices bit for bit; no lane reads a row of another model or series, nor the off-diagonal entry of a cut gap or of
+ * the boundary between two models, whatever they hold.  Errors: those of cgps_leg_intercast_seg, and M outside 1..65535:
+ * CGPS_ERR_ARG; B = 0 or P = 0: CGPS_OK, nothing launched.  No workspace, no info word. */
+int cgps_leg_intercast_models(const void* ts, const int64_t* row_offsets, const void* target_ts,
+                              const int64_t* target_offsets, int64_t B, int64_t P, int64_t M, const void* G, int d,
+                              int dtype, const void* ip_mean, const void* ip_cov_diag, const void* ip_cov_offdiag,
+                              void* out_mean, void* out_cov, void* stream);
 
 /* ---- time-axis sharding (one shard per GPU / rank) -----------------------------------------
  * The reference has no distributed code; this is the multi-GPU form BASELINE.json asks for.
