@@ -1,7 +1,9 @@
-// cgps_sample.hip -- counter-based standard normals and samples from N(mean, J^-1) off a stored factor
+// cgps_sample.hip -- counter-based standard normals, samples from N(mean, J^-1) off a stored factor, and the
+// perturbed right-hand sides of the batched LEG draws (cgps_leg_perturb.h)
 // One translation unit of libcgps (include/cgps.h); host code only decides sizes/offsets and
 // enqueues kernels on the caller's stream: nothing here allocates, copies to the host or synchronises.
 #include "cgps_host.h"
+#include "cgps_leg_perturb.h"
 #include "cgps_sample_tile.h"
 
 using namespace cgps_host;
@@ -73,6 +75,20 @@ int run_sample(const T* Dp, const T* Fp, const T* Gp, int64_t N, int64_t nrhs, c
   }
   return check_launch("sample");
 }
+
+template <typename T, int D, int HSRC>
+int run_perturbation(const T* ts, int64_t R, const T* G, const int64_t* roff, const int64_t* ids, int64_t B, const T* hterm,
+                     int entries, int obs, const unsigned char* rows, const T* v, int64_t nrhs, uint64_t seed,
+                     uint32_t stream_id, T* out, int* info, hipStream_t st) {
+  constexpr int GC = cgps::RngGroup<T>::COLS;
+  const int64_t groups = (nrhs + GC - 1) / GC, nb = (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+  const int64_t chunks = (groups + cgps::PERT_CHUNK_GROUPS - 1) / cgps::PERT_CHUNK_GROUPS;
+  (void)hipMemsetAsync(info, 0, sizeof(int), st);
+  hipLaunchKernelGGL((cgps::leg_perturbation_kernel<T, D, HSRC>), dim3((unsigned)nb, (unsigned)(chunks < 65535 ? chunks : 65535)),
+                     dim3(cgps::LEG_THREADS), 0, st, ts, R, G, roff, ids, B, hterm, entries, obs, rows, v, nrhs, groups, seed,
+                     stream_id, out, info);
+  return check_launch("leg_perturbation_seg");
+}
 }  // namespace
 
 extern "C" {
@@ -106,6 +122,41 @@ int cgps_sample(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d
                                          (char*)ws, ws_bytes, (hipStream_t)stream);
       default: return run_sample<T, D, 8>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)mean, seed, stream_id, (T*)x,
                                           (char*)ws, ws_bytes, (hipStream_t)stream);
+    }
+  });
+}
+
+int cgps_leg_perturbation_seg(const void* ts, int64_t R, const void* G, int d, int dtype, const int64_t* row_offsets,
+                              const int64_t* series_ids, int64_t B, int hsource, const void* hterm, int entries, int obs,
+                              const unsigned char* rows, const void* v, int64_t nrhs, uint64_t seed, uint32_t stream_id,
+                              void* out, int* info, void* stream) {
+  if (B < 0 || R < 0) return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_seg: B < 0 or R < 0");
+  if (B == 0 || R == 0) return CGPS_OK;
+  if (d < 1 || nrhs < 1 || !ts || !G || !row_offsets || !series_ids || !out || !info)
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_seg: null pointer, d < 1 or nrhs < 1");
+  if (hsource < CGPS_H_NONE || hsource > CGPS_H_ROWS)
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_seg: hsource = %d, outside 0..3", hsource);
+  if (hsource != CGPS_H_NONE && (!hterm || obs < 1 || obs > 8))
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_seg: null hterm or obs = %d outside 1..8", obs);
+  if (hsource == CGPS_H_TABLE && (!rows || entries < 1 || entries > 256))
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_seg: null pattern or %d table entries, outside 1..256", entries);
+  if (B > 0x7fffffffLL || (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS > 0x7fffffffLL)
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_seg: B = %lld series or R = %lld rows, too many for one launch",
+                (long long)B, (long long)R);
+  if (nrhs > (int64_t)1 << 32) return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_seg: more than 2^32 columns");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    auto run = [&](auto hs) {
+      return run_perturbation<T, D, decltype(hs)::value>((const T*)ts, R, (const T*)G, row_offsets, series_ids, B, (const T*)hterm,
+                                                         entries, obs, rows, (const T*)v, nrhs, seed, stream_id, (T*)out, info,
+                                                         (hipStream_t)stream);
+    };
+    switch (hsource) {
+      case CGPS_H_NONE: return run(std::integral_constant<int, cgps::PERT_H_NONE>{});
+      case CGPS_H_PLAIN: return run(std::integral_constant<int, cgps::PERT_H_PLAIN>{});
+      case CGPS_H_TABLE: return run(std::integral_constant<int, cgps::PERT_H_TABLE>{});
+      default: return run(std::integral_constant<int, cgps::PERT_H_ROWS>{});
     }
   });
 }

@@ -17,6 +17,7 @@ OP_MAHAL_LOGDET, OP_DECOMPOSE, OP_HALFSOLVE, OP_BACKSOLVE, OP_SOLVE, OP_LOGDET_F
     OP_MAHAL_LOGDET_LEVELWISE, OP_DECOMPOSE_SOLVE = range(9)
 MAX_LEVELS = 64
 ROWS_PLAIN, ROWS_TABLE, ROWS_WEIGHTED = range(3)
+H_NONE, H_PLAIN, H_TABLE, H_ROWS = range(4)
 
 _lib = None
 
@@ -68,6 +69,8 @@ _SIGNATURES = {
     "cgps_leg_posterior_blocks_seg": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "cgps_leg_posterior_blocks_models": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "cgps_leg_intercast_models": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cgps_leg_perturbation_seg": (_int, [_vp, _i64, _vp, _int, _int, _vp, _vp, _i64, _int, _vp, _int, _int, _vp, _vp, _i64,
+                                         ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp]),
     "cgps_record_elems": (_int, [_int, _int, ctypes.POINTER(_i64)]),
     "cgps_shard_reduce": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp, _vp, _vp]),
     "cgps_finish_records": (_int, [_vp, _sz, _vp, _sz, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),

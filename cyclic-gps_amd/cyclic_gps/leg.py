@@ -1317,6 +1317,64 @@ def _noise_operands(m, ts, xs, observed, noise_var):
     return basis, weights, c_rows, xl, xz
 
 
+def _chol_forward(W, Y):
+    """T^-1 Y [..., obs, k] for the lower Cholesky factor T of W [..., obs, obs], obs <= 8: the obs steps of the
+    factorisation and of the forward substitution as batched elementwise ops -- no factorisation call, nothing read on
+    the host (capturable).  A pivot that is not positive gives NaN, like the square root of a failed block elsewhere."""
+    obs = W.shape[-1]
+    L = torch.zeros_like(W)
+    X = torch.empty_like(Y)
+    for j in range(obs):
+        lj = L[..., j, :j]
+        ljj = torch.sqrt(W[..., j, j] - (lj * lj).sum(-1)).unsqueeze(-1)
+        L[..., j, j:j + 1] = ljj
+        if j + 1 < obs:
+            L[..., j + 1:, j] = (W[..., j + 1:, j] - (L[..., j + 1:, :j] * lj.unsqueeze(-2)).sum(-1)) / ljj
+        X[..., j, :] = (Y[..., j, :] - (lj.unsqueeze(-1) * X[..., :j, :]).sum(-2)) / ljj
+    return X
+
+
+def observation_noise_factors(m, observed=None, noise_var=None):
+    """The factor H of a row's observation term, H H^T = B^T Li B, that perturb-and-solve sampling multiplies the row's
+    observation noise with (``posterior_perturbation_batch``): H = B^T M T^-T [rank, obs_dim] with M = diag(observed),
+    W = M (LLT + diag(s)) M + (I - M) -- exactly the W of ``observation_tables`` and ``observation_weights`` -- and T its
+    lower Cholesky factor.  The column of an unobserved channel is exactly zero.  Neither argument: one block
+    [rank, obs_dim].  ``observed`` alone (bool [n, obs_dim] or [n]): the table [2^obs_dim, rank, obs_dim] of all
+    patterns, indexed by ``observation_tables``' pattern byte.  ``noise_var`` ([n, obs_dim] or [n]; with or without
+    ``observed``): one block per row, [n, rank, obs_dim]; noise_var at unobserved entries is ignored, NaN included.
+    obs_dim <= 8.  Batched torch ops, nothing read on the host, no factorisation call."""
+    obs = m.B.shape[0]
+    if obs > MAX_PATTERN_OBS:
+        raise ValueError("observation noise factors are built for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, obs))
+    dt, dev = m.B.dtype, m.B.device
+    LLT = m.LLT
+    if noise_var is None and observed is None:
+        return _chol_forward(LLT, m.B).transpose(-1, -2).contiguous()
+    if noise_var is None:
+        _observed_2d(observed, obs)                                          # (its checks; every pattern is tabulated)
+        Mt = _pattern_mask_table(obs, dt, dev)
+        C = LLT
+    else:
+        if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
+            raise ValueError("noise_var must be a floating-point tensor")
+        s = noise_var.to(dt)
+        if s.dim() == 1:
+            s = s.unsqueeze(-1).expand(-1, obs)
+        if s.dim() != 2 or s.shape[1] != obs:
+            raise ValueError("noise_var must be [n] or [n, %d], got %s" % (obs, tuple(noise_var.shape)))
+        if observed is None:
+            Mt = torch.ones((), dtype=dt, device=dev).expand(s.shape)
+        else:
+            observed = _observed_2d(observed, obs)
+            if observed.shape[0] != s.shape[0]:
+                raise ValueError("observed has %d rows, noise_var has %d" % (observed.shape[0], s.shape[0]))
+            s = torch.where(observed, s, torch.zeros((), dtype=dt, device=s.device))
+            Mt = observed.to(dt)
+        C = LLT + torch.diag_embed(s)
+    W = Mt.unsqueeze(2) * C * Mt.unsqueeze(1) + torch.diag_embed(1 - Mt)
+    return _chol_forward(W, Mt.unsqueeze(2) * m.B).transpose(-1, -2).contiguous()
+
+
 def merge_targets(ts, xs, target_ts, check=True):
     """Insert the times ``target_ts`` [k] into the series as wholly unobserved rows: ``(ts_all [n + k], xs_all
     [n + k, obs], observed_all bool [n + k], target_index int64 [k])``, ts_all sorted (a stable sort on the device),
@@ -1603,14 +1661,10 @@ def _posterior_blocks_seg(ts, G, cut, source, term, rows=None):
     return K_Rs, Os, info
 
 
-def _posterior_system_batch(m, ts, xs, observed, noise_var, plan):
-    """(K_Rs, K_Os, v) of the concatenated, block-diagonal posterior system of all series: ``_posterior_system`` with the
-    series-aware assembly (zero coupling across a series boundary, the gap there never evaluated) and the rows' terms
-    added inside it (cgps_leg_posterior_blocks_seg).  CGPS_LEG_BLOCKS_COMPOSED=1 takes the composition it replaces
-    instead -- cgps_peg_precision_seg, then the gather or einsum and the add as torch passes -- for A/B timing.  With
-    ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series."""
-    G = m.G
-    dt = G.dtype
+def _posterior_operands_batch(m, ts, xs, observed, noise_var):
+    """(source, term, rows, v) of the concatenated posterior system: where the assembly takes a row's diagonal term from
+    (``_posterior_blocks_seg``) and the right-hand side v [R, d], contiguous and of G's dtype."""
+    dt = m.N.dtype
     if noise_var is not None:
         basis, weights, _, xl, _ = _noise_operands(m, ts, xs, observed, noise_var)
         source, term, rows = _hip.ROWS_WEIGHTED, basis.to(dt).contiguous(), weights.to(dt).contiguous()
@@ -1621,7 +1675,18 @@ def _posterior_system_batch(m, ts, xs, observed, noise_var, plan):
         Li = m.LLT_inv
         xl = xs @ Li
         source, term, rows = _hip.ROWS_PLAIN, (m.B.T @ Li @ m.B).to(dt).contiguous(), None
-    v = (xl @ m.B).to(dt).contiguous()
+    return source, term, rows, (xl @ m.B).to(dt).contiguous()
+
+
+def _posterior_system_batch(m, ts, xs, observed, noise_var, plan):
+    """(K_Rs, K_Os, v) of the concatenated, block-diagonal posterior system of all series: ``_posterior_system`` with the
+    series-aware assembly (zero coupling across a series boundary, the gap there never evaluated) and the rows' terms
+    added inside it (cgps_leg_posterior_blocks_seg).  CGPS_LEG_BLOCKS_COMPOSED=1 takes the composition it replaces
+    instead -- cgps_peg_precision_seg, then the gather or einsum and the add as torch passes -- for A/B timing.  With
+    ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series."""
+    G = m.G
+    dt = G.dtype
+    source, term, rows, v = _posterior_operands_batch(m, ts, xs, observed, noise_var)
     tsc, Gc = ts.to(dt).contiguous(), G.contiguous()
     if os.environ.get("CGPS_LEG_BLOCKS_COMPOSED") == "1":
         R, d = plan.R, G.shape[0]
@@ -1997,6 +2062,205 @@ def sample_from_posterior(m, ts, xs, num_samples, seed, observed=None, noise_var
         K_Rs, K_Os, v = _posterior_system(m, ts, xs, observed, noise_var)
         dec, mean = cr.decompose_solve(K_Rs, K_Os, v)
         return cr.sample(dec, num_samples, seed, mean=mean)
+
+
+# ---- drawing paths for many series at once: perturb and solve -------------------------------------
+# x = K^-1 (v + w), w ~ N(0, K), is a draw from the posterior N(K^-1 v, K^-1).  K is a sum of local positive
+# semi-definite pieces (the stationary start of a series, one transition per time gap, one observation per row), so w
+# is a sum of local pieces of noise indexed by (series id, local row): cgps_leg_perturbation_seg makes v + w for all
+# rows, series and samples in one launch, and the draw of a series does not depend on where it sits in the batch.
+MAX_SERIES_ID = 1 << 24
+SAMPLE_RHS_FACTOR = 4
+"""``sample_from_posterior_batch`` solves the right-hand sides in chunks of columns: a multiple of eight (one solve
+panel) that keeps a chunk at most this many times the size of K's own blocks (2 d^2 values a row), eight at the least."""
+
+
+def _sample_column_chunk(d):
+    return max(8, 2 * d * SAMPLE_RHS_FACTOR // 8 * 8)
+
+
+def _series_ids_arg(series_ids, lengths, d, obs, device):
+    """The ids as a device int64 [B] after the checks of the generator's index space (ValueError before any launch)."""
+    B = len(lengths)
+    if lengths and max(lengths) * max(d, obs) >= 1 << 40:
+        raise ValueError("a series of %d rows does not fit the generator's 2^40 elements per series" % max(lengths))
+    if series_ids is None:
+        if B > MAX_SERIES_ID:
+            raise ValueError("%d series: the default ids 0 .. B-1 must stay below 2^24" % B)
+        return torch.arange(B, dtype=torch.int64, device=device)
+    if isinstance(series_ids, torch.Tensor):
+        if series_ids.dim() != 1 or series_ids.dtype.is_floating_point or series_ids.dtype == torch.bool:
+            raise ValueError("series_ids must be a list or a 1-d integer tensor")
+        series_ids = series_ids.tolist()
+    ids = [int(k) for k in series_ids]
+    if len(ids) != B:
+        raise ValueError("series_ids names %d series, the batch has %d" % (len(ids), B))
+    bad = [k for k in ids if not 0 <= k < MAX_SERIES_ID]
+    if bad:
+        raise ValueError("series id %d outside 0 .. 2^24 - 1" % bad[0])
+    return torch.tensor(ids, dtype=torch.int64).to(device)
+
+
+def _sample_count(num_samples):
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError("num_samples must be at least 1, got %d" % S)
+    return S
+
+
+def _perturbation_seg(ts, G, plan, ids, hsource, hterm, rows, v, S, seed, stream):
+    """rhs [R, d, S] of cgps_leg_perturbation_seg; contiguous operands of G's dtype on G's device.  With
+    ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series and local row."""
+    R, d, dt = plan.R, G.shape[0], G.dtype
+    out = torch.empty(R, d, S, dtype=dt, device=G.device)
+    info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    entries = hterm.shape[0] if hsource == _hip.H_TABLE else 0
+    obs = hterm.shape[-1] if hsource != _hip.H_NONE else 0
+    _hip.check(_hip.lib().cgps_leg_perturbation_seg(
+        _hip.ptr(ts), R, _hip.ptr(G), d, _hip.dtype_code(dt), _hip.ptr(plan.offsets), _hip.ptr(ids), plan.B, hsource,
+        _hip.ptr(hterm), entries, obs, _hip.ptr(rows), _hip.ptr(v), S, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        int(stream) & 0xFFFFFFFF, _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = int(info.item())
+        if bad:
+            b, r = _series_of_row(plan, bad - 1)
+            raise cr.NotPSDError("LEG batch: series %d: the time gap next to its row %d is singular (zero-length gap?)" % (b, r))
+    return out
+
+
+def _posterior_perturbation_flat(m, ts, xs, observed, noise_var, plan, ids, S, seed, stream):
+    """(K_Rs, K_Os, rhs [R, d, S]) of the concatenated batch (already validated, on the GPU)."""
+    K_Rs, K_Os, v = _posterior_system_batch(m, ts, xs, observed, noise_var, plan)
+    dt = K_Rs.dtype
+    if noise_var is not None:
+        hsource, rows = _hip.H_ROWS, None
+    elif observed is not None:
+        bits = 1 << torch.arange(observed.shape[1], device=observed.device)
+        hsource, rows = _hip.H_TABLE, (observed * bits).sum(1).to(torch.uint8)       # observation_tables' pattern byte
+    else:
+        hsource, rows = _hip.H_PLAIN, None
+    hterm = observation_noise_factors(m, observed, noise_var).to(dt).contiguous()
+    rhs = _perturbation_seg(ts.to(dt).contiguous(), m.G.contiguous(), plan, ids, hsource, hterm, rows, v, S, seed, stream)
+    return K_Rs, K_Os, rhs
+
+
+def _solve_columns(K_Rs, K_Os, rhs, plan):
+    """K^-1 rhs [R, d, S]: one factorisation, the right-hand sides in column chunks (a column never depends on the
+    chunking: the solve treats its columns independently)."""
+    try:
+        dec = cr.decompose(K_Rs, K_Os)
+    except cr.NotPSDError as e:
+        row = getattr(e, "row", None)
+        if row is None:
+            raise
+        b, r = _series_of_row(plan, row)
+        raise cr.NotPSDError("LEG batch: series %d: a block near its row %d is not positive definite" % (b, r)) from None
+    S, chunk = rhs.shape[2], _sample_column_chunk(rhs.shape[1])
+    if S <= chunk:
+        return cr.solve(dec, rhs)
+    x = torch.empty_like(rhs)
+    for c in range(0, S, chunk):
+        x[:, :, c:c + chunk] = cr.solve(dec, rhs[:, :, c:c + chunk])
+    return x
+
+
+def _on_gpu(m, *tensors):
+    """The model and the tensors on the GPU the kernels run on (there is no CPU implementation)."""
+    dev = m.N.device if m.N.is_cuda else cr._device()
+    return (m if m.N.is_cuda else m.to(dev),) + tuple(None if t is None else t.to(dev) for t in tensors)
+
+
+def _perturbation_call(m, ts, xs, num_samples, seed, lengths, observed, noise_var, series_ids, stream, solve):
+    like = ts
+    ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+    S = _sample_count(num_samples)
+    d, obs, dt = m.N.shape[0], m.B.shape[0], m.N.dtype
+    if not 1 <= d <= 8 or dt not in (torch.float32, torch.float64) or obs > MAX_PATTERN_OBS:
+        raise ValueError("batched sampling is built for rank 1..8, obs_dim <= 8, float32 / float64")
+    if not lengths:
+        _series_ids_arg(series_ids, lengths, d, obs, "cpu")
+        return torch.empty(((0, bn[1], d, S) if dense else (0, d, S)), dtype=dt, device=like.device)
+    m, ts, xs, observed, noise_var = _on_gpu(m, ts, xs, observed, noise_var)
+    ids = _series_ids_arg(series_ids, lengths, d, obs, m.N.device)
+    plan = _cached_batch_plan(lengths, m.N.device)
+    K_Rs, K_Os, out = _posterior_perturbation_flat(m, ts, xs, observed, noise_var, plan, ids, S, seed, stream)
+    if solve:
+        out = _solve_columns(K_Rs, K_Os, out, plan)
+    out = cr._back(out, like)
+    return out.reshape(bn[0], bn[1], d, S) if dense else out
+
+
+def posterior_perturbation_batch(m, ts, xs, num_samples, seed, lengths=None, observed=None, noise_var=None,
+                                 series_ids=None, stream=0):
+    """The right-hand sides of ``sample_from_posterior_batch``: rhs = v + w with w ~ N(0, K), K the concatenated
+    posterior precision of the batch (``insample_posterior_batch``'s system) and v its right-hand side, so that
+    K^-1 rhs[:, :, s] is a posterior draw.  One kernel (cgps_leg_perturbation_seg) makes every row of every series and
+    sample; the noise is generated in registers.  Arguments as ``sample_from_posterior_batch``; returns [B, n, rank, S]
+    (dense) or [R, rank, S] (ragged).  For a caller with a factor of K of their own.
+
+    Series b's rows depend only on (seed, stream, series_ids[b], its own ts / xs / observed / noise_var, the column s)
+    -- bitwise: not on the series' position in the batch, on the other series, on the layout or on num_samples."""
+    with torch.no_grad():
+        return _perturbation_call(m, ts, xs, num_samples, seed, lengths, observed, noise_var, series_ids, stream, False)
+
+
+def sample_from_posterior_batch(m, ts, xs, num_samples, seed, lengths=None, observed=None, noise_var=None,
+                                series_ids=None, stream=0):
+    """num_samples latent paths from the posterior of each of B independent series, in one call: [B, n, rank, S]
+    (dense) or [R, rank, S] (ragged).  Layouts, ``lengths``, ``observed`` and ``noise_var``: exactly those of
+    ``insample_posterior_batch`` (paths run through every row, observed or not; what xs and noise_var hold at unobserved
+    entries is ignored, NaN included).  ``series_ids``: B integers in 0 .. 2^24 - 1 (a list or an integer tensor; read
+    on the host), default 0 .. B-1, that name the series to the noise generator -- give a series the id it has in the
+    whole data set and its draws are the same in every batch it appears in; two series with one id share their noise.
+    ``stream``: the generator's stream word; the latent noise uses ``stream``, the observation noise ``stream + 1``.
+    A series of n rows needs n max(rank, obs_dim) < 2^40.  No autograd graph.  B = 0 returns an empty tensor.  Every
+    ValueError is raised before anything is launched.
+
+    What is guaranteed.  The DISTRIBUTION is that of ``sample_from_posterior`` series by series, N(K_b^-1 v_b,
+    K_b^-1), independent across series with different ids.  The NUMBERS are not those of ``sample_from_posterior``:
+    that draws mean + (factor)^T eps off the cyclic-reduction factor, this is another sampler, perturb and solve:
+    x = K^-1 (v + w) with w ~ N(0, K) summed from local pieces of noise.  The draw of a series depends
+    only on (seed, stream, its id, its data, s): not on its position in the batch, on the other series, on the layout
+    or on num_samples -- bitwise on the right-hand side (``posterior_perturbation_batch``), to the accuracy of the solve
+    on the draw itself.  There is no per-series fallback to ``sample_from_posterior``.
+
+    How: ``_posterior_system_batch`` (one assembly launch), one cgps_leg_perturbation_seg launch for the right-hand
+    sides, ONE ``cr.decompose`` and ``cr.solve`` on column chunks of at most ``_sample_column_chunk(rank)`` columns.  A
+    repeated call with the same lengths and default ids copies nothing from the host.  With
+    ``cr.CHECK_POSITIVE_DEFINITE`` a zero-length gap or a block that is not positive definite raises ``cr.NotPSDError``
+    naming the series and its local row.  CPU tensors: the work still runs on the GPU (there is no CPU implementation)
+    and the result comes back to the CPU."""
+    with torch.no_grad():
+        return _perturbation_call(m, ts, xs, num_samples, seed, lengths, observed, noise_var, series_ids, stream, True)
+
+
+def sample_from_prior_batch(m, ts, num_samples, seed, lengths=None, series_ids=None, stream=0):
+    """num_samples latent paths of the LEG process at each of B independent series' times: ts [B, n] -> [B, n, rank, S],
+    or ts [R] with host ``lengths`` -> [R, rank, S].  ``sample_from_posterior_batch`` without data: K is the prior
+    precision (cgps_peg_precision_seg), there is no v and no observation noise.  ``series_ids``, ``stream`` and the
+    guarantee as there: the distribution is ``sample_from_prior``'s latent paths series by series, the numbers are not,
+    and a series' draw depends only on (seed, stream, its id, its times, s).  No autograd graph."""
+    with torch.no_grad():
+        like = ts
+        dense = lengths is None
+        shape = tuple(ts.shape)
+        ts, _, lengths = _batch_layout(ts, ts.new_zeros(shape + (1,)) if dense else ts.new_zeros(shape[0] if shape else 0, 1),
+                                       lengths)
+        S = _sample_count(num_samples)
+        d, dt = m.N.shape[0], m.N.dtype
+        if not 1 <= d <= 8 or dt not in (torch.float32, torch.float64):
+            raise ValueError("batched sampling is built for rank 1..8, float32 / float64")
+        if not lengths:
+            _series_ids_arg(series_ids, lengths, d, 1, "cpu")
+            return torch.empty(((0, shape[1], d, S) if dense else (0, d, S)), dtype=dt, device=like.device)
+        m, ts = _on_gpu(m, ts)
+        ids = _series_ids_arg(series_ids, lengths, d, 1, m.N.device)
+        plan = _cached_batch_plan(lengths, m.N.device)
+        tsc, G = ts.to(dt).contiguous(), m.G.contiguous()
+        rhs = _perturbation_seg(tsc, G, plan, ids, _hip.H_NONE, None, None, None, S, seed, stream)   # (names a singular gap)
+        Rs, Os = _peg_precision_seg(tsc, G, plan.cut)
+        out = cr._back(_solve_columns(Rs, Os, rhs, plan), like)
+        return out.reshape(shape + (d, S)) if dense else out
 
 
 # ---- the config-5 workload -----------------------------------------------------------------

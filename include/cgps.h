@@ -447,6 +447,35 @@ int cgps_leg_intercast_models(const void* ts, const int64_t* row_offsets, const 
                               int dtype, const void* ip_mean, const void* ip_cov_diag, const void* ip_cov_offdiag,
                               void* out_mean, void* out_cov, void* stream);
 
+/* Perturb and solve: the right-hand sides of draws from the posterior (or prior) of B concatenated LEG series.
+ * K = J_prior + blockdiag(B^T Li_i B) (cgps_leg_posterior_blocks_seg; cgps_peg_precision_seg for the prior) is a sum of
+ * local positive semi-definite pieces, so noise w ~ N(0, K) is a sum of local pieces, and  x = K^-1 (v + w)  is a draw
+ * from N(K^-1 v, K^-1).  This call writes out[R][d][nrhs] = v + w; the caller solves (cgps_solve on K's factor).
+ * Series b is rows row_offsets[b] .. row_offsets[b+1]-1 (local rows r = 0 .. n_b - 1) and has the caller's number
+ * k_b = series_ids[b], 0 <= k_b < 2^24; n_b max(d, obs) < 2^40.  Both arrays are int64 DEVICE memory (B + 1 and B
+ * entries); the caller checks the two ranges.  With E_r = exp(-1/2 (t_{r+1} - t_r) G), I - E_r E_r^T = L_r L_r^T
+ * (evaluated as the assembly evaluates it, never across a series boundary) and u_r = L_r^-T eps_{r+1}:
+ *     w_r = (r == 0 ? eps_0 : u_{r-1}) - (r + 1 < n_b ? E_r^T u_r : 0) + H_r eps'_r
+ * eps_r[i], column s  = element (k_b 2^40 + r d + i, s) of cgps_normal_fill's generator, key seed, stream word stream_id;
+ * eps'_r[c], column s = element (k_b 2^40 + r obs + c, s), stream word stream_id + 1.
+ * H_r [d][obs] with H_r H_r^T = B^T Li_r B comes from
+ *   hsource = CGPS_H_NONE:  nothing (the prior; hterm, entries, obs and rows are not read);
+ *             CGPS_H_PLAIN: hterm[d][obs] for every row;
+ *             CGPS_H_TABLE: hterm[min(rows[i], entries - 1)] of hterm[entries][d][obs], rows = pattern bytes [R],
+ *                           1 <= entries <= 256;
+ *             CGPS_H_ROWS:  hterm[i] of hterm[R][d][obs].
+ * v[R][d] may be NULL (zero).  A row's values depend only on (seed, stream_id, k_b, r, the series' time stamps and
+ * H_r, v_r, the column): not on the series' position, the rest of the batch, nrhs or the launch geometry, bit for bit.
+ * info: 0, or 1 + a row of the concatenated batch next to a singular (zero-length) gap.  One lane per row; no
+ * workspace.  Built for every d in 1..8 in both precisions, 1 <= obs <= 8.  B < 0, R < 0, nrhs < 1, a null pointer, an
+ * unknown hsource, obs or entries outside their ranges: CGPS_ERR_ARG before anything is launched; B = 0 or R = 0:
+ * CGPS_OK, nothing launched; d outside 1..8 or an unknown dtype: CGPS_ERR_UNSUPPORTED. */
+enum { CGPS_H_NONE = 0, CGPS_H_PLAIN = 1, CGPS_H_TABLE = 2, CGPS_H_ROWS = 3 };
+int cgps_leg_perturbation_seg(const void* ts, int64_t R, const void* G, int d, int dtype, const int64_t* row_offsets,
+                              const int64_t* series_ids, int64_t B, int hsource, const void* hterm, int entries, int obs,
+                              const unsigned char* rows, const void* v, int64_t nrhs, uint64_t seed, uint32_t stream_id,
+                              void* out, int* info, void* stream);
+
 /* ---- time-axis sharding (one shard per GPU / rank) -----------------------------------------
  * The reference has no distributed code; this is the multi-GPU form BASELINE.json asks for.
  * A shard is n_loc consecutive block rows: Rs[n_loc], Os[n_loc-1] (couplings INSIDE the shard),
