@@ -4,11 +4,13 @@
 // of their own: every row adds a weighted sum of a basis shared by all rows (chunk_reduce_kernel<.., SRC = 3>; for many
 // series in one launch leg_batch_kernel<.., LEG_ROWS_WEIGHTED>).  Both for M models over the same batch as well
 // (LEG_ROWS_MODELS_TABLE, LEG_ROWS_MODELS_WEIGHTED: grid (B, 2, M)).
+// The leave-one-out predictives of such series from their posterior (cgps_leg_loo: cgps_leg_loo.h) live here too.
 // A translation unit of its own: these are the heaviest stage-1 instantiations of the library and compile next to
 // cgps_mahal.hip, not after it.
 #include "cgps_host.h"
 #include "cgps_tile.h"
 #include "cgps_tile_leg_batch.h"
+#include "cgps_leg_loo.h"
 
 using namespace cgps_host;
 
@@ -85,6 +87,32 @@ int cgps_leg_loglik_models_w(const void* ts, const int64_t* offsets, int64_t B, 
   return leg_rows_entry<cgps::LEG_ROWS_MODELS_WEIGHTED>(
       "cgps_leg_loglik_models_w", "LEG batched reduction (models, per-row weighted basis)", !basis || !weights, ts, offsets, B,
       R, M, G, basis, Kb, weights, v, q, d, dtype, max_rows, out4, info2, stream);
+}
+
+int cgps_leg_loo(const void* xs, const uint8_t* pattern, const void* noise_var, const int64_t* row_offsets, int64_t B,
+                 int64_t R, int64_t M, const void* Bmat, const void* LLT, int d, int obs, int dtype, const void* ip_mean,
+                 const void* ip_cov_diag, int leave, void* out_mean, void* out_var, void* out_logpdf, double* out_score,
+                 int* info, void* stream) {
+  if (B < 0 || R < 0) return fail(CGPS_ERR_ARG, "cgps_leg_loo: B = %lld series, R = %lld rows", (long long)B, (long long)R);
+  if (M < 1 || M > 65535) return fail(CGPS_ERR_ARG, "cgps_leg_loo: M = %lld models, outside 1..65535", (long long)M);
+  if (leave != cgps::LOO_ENTRY && leave != cgps::LOO_ROW)
+    return fail(CGPS_ERR_ARG, "cgps_leg_loo: leave = %d, neither 0 (entry) nor 1 (row)", leave);
+  if (obs < 1 || obs > 8) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_loo: obs = %d outside 1..8", obs);
+  if (dtype != CGPS_F32 && dtype != CGPS_F64) return fail(CGPS_ERR_UNSUPPORTED, "dtype %d not supported", dtype);
+  if (d < 1 || d > 8) return fail(CGPS_ERR_UNSUPPORTED, "block size d=%d outside 1..8", d);
+  if (R == 0 || B == 0) return CGPS_OK;
+  if (!xs || !row_offsets || !Bmat || !LLT || !ip_mean || !ip_cov_diag || !out_mean || !out_var || !out_logpdf ||
+      !out_score || !info)
+    return fail(CGPS_ERR_ARG, "cgps_leg_loo: null pointer");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    (void)hipMemsetAsync(info, 0, sizeof(int), (hipStream_t)stream);
+    cgps::launch_loo<T, D>((const T*)xs, pattern, (const T*)noise_var, row_offsets, B, R, M, (const T*)Bmat, (const T*)LLT,
+                           obs, (const T*)ip_mean, (const T*)ip_cov_diag, leave, (T*)out_mean, (T*)out_var, (T*)out_logpdf,
+                           out_score, info, (hipStream_t)stream);
+    return check_launch("LEG leave-one-out predictives");
+  });
 }
 
 }  // extern "C"

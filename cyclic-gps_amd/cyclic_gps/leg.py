@@ -15,6 +15,7 @@ The d x d assembly (matrix exponentials, two small solves per time gap) is embar
 parallel batched device work done with torch ops; everything block-tridiagonal goes through
 cyclic_gps.cyclic_reduction, i.e. the HIP kernels.  Tensors follow the device of `ts`.
 """
+import collections
 import math
 import os
 
@@ -2030,6 +2031,223 @@ def insample_posterior_models(ms, ts, xs, lengths=None, observed=None, noise_var
         if dense:
             return mean.view(M, B, n, d), (Sd.view(M, B, n, d, d), So)
         return mean, (Sd, So)
+
+
+# ---- leave-one-out predictives -----------------------------------------------------------------------------------
+# How well a fitted model explains the data it was fitted to, point by point: the distribution of every observation given
+# all the others.  Nothing is refitted: with (mu_i, S_ii) the posterior of row i's latent, Li_i = M W_i^-1 M the row's
+# noise precision on its observed channels (``observation_weights``) and x~ the data with zeros where nothing is
+# observed,  g_i = Li_i M (x~_i - B mu_i)  and  P_i = Li_i - Li_i (B S_ii B^T) Li_i  are the row's block of P x and of P,
+# P the precision of the marginal Gaussian of ALL observed entries (Woodbury), and a Gaussian's conditionals are read off
+# its precision.  cgps_leg_loo evaluates that for every row of every series under every model.
+LooPredictive = collections.namedtuple("LooPredictive", ["mean", "var", "logpdf", "score"])
+_LEAVE = {"entry": 0, "row": 1}
+
+
+def _loo_leave(leave, obs):
+    if leave not in _LEAVE:
+        raise ValueError("leave must be 'entry' or 'row', got %r" % (leave,))
+    if obs > MAX_PATTERN_OBS:
+        raise ValueError("observation patterns are tabulated for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, obs))
+    return _LEAVE[leave]
+
+
+def _loo_data(xs, observed, noise_var, dt):
+    """The data as cgps_leg_loo reads it: (xs [R, obs] of the models' dtype, pattern bytes [R] or None, noise_var
+    [R, obs] or None), contiguous."""
+    obs = xs.shape[1]
+    pattern = None
+    if observed is not None:
+        pattern = (observed * (1 << torch.arange(obs, device=observed.device))).sum(1).to(torch.uint8).contiguous()
+    if noise_var is not None:
+        noise_var = noise_var.to(dt)
+        if noise_var.dim() == 1:
+            noise_var = noise_var.unsqueeze(-1).expand(-1, obs)
+        noise_var = noise_var.contiguous()
+    return xs.to(dt).contiguous(), pattern, noise_var
+
+
+def _loo_rows(xs, pattern, noise_var, offsets, Bm, LLT, mean, Sd, leave):
+    """cgps_leg_loo on a given posterior: xs [R, obs], pattern uint8 [R] or None, noise_var [R, obs] or None, offsets
+    device int64 [B + 1] (shared by the models), Bm [M, obs, d], LLT [M, obs, obs], mean [M R, d] and Sd [M R, d, d] (the
+    rows of ``_posterior_models_chunks``; M = 1: those of one batch), leave 0 (entry) or 1 (row), all contiguous and of
+    one dtype.  Returns (mean [M, R, obs], var [M, R, obs] or [M, R, obs, obs], logpdf [M, R, obs] or [M, R], score
+    [M, B] fp64, info int32 [1]: 0 or 1 + the smallest failing row of the M R).  Nothing is read on the host."""
+    if not (xs.is_cuda and mean.is_cuda and Sd.is_cuda and Bm.is_cuda):
+        raise _hip.CgpsError("leave-one-out predictives run on the GPU (there is no CPU implementation)")
+    M, obs, d = Bm.shape
+    R, B, dt, dev = xs.shape[0], offsets.shape[0] - 1, mean.dtype, mean.device
+    assert tuple(mean.shape) == (M * R, d) and tuple(Sd.shape) == (M * R, d, d) and tuple(LLT.shape) == (M, obs, obs)
+    assert tuple(xs.shape) == (R, obs) and all(t.dtype == dt for t in (xs, Bm, LLT, Sd))
+    assert pattern is None or (pattern.dtype == torch.uint8 and tuple(pattern.shape) == (R,))
+    assert noise_var is None or (noise_var.dtype == dt and tuple(noise_var.shape) == (R, obs))
+    assert offsets.dtype == torch.int64 and offsets.is_cuda
+    row = leave == _LEAVE["row"]
+    out_mean = torch.empty(M, R, obs, dtype=dt, device=dev)
+    out_var = torch.empty((M, R, obs, obs) if row else (M, R, obs), dtype=dt, device=dev)
+    out_lp = torch.empty((M, R) if row else (M, R, obs), dtype=dt, device=dev)
+    score = torch.zeros(M, B, dtype=torch.float64, device=dev)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    c = lambda t: None if t is None else t.contiguous()      # noqa: E731
+    xs, pattern, noise_var, Bm, LLT, mean, Sd = (c(t) for t in (xs, pattern, noise_var, Bm, LLT, mean, Sd))
+    _hip.check(_hip.lib().cgps_leg_loo(
+        _hip.ptr(xs), _hip.ptr(pattern), _hip.ptr(noise_var), _hip.ptr(offsets), B, R, M, _hip.ptr(Bm), _hip.ptr(LLT), d, obs,
+        _hip.dtype_code(dt), _hip.ptr(mean), _hip.ptr(Sd), leave, _hip.ptr(out_mean), _hip.ptr(out_var), _hip.ptr(out_lp),
+        _hip.ptr(score), _hip.ptr(info), _hip.stream_ptr()))
+    return out_mean, out_var, out_lp, score, info
+
+
+_LOO_FAILED = ("its leave-one-out precision is not positive definite (the posterior failed, or the noise of the row is "
+               "indefinite)")
+
+
+def _loo_empty(lead, obs, leave, dt, device):
+    """Empty results with the leading dimensions ``lead`` (the last of them the empty one) in front of the row axes."""
+    e = lambda *shape: torch.empty(lead + shape, dtype=dt, device=device)      # noqa: E731
+    return e(obs), (e(obs, obs) if leave else e(obs)), (e() if leave else e(obs))
+
+
+def loo_predictive(m, ts, xs, observed=None, noise_var=None, leave="entry"):
+    """Leave-one-out predictives of one series under a fitted model: ``LooPredictive(mean, var, logpdf, score)``.
+
+    ``leave="entry"``: for every observed entry (i, c), the Gaussian of x_ic given every OTHER observed entry of the
+    series, the other channels of row i included: mean, var and logpdf (the log density of the value that was seen), each
+    [n, obs_dim].  ``leave="row"``: for every row, the Gaussian of its observed channels given all other ROWS: mean
+    [n, obs_dim], var the covariance [n, obs_dim, obs_dim], logpdf [n].  ``score`` = sum of logpdf, a 0-d fp64 tensor:
+    the LOO-CV score of Rasmussen & Williams 5.4.2.  (x - mean) / sqrt(var) are the standardised residuals.  For
+    obs_dim = 1 the two coincide.  An unobserved entry has mean = var = NaN (row mode: its row and column of var) and
+    logpdf 0; a row that observes nothing has logpdf 0.  ``observed`` and ``noise_var`` as in ``log_likelihood``; what xs
+    and noise_var hold at unobserved entries is ignored, NaN included.
+
+    Nothing is refitted: all n obs_dim predictives follow from ONE ``insample_posterior`` and a few obs_dim x obs_dim
+    operations per row (cgps_leg_loo).  An evaluation from the posterior loses the factor
+    kappa = var_loo / (the entry's noise variance) in relative accuracy, which no formulation from (mu_i, S_ii) avoids.
+    Inference only: runs under ``torch.no_grad``.  obs_dim <= 8.  With ``cr.CHECK_POSITIVE_DEFINITE`` a row whose
+    predictive does not exist raises ``cr.NotPSDError`` naming it; with the check off its results are NaN.  CPU tensors
+    behave as ``insample_posterior`` does (there is no CPU implementation)."""
+    with torch.no_grad():
+        obs = m.B.shape[0]
+        lv = _loo_leave(leave, obs)
+        if ts.dim() != 1 or xs.dim() != 2 or xs.shape[0] != ts.shape[0] or xs.shape[1] != obs:
+            raise ValueError("one series wants ts[n] and xs[n, %d], got %s and %s" % (obs, tuple(ts.shape), tuple(xs.shape)))
+        n, dt = ts.shape[0], m.N.dtype
+        if observed is not None:
+            observed = _observed_2d(observed, obs)
+            if observed.shape[0] != n:
+                raise ValueError("observed has %d rows, xs has %d" % (observed.shape[0], n))
+        if noise_var is not None:
+            if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
+                raise ValueError("noise_var must be a floating-point tensor")
+            if noise_var.dim() not in (1, 2) or noise_var.shape[0] != n or (noise_var.dim() == 2 and noise_var.shape[1] != obs):
+                raise ValueError("noise_var must be [n] or [n, %d], got %s" % (obs, tuple(noise_var.shape)))
+        if n == 0:
+            return LooPredictive(*_loo_empty((0,), obs, lv, dt, ts.device),
+                                 torch.zeros((), dtype=torch.float64, device=ts.device))
+        mean, (Sd, _) = insample_posterior(m, ts, xs, observed, noise_var)
+        offsets = _cached_batch_plan([n], m.N.device).offsets
+        xs_c, pattern, nv = _loo_data(xs, observed, noise_var, dt)
+        om, ov, ol, score, info = _loo_rows(xs_c, pattern, nv, offsets, m.B.unsqueeze(0).contiguous(), m.LLT.unsqueeze(0),
+                                            mean.contiguous(), Sd.contiguous(), lv)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            bad = int(info.item())
+            if bad:
+                raise cr.NotPSDError("LEG leave-one-out: row %d: %s" % (bad - 1, _LOO_FAILED))
+        return LooPredictive(om[0], ov[0], ol[0], score[0, 0])
+
+
+def loo_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None, leave="entry"):
+    """``loo_predictive`` of B independent series in one call: ``LooPredictive(mean, var, logpdf, score)`` with
+    ``score`` [B] (fp64), the LOO-CV score of every series.
+
+    Layouts, ``lengths``, ``observed`` and ``noise_var``: those of ``insample_posterior_batch``, with its checks and
+    ValueErrors, raised before anything is launched.  Dense (``lengths=None``): mean and, for ``leave="entry"``, var and
+    logpdf are [B, n, obs_dim]; for ``leave="row"`` var is [B, n, obs_dim, obs_dim] and logpdf [B, n].  Ragged: the same
+    with the leading [R] of the concatenated rows.  B = 0 returns empty tensors.
+
+    How: the posterior of the concatenated batch (``insample_posterior_batch``'s ONE ``cr.decompose_solve`` and ONE
+    ``cr.inverse_blocks``), then ONE cgps_leg_loo: one lane per row, then one workgroup per series that adds the
+    series' log densities in a fixed order, so that a series' score does not depend on its place in the batch.
+
+    Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a failed posterior raises as ``insample_posterior_batch`` does, and a
+    row whose predictive does not exist (its P not positive definite: indefinite noise, a negative ``noise_var``) raises
+    ``cr.NotPSDError`` naming the series and its local row; with the check off the row's results and its series' score
+    are NaN.  CPU tensors, or a rank or dtype outside the kernels', behave as ``insample_posterior_batch`` does (there is
+    no CPU implementation)."""
+    with torch.no_grad():
+        obs = m.B.shape[0]
+        lv = _loo_leave(leave, obs)
+        ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        dt = m.N.dtype
+        if not lengths:
+            lead = (0, bn[1]) if dense else (0,)
+            return LooPredictive(*_loo_empty(lead, obs, lv, dt, ts.device), torch.empty(0, dtype=torch.float64, device=ts.device))
+        mean, Sd, _ = _posterior_flat(m, ts, xs, lengths, observed, noise_var)
+        plan = _cached_batch_plan(lengths, m.N.device)
+        xs_c, pattern, nv = _loo_data(xs, observed, noise_var, dt)
+        om, ov, ol, score, info = _loo_rows(xs_c, pattern, nv, plan.offsets, m.B.unsqueeze(0).contiguous(), m.LLT.unsqueeze(0),
+                                            mean.contiguous(), Sd.contiguous(), lv)
+        if cr.CHECK_POSITIVE_DEFINITE:
+            bad = int(info.item())
+            if bad:
+                b, r = _series_of_row(plan, bad - 1)
+                raise cr.NotPSDError("LEG leave-one-out: series %d: row %d: %s" % (b, r, _LOO_FAILED))
+        om, ov, ol = om[0], ov[0], ol[0]
+        if dense:
+            om, ov, ol = (t.reshape(bn + tuple(t.shape[1:])) for t in (om, ov, ol))
+        return LooPredictive(om, ov, ol, score[0])
+
+
+def loo_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=None, leave="entry"):
+    """``loo_predictive_batch`` of M LEG models for the same B series in one call: slot k of every result is
+    ``loo_predictive_batch(ms[k], ...)``, and ``score`` [M, B] (fp64) is the LOO-CV score of every model on every series
+    -- the number that ranks restarts, chains, grid points or mixture components by held-out fit without holding
+    anything out.
+
+    ``ms``, ``ts`` / ``xs`` / ``lengths``, ``observed`` and ``noise_var``: exactly those of ``insample_posterior_models``,
+    with its ValueErrors, raised before anything is launched; the mask and the variances belong to the data and are
+    shared by all models.  Dense: [M, B, n, ...]; ragged: [M, R, ...]; an empty batch gives empty tensors with leading
+    dimension M.
+
+    How: ``insample_posterior_models``' chunks of whole models (MODELS_POSTERIOR_MAX_ROWS), each consumed by ONE
+    cgps_leg_loo (grid over rows and models) as soon as it exists: only the LOO outputs are kept, the [M, R, d, d]
+    covariance blocks of all models are never held at once.
+
+    Failures: with ``cr.CHECK_POSITIVE_DEFINITE``, as ``insample_posterior_models`` for the posterior, and a row whose
+    predictive does not exist raises ``cr.NotPSDError`` naming the model, the series and its local row.  CPU tensors, or a
+    rank or dtype outside the kernels', take one ``loo_predictive_batch`` per model."""
+    with torch.no_grad():
+        ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
+                                                                                          noise_var)
+        M, obs, dt = len(ms), mats[2].shape[1], mats[0].dtype
+        lv = _loo_leave(leave, obs)
+        if not lengths:
+            lead = (M, 0, bn[1]) if dense else (M, 0)
+            return LooPredictive(*_loo_empty(lead, obs, lv, dt, ts.device),
+                                 torch.empty(M, 0, dtype=torch.float64, device=ts.device))
+        if not _posterior_batch_supported(ts, mats[0][0]):
+            outs = _posterior_models_per_model(
+                ms, lambda m: loo_predictive_batch(m, ts, xs, lengths, observed, noise_var, leave))
+            om, ov, ol, score = (torch.stack([o[j] for o in outs]) for j in range(4))
+        else:
+            plan = _cached_batch_plan(lengths, mats[0].device)
+            G, source, term, rows, v = _models_posterior_operands(mats, xs, observed, noise_var)
+            Bm = mats[2].contiguous()
+            LLT = (_contract(mats[3], mats[3].transpose(1, 2)) + _scaled_eye(obs, 1e-9, dt, Bm.device)).contiguous()
+            xs_c, pattern, nv = _loo_data(xs, observed, noise_var, dt)
+            parts = []
+            for k0, k1, mean_c, Sd_c, _ in _posterior_models_chunks(plan, ts.to(dt).contiguous(), G, source, term, rows, v):
+                out = _loo_rows(xs_c, pattern, nv, plan.offsets, Bm[k0:k1], LLT[k0:k1], mean_c, Sd_c, lv)
+                del mean_c, Sd_c
+                if cr.CHECK_POSITIVE_DEFINITE:
+                    bad = int(out[4].item())
+                    if bad:
+                        k, b, r = _models_row(plan, bad - 1)
+                        raise cr.NotPSDError("LEG leave-one-out: model %d, series %d: row %d: %s" % (k0 + k, b, r, _LOO_FAILED))
+                parts.append(out[:4])
+            om, ov, ol, score = (parts[0][j] if len(parts) == 1 else torch.cat([p[j] for p in parts]) for j in range(4))
+        if dense:
+            om, ov, ol = (t.reshape((M,) + bn + tuple(t.shape[2:])) for t in (om, ov, ol))
+        return LooPredictive(om, ov, ol, score)
 
 
 # ---- drawing from the process -----------------------------------------------------------------------

@@ -476,6 +476,34 @@ int cgps_leg_perturbation_seg(const void* ts, int64_t R, const void* G, int d, i
                               const unsigned char* rows, const void* v, int64_t nrhs, uint64_t seed, uint32_t stream_id,
                               void* out, int* info, void* stream);
 
+/* Leave-one-out predictives of B concatenated LEG series under M models, from the posterior of the latent
+ * (cgps_decompose_solve + cgps_inverse_blocks of cgps_leg_posterior_blocks_seg / _models' system): one lane per
+ * (row, model), grid (ceil(R / 256), M), then one workgroup per (model, series) for the scores, in the same call.
+ * xs[R][obs], pattern[R] (bit c set: channel c of the row is observed; NULL: everything is), noise_var[R][obs] (extra
+ * variances s of the observed entries; NULL: none) and row_offsets[B+1] (int64 DEVICE memory, row_offsets[B] = R)
+ * describe the data once and are shared by the models; xs and noise_var are never read at an unobserved entry.  Model k
+ * brings Bmat[k] of Bmat[M][obs][d], LLT[k] of LLT[M][obs][obs] (Lambda Lambda^T + 1e-9 I) and rows k R .. (k+1) R - 1
+ * of ip_mean[M R][d] and ip_cov_diag[M R][d][d].  With m = diag(pattern bits), W = m (LLT + diag(s)) m + (I - m),
+ * Li = m W^-1 m, x~ = xs where observed and 0 elsewhere, and (mu, S) the row's posterior:
+ *     g = Li m (x~ - Bmat mu),   P = Li - Li (Bmat S Bmat^T) Li
+ * (the row's block of the precision of all observed entries, and of that precision times the data), and
+ *   leave = 0 (entry), per observed (row, c): out_var = 1 / P[c][c], out_mean = x_c - g_c / P[c][c],
+ *       out_logpdf = -1/2 g_c^2 / P[c][c] + 1/2 log P[c][c] - 1/2 log 2 pi;  out_mean, out_var, out_logpdf [M][R][obs];
+ *   leave = 1 (row), o the row's k observed channels: out_var = cov = (P[o][o])^-1 scattered into [M][R][obs][obs],
+ *       out_mean = x_o - cov g_o [M][R][obs], out_logpdf = -1/2 g_o^T cov g_o + 1/2 log|P[o][o]| - k/2 log 2 pi [M][R].
+ * An unobserved entry gets mean = var = NaN (row mode: its row and column of cov) and logpdf 0; a row that observes
+ * nothing has logpdf 0.  out_score[M][B] (double): the sum of series b's log densities under model k, added in a fixed
+ * order that depends on the series' own rows only (no atomics): a score does not depend on the series' place in the
+ * batch.  A pivot of W or of P[o][o], or a P[c][c], that is not positive and finite fails the row: its outputs are NaN
+ * (its series' score too) and info holds 1 + the smallest failing k R + i, else 0.  Built for every d in 1..8 and
+ * obs in 1..8 in both precisions.  B < 0, R < 0, M outside 1..65535, leave outside {0, 1} or a null pointer with work
+ * to do: CGPS_ERR_ARG; d or obs outside 1..8 or an unknown dtype: CGPS_ERR_UNSUPPORTED; B = 0 or R = 0: CGPS_OK,
+ * nothing launched.  No workspace. */
+int cgps_leg_loo(const void* xs, const uint8_t* pattern, const void* noise_var, const int64_t* row_offsets, int64_t B,
+                 int64_t R, int64_t M, const void* Bmat, const void* LLT, int d, int obs, int dtype, const void* ip_mean,
+                 const void* ip_cov_diag, int leave, void* out_mean, void* out_var, void* out_logpdf, double* out_score,
+                 int* info, void* stream);
+
 /* ---- time-axis sharding (one shard per GPU / rank) -----------------------------------------
  * The reference has no distributed code; this is the multi-GPU form BASELINE.json asks for.
  * A shard is n_loc consecutive block rows: Rs[n_loc], Os[n_loc-1] (couplings INSIDE the shard),
