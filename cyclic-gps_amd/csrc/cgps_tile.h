@@ -27,7 +27,8 @@
 //    (fold_record_stages): the workgroup of a group of 16 tiles that arrives last reduces the
 //    group's records with the same tile_cr, the group leader that arrives last reduces the
 //    group records, eliminates the final row, sums the partial log-det / mahal in a fixed order
-//    and writes the info word (or leaves a shard's single record).  Beyond 1024 stage-1
+//    and writes the info word (or leaves a shard's single record).  4 x 4 fp64 blocks, at most 256
+//    tiles: each of the two stages in the registers of one wave, no LDS (cgps_tile_rec.h).  Beyond 1024 stage-1
 //    workgroups: record_reduce_kernel launches (recursively for very large N).
 //
 // Ragged sizes are exact, no padding rows: a short chunk / tile simply keeps its
@@ -469,6 +470,7 @@ __device__ __forceinline__ typename Vec16<T>::type load16_coh(const T* p) {
 // one slot (fold_slot_for): two launches may be in flight at the same time only with different
 // workspaces (include/cgps.h), hence with different counters.
 constexpr int FOLD_SLOTS = 1024;
+constexpr int FOLD_SLOT_LDS_STAGES = 1 << 16;   // set in FoldArgs::slot: record stages through the LDS tile (CGPS_FOLD_REG=0)
 #ifndef CGPS_FOLD_GROUP
 #define CGPS_FOLD_GROUP 16
 #endif
@@ -720,6 +722,7 @@ struct FoldArgs {
   const unsigned char* obs_pattern; // SRC = 2: [N] table entry of each row's diagonal term, and the table's length
   int obs_entries;                 // (SRC = 3 reads the same two fields as its weights [N][Kb], of type T, and Kb)
 };
+#include "cgps_tile_rec.h"
 template <typename T, int D, int NTILE, int NT, bool FINAL, bool INL = false>
 __device__ __forceinline__ void record_reduce_body(char* smem, unsigned tile_index, const T* __restrict__ rin, int64_t n,
                                                    int rc, T* __restrict__ rout, double* __restrict__ partial_out,
@@ -753,6 +756,58 @@ __device__ __forceinline__ void fold_record_stages(char* smem, int* last_flag, T
     using RL = RecordLayout<T, D>;
     const unsigned grp = blockIdx.x / FOLD_GROUP, ngrp = (gridDim.x + FOLD_GROUP - 1) / FOLD_GROUP;
     const unsigned gsize = (grp + 1 < ngrp) ? (unsigned)FOLD_GROUP : gridDim.x - grp * FOLD_GROUP;
+    const int slot = fold.slot & (FOLD_SLOT_LDS_STAGES - 1);
+    if constexpr (std::is_same<T, double>::value && D == 4 && FOLD_GROUP == fold_reg::MAX_RECORDS) {
+      // 4 x 4 fp64, at most 16 groups of 16: each stage in the registers of ONE wave (cgps_tile_rec.h).
+      // Wave 0 has issued every store of the record and the partial result, so it alone goes on: it
+      // drains them, one lane arrives, and the answer reaches the wave by readfirstlane -- no LDS
+      // word, no barrier.  It is also the only wave that loads the handed-off bytes, after its own
+      // arrival has returned.  Nothing here waits for another workgroup.
+      if (gridDim.x <= FOLD_GROUP * fold_reg::MAX_RECORDS && !(fold.slot & FOLD_SLOT_LDS_STAGES)) {
+        if (tid >= 64) return;
+        int lane = tid;
+        asm volatile("" : "+v"(lane));             // (keeps the stages' lane arithmetic below the streaming loop)
+        auto arrive1 = [&](unsigned int* ctr, unsigned expected) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          int last = 0;
+          if (lane == 0) last = atomicInc(ctr, expected - 1u) == expected - 1u;
+          last = __builtin_amdgcn_readfirstlane(last);
+          if (!COH && last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          }
+          return last != 0;                        // wave-uniform
+        };
+        const double* recd = reinterpret_cast<const double*>(rec);
+        double* grecd = reinterpret_cast<double*>(fold.group_records);
+        double* gpart = partial + PARTIAL_STRIDE * (size_t)gridDim.x;
+        const bool lead1 = arrive1(&g_fold_counter[slot][1 + grp], gsize);
+        CGPS_KSTAMP(4);
+        if (!lead1) return;
+        // the group stage, then (for the group whose record arrives last) the top stage: ONE copy of the
+        // stage's code, walked twice.  A single tile's record is what the top stage would be handed.
+        const bool single = gridDim.x == 1;
+#pragma unroll 1
+        for (int top = single ? 1 : 0; top < 2; ++top) {
+          const bool t1 = top != 0;
+          const double* rin = t1 ? (single ? recd : grecd) : recd + (size_t)grp * FOLD_GROUP * RL::STRIDE;
+          double* rout = t1 ? reinterpret_cast<double*>(fold.shard_record) : grecd + (size_t)grp * RL::STRIDE;
+          double* pout = t1 ? fold.shard_partial : gpart + PARTIAL_STRIDE * (size_t)grp;
+          const int n = t1 ? (single ? 1 : (int)ngrp) : (int)gsize;
+          const int np = t1 ? (single ? 1 : (int)(gridDim.x + ngrp)) : 0;
+          record_stage_reg<COH>(lane, t1 && fold.shard_record == nullptr, rin, n, rout, pout, t1 ? partial : nullptr, np,
+                                fold.out2, fold.info, t1 ? (int64_t)0 : (int64_t)grp * FOLD_GROUP,
+                                (t1 && !single) ? rows_per_tile * FOLD_GROUP : rows_per_tile, N);
+          if (t1) break;
+          CGPS_KSTAMP(5);
+          const bool fin1 = arrive1(&g_fold_counter[slot][0], ngrp);
+          CGPS_KSTAMP(6);
+          if (!fin1) return;
+        }
+        CGPS_KSTAMP(7);
+        return;
+      }
+    }
     auto arrive = [&](unsigned int* ctr, unsigned expected) {
       if (tid < 64) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -770,7 +825,7 @@ __device__ __forceinline__ void fold_record_stages(char* smem, int* last_flag, T
     };
     T* grec = reinterpret_cast<T*>(fold.group_records);
     double* gpartial = partial + PARTIAL_STRIDE * (size_t)gridDim.x;       // the groups' partial results
-    const bool lead = arrive(&g_fold_counter[fold.slot][1 + grp], gsize);
+    const bool lead = arrive(&g_fold_counter[slot][1 + grp], gsize);
     CGPS_KSTAMP(4);
     if (gridDim.x == 1) {
       // a single tile: its one record is what the top stage would be handed
@@ -786,7 +841,7 @@ __device__ __forceinline__ void fold_record_stages(char* smem, int* last_flag, T
                                                            (int*)nullptr, rows_per_tile, N, (int64_t)RL::STRIDE,
                                                            (int64_t)PARTIAL_STRIDE);
       CGPS_KSTAMP(5);
-      const bool fin = arrive(&g_fold_counter[fold.slot][0], ngrp);
+      const bool fin = arrive(&g_fold_counter[slot][0], ngrp);
       CGPS_KSTAMP(6);
       if (fin) {
         if (fold.shard_record != nullptr)
@@ -1365,6 +1420,11 @@ void tile_set_attributes() {
   });
 }
 
+inline bool fold_reg_enabled() {            // CGPS_FOLD_REG=0: the in-launch record stages through the LDS tile (cross-check / A-B timing)
+  static const bool on = [] { const char* e = getenv("CGPS_FOLD_REG"); return !(e && e[0] == '0'); }();
+  return on;
+}
+
 // Slot of the arrival counters that belongs to this (device, workspace).  The counters are device data of THIS
 // translation unit (static __device__ above), so the map is too (internal linkage, not `inline`).  A slot's
 // counters are zero whenever no launch that uses it is in flight (the arrival that completes a count wraps it to
@@ -1400,7 +1460,7 @@ static int fold_slot_for(const void* ws) {
     owner[s] = key;
   }
   last_use[s] = ++tick;
-  return s;
+  return fold_reg_enabled() ? s : (s | FOLD_SLOT_LDS_STAGES);
 }
 // zero every arrival counter of the current device, on `st` (cgps_reset_counters)
 static hipError_t fold_reset_counters(hipStream_t st) {

@@ -234,6 +234,110 @@ void run_tilecr(int grid, hipStream_t st) {
   CK(hipFree(sums));
 }
 
+// ---- one record stage alone: n records -> one record (or the two scalars), LDS form against register form ----
+// One workgroup of 512 threads, as in the headline launch; the records are read with coherent loads every repetition
+// (never from this CU's L1), the time is stamped by thread 0 around the stage.
+template <bool REG, bool FINAL>
+__global__ __launch_bounds__(512) void record_stage_bench_kernel(const double* rec, int n, int reps, double* rout, double* pout,
+                                                                 const double* pin, int n_partial, double* out2, int* info,
+                                                                 long long* ticks) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using RL = RecordLayout<double, 4>;
+  long long acc = 0;
+  for (int rep = 0; rep < reps; ++rep) {
+    __syncthreads();
+    const long long t0 = wall_clock64();
+    if constexpr (REG) {
+      if (threadIdx.x < 64)
+        record_stage_reg<true>((int)threadIdx.x, FINAL, rec, n, rout, pout, FINAL ? pin : nullptr, FINAL ? n_partial : 0, out2, info,
+                                      0, 4096, (int64_t)n * 4096);
+    } else {
+      record_reduce_body<double, 4, (FINAL ? FOLD_MAX_GROUPS : FOLD_GROUP), 512, FINAL, true>(smem, 0u, rec, (int64_t)n, 1, rout, pout, FINAL ? pin : nullptr,
+                                                                  FINAL ? (int64_t)n_partial : 0, out2, info, 4096,
+                                                                  (int64_t)n * 4096, (int64_t)RL::STRIDE, (int64_t)PARTIAL_STRIDE);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const long long t1 = wall_clock64();
+    acc += t1 - t0;
+  }
+  if (threadIdx.x == 0) ticks[0] = acc;
+}
+
+template <bool REG, bool FINAL>
+static void run_record_stage(const double* rec, int n, double* rout, double* pout, const double* pin, int n_partial, double* out2,
+                             int* info, long long* ticks, hipStream_t st) {
+  using RL = RecordLayout<double, 4>;
+  const size_t lds = stage_lds_bytes<double, 4>(FOLD_MAX_GROUPS, 512);
+  const int reps = 200;
+  for (int pass = 0; pass < 2; ++pass)        // the second launch is the one reported
+    hipLaunchKernelGGL((record_stage_bench_kernel<REG, FINAL>), dim3(1), dim3(512), lds, st, rec, n, reps, rout, pout, pin, n_partial,
+                       out2, info, ticks);
+  CK(hipStreamSynchronize(st));
+  long long t;
+  CK(hipMemcpy(&t, ticks, sizeof(t), hipMemcpyDeviceToHost));
+  double r[RL::STRIDE], p[4], o[2];
+  int inf;
+  CK(hipMemcpy(r, rout, sizeof(r), hipMemcpyDeviceToHost));
+  CK(hipMemcpy(p, pout, sizeof(p), hipMemcpyDeviceToHost));
+  CK(hipMemcpy(o, out2, sizeof(o), hipMemcpyDeviceToHost));
+  CK(hipMemcpy(&inf, info, sizeof(inf), hipMemcpyDeviceToHost));
+  double cs = 0;
+  for (int i = 0; i < RL::STRIDE; ++i) cs += r[i] * (1 + i);
+  if (FINAL)
+    printf("  %-9s top stage   n=%2d (+%3d partial results): %6.0f ns   [out2 %.15g %.15g info %d]\n", REG ? "registers" : "LDS", n,
+           n_partial, (double)t / reps * 10.0, o[0], o[1], inf);
+  else
+    printf("  %-9s group stage n=%2d: %6.0f ns   [record checksum %.15g partial %.15g %.15g %g]\n", REG ? "registers" : "LDS", n,
+           (double)t / reps * 10.0, cs, p[0], p[1], p[2]);
+}
+
+static void run_record_stages(hipStream_t st) {
+  using RL = RecordLayout<double, 4>;
+  constexpr int NREC = 16, NPART = 272;
+  std::vector<double> h((size_t)NREC * RL::STRIDE), hp((size_t)NPART * PARTIAL_STRIDE, 0.0);
+  unsigned s = 12345u;
+  auto rnd = [&]() { s = s * 1664525u + 1013904223u; return (double)((s >> 8) & 0xffff) / 65536.0 - 0.5; };
+  for (int w = 0; w < NREC; ++w) {
+    double* r = h.data() + (size_t)w * RL::STRIDE;
+    for (int a = 0; a < 4; ++a)
+      for (int b = 0; b <= a; ++b) {
+        const double v = (a == b) ? 2.5 + 0.2 * rnd() : 0.1 * rnd(), u = (a == b) ? -0.2 - 0.1 * rnd() : 0.02 * rnd();
+        r[RL::RS + 4 * a + b] = r[RL::RS + 4 * b + a] = v;
+        r[RL::DRA + 4 * a + b] = r[RL::DRA + 4 * b + a] = u;
+      }
+    for (int a = 0; a < 16; ++a) r[RL::CS + a] = 0.3 * rnd();
+    for (int a = 0; a < 4; ++a) { r[RL::YS + a] = rnd(); r[RL::DYA + a] = 0.1 * rnd(); }
+  }
+  for (int i = 0; i < NPART; ++i) { hp[(size_t)i * PARTIAL_STRIDE] = 1.0 + rnd(); hp[(size_t)i * PARTIAL_STRIDE + 1] = 3.0 + rnd(); }
+  double *rec, *rout, *pout, *pin, *out2;
+  int* info;
+  long long* ticks;
+  CK(hipMalloc(&rec, h.size() * sizeof(double)));
+  CK(hipMalloc(&rout, RL::STRIDE * sizeof(double)));
+  CK(hipMalloc(&pout, 4 * sizeof(double)));
+  CK(hipMalloc(&pin, hp.size() * sizeof(double)));
+  CK(hipMalloc(&out2, 2 * sizeof(double)));
+  CK(hipMalloc(&info, sizeof(int)));
+  CK(hipMalloc(&ticks, sizeof(long long)));
+  CK(hipMemcpy(rec, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  CK(hipMemcpy(pin, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
+  CK(hipMemset(rout, 0, RL::STRIDE * sizeof(double)));
+  CK(hipMemset(pout, 0, 4 * sizeof(double)));
+  CK(hipMemset(out2, 0, 2 * sizeof(double)));
+  CK(hipMemset(info, 0, sizeof(int)));
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&record_stage_bench_kernel<false, false>),
+                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_lds_bytes<double, 4>(FOLD_MAX_GROUPS, 512)));
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&record_stage_bench_kernel<false, true>),
+                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_lds_bytes<double, 4>(FOLD_MAX_GROUPS, 512)));
+  printf("one record stage, one workgroup of 512 threads, mean of 200 repetitions inside one launch\n");
+  for (int n : {16, 9, 2}) {
+    run_record_stage<false, false>(rec, n, rout, pout, pin, NPART, out2, info, ticks, st);
+    run_record_stage<true, false>(rec, n, rout, pout, pin, NPART, out2, info, ticks, st);
+    run_record_stage<false, true>(rec, n, rout, pout, pin, NPART, out2, info, ticks, st);
+    run_record_stage<true, true>(rec, n, rout, pout, pin, NPART, out2, info, ticks, st);
+  }
+}
+
 template <typename F>
 float time_ms(F&& launch, int reps, hipStream_t st) {
   hipEvent_t a, b;
@@ -336,6 +440,12 @@ int main(int argc, char** argv) {
       }
       break;   // fold_final_enabled() latches the environment at first use: one mode per process
     }
+    return 0;
+  }
+  if (argc > 2 && atoi(argv[2]) == 3) {           // dev_bench 20 3: one record stage alone, LDS form against register form
+    hipStream_t s3;
+    CK(hipStreamCreate(&s3));
+    run_record_stages(s3);
     return 0;
   }
   if (argc > 2 && atoi(argv[2]) == 1) {           // dev_bench 20 1: only the in-LDS reduction timings

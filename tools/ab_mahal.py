@@ -1,5 +1,7 @@
 """A/B timing of cgps_mahal_logdet between two builds of the library on the same box:
-   python tools/ab_mahal.py LIB_A LIB_B [rows d dtype]   (direct ctypes: only the symbols both builds have)"""
+   python tools/ab_mahal.py LIB_A LIB_B [rows d dtype [trials warmup_calls]]   (direct ctypes: only the symbols both builds have)
+trials: timed repetitions of 30 calls per build, alternating (default 4); warmup_calls: untimed calls per build before
+them (default 5; a few thousand take the GPU out of its idle clocks, whose ramp otherwise shows as a drift over the trials)"""
 import ctypes
 import os
 import sys
@@ -16,6 +18,8 @@ libs = sys.argv[1:3]
 rows = int(sys.argv[3]) if len(sys.argv) > 3 else 1 << 22
 d = int(sys.argv[4]) if len(sys.argv) > 4 else 8
 dtype = torch.float32 if (len(sys.argv) <= 5 or sys.argv[5] == "f32") else torch.float64
+trials = int(sys.argv[6]) if len(sys.argv) > 6 else 4
+warmup_calls = int(sys.argv[7]) if len(sys.argv) > 7 else 5
 rt = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
 ctypes.CDLL(rt, mode=ctypes.RTLD_GLOBAL)
 Rs, Os, b, _, _ = _util.conditioned_system(rows, d, dtype=dtype, device="cuda")
@@ -49,6 +53,6 @@ def run(h, reps):
 
 
 for h in handles:
-    run(h, 5)
-for trial in range(4):
+    run(h, warmup_calls)
+for trial in range(trials):
     print("  ".join("%s %.1f us" % (os.path.basename(h[0]), run(h, 30)) for h in handles), " [%s]" % out.tolist(), flush=True)
