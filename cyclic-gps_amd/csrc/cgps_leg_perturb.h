@@ -43,14 +43,15 @@ __device__ __forceinline__ bool perturb_gap(T dt, const T (&G)[D][D], Chol<T, D>
   return !f;
 }
 
+// the row arithmetic of both kernels below: lane `row` of column chunk `chunk` of `nchunks`; info_row0 is the number of
+// the operands' first row in the system info speaks of (0, or k R for model k of a concatenated system)
 template <typename T, int D, int HSRC>
-__global__ __launch_bounds__(LEG_THREADS) void leg_perturbation_kernel(
-    const T* __restrict__ ts, int64_t R, const T* __restrict__ Gg, const int64_t* __restrict__ roff,
-    const int64_t* __restrict__ ids, int64_t B, const T* __restrict__ hterm, int entries, int obs,
-    const unsigned char* __restrict__ pattern, const T* __restrict__ v, int64_t nrhs, int64_t groups, uint64_t seed,
-    uint32_t stream, T* __restrict__ out, int* __restrict__ info) {
+__device__ __forceinline__ void leg_perturbation_row(
+    int64_t row, unsigned chunk, unsigned nchunks, const T* __restrict__ ts, int64_t R, const T* __restrict__ Gg,
+    const int64_t* __restrict__ roff, const int64_t* __restrict__ ids, int64_t B, const T* __restrict__ hterm, int entries,
+    int obs, const unsigned char* __restrict__ pattern, const T* __restrict__ v, int64_t nrhs, int64_t groups,
+    uint64_t seed, uint32_t stream, T* __restrict__ out, int* __restrict__ info, int64_t info_row0) {
   constexpr int GC = RngGroup<T>::COLS;
-  const int64_t row = (int64_t)blockIdx.x * LEG_THREADS + threadIdx.x;
   if (row >= R) return;
   int64_t lo = 0, hi = B;                          // first b with roff[b + 1] > row
   while (lo < hi) {
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_perturbation_kernel(
     ok = perturb_gap<T, D, false>(ts[row] - ts[row - 1], G, Lp, F) && ok;
   }
   if (has_next) ok = perturb_gap<T, D, true>(ts[row + 1] - ts[row], G, Lc, E) && ok;
-  if (!ok && blockIdx.y == 0) report_fail(info, row);
+  if (!ok && chunk == 0) report_fail(info, info_row0 + row);
 
   const T* __restrict__ H = hterm;
   if constexpr (HSRC == PERT_H_TABLE) {
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_perturbation_kernel(
   for (int i = 0; i < D; ++i) vr[i] = v != nullptr ? v[row * D + i] : T(0);
 
   T* __restrict__ orow = out + row * D * nrhs;
-  for (int64_t c0 = (int64_t)blockIdx.y * PERT_CHUNK_GROUPS; c0 < groups; c0 += (int64_t)gridDim.y * PERT_CHUNK_GROUPS) {
+  for (int64_t c0 = (int64_t)chunk * PERT_CHUNK_GROUPS; c0 < groups; c0 += (int64_t)nchunks * PERT_CHUNK_GROUPS) {
     const int64_t c1 = c0 + PERT_CHUNK_GROUPS < groups ? c0 + PERT_CHUNK_GROUPS : groups;
 #pragma unroll 1
     for (int64_t g = c0; g < c1; ++g) {
@@ -140,6 +141,35 @@ __global__ __launch_bounds__(LEG_THREADS) void leg_perturbation_kernel(
           if (g * GC + u < nrhs) orow[i * nrhs + g * GC + u] = w[u][i] + vr[i];
     }
   }
+}
+
+template <typename T, int D, int HSRC>
+__global__ __launch_bounds__(LEG_THREADS) void leg_perturbation_kernel(
+    const T* __restrict__ ts, int64_t R, const T* __restrict__ Gg, const int64_t* __restrict__ roff,
+    const int64_t* __restrict__ ids, int64_t B, const T* __restrict__ hterm, int entries, int obs,
+    const unsigned char* __restrict__ pattern, const T* __restrict__ v, int64_t nrhs, int64_t groups, uint64_t seed,
+    uint32_t stream, T* __restrict__ out, int* __restrict__ info) {
+  leg_perturbation_row<T, D, HSRC>((int64_t)blockIdx.x * LEG_THREADS + threadIdx.x, blockIdx.y, gridDim.y, ts, R, Gg, roff, ids,
+                                   B, hterm, entries, obs, pattern, v, nrhs, groups, seed, stream, out, info, 0);
+}
+
+// MODELS (cgps_leg_perturbation_models): the same R rows under gridDim.z models, the right-hand sides of the system
+// "model 0's batch, then model 1's batch, ...".  blockIdx.z = k names the model: it brings G[k], v[k] of v[M][R][d],
+// its factors hterm + k hstride (hstride = d obs, entries d obs or R d obs values by source) and its own stream word
+// stream_ids[k]; ts, roff, ids and the pattern bytes belong to the data and are shared.  Every lane runs
+// leg_perturbation_row on its model's slices, so rows k R .. (k + 1) R - 1 of out are leg_perturbation_kernel's for
+// model k's operands bit for bit.
+template <typename T, int D, int HSRC>
+__global__ __launch_bounds__(LEG_THREADS) void leg_perturbation_models_kernel(
+    const T* __restrict__ ts, int64_t R, const T* __restrict__ Gg, const int64_t* __restrict__ roff,
+    const int64_t* __restrict__ ids, int64_t B, const T* __restrict__ hterm, size_t hstride, int entries, int obs,
+    const unsigned char* __restrict__ pattern, const T* __restrict__ v, int64_t nrhs, int64_t groups, uint64_t seed,
+    const int64_t* __restrict__ stream_ids, T* __restrict__ out, int* __restrict__ info) {
+  const int64_t k = blockIdx.z;
+  leg_perturbation_row<T, D, HSRC>((int64_t)blockIdx.x * LEG_THREADS + threadIdx.x, blockIdx.y, gridDim.y, ts, R,
+                                   Gg + k * D * D, roff, ids, B, HSRC == PERT_H_NONE ? hterm : hterm + k * hstride, entries,
+                                   obs, pattern, v != nullptr ? v + k * R * D : nullptr, nrhs, groups, seed,
+                                   (uint32_t)stream_ids[k], out + k * R * D * nrhs, info, k * R);
 }
 
 }  // namespace cgps

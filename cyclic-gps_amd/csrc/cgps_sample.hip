@@ -1,9 +1,11 @@
 // cgps_sample.hip -- counter-based standard normals, samples from N(mean, J^-1) off a stored factor, and the
-// perturbed right-hand sides of the batched LEG draws (cgps_leg_perturb.h)
+// perturbed right-hand sides of the batched LEG draws, for one model and for many (cgps_leg_perturb.h), and replicated
+// observations given latent paths (cgps_leg_replicate.h)
 // One translation unit of libcgps (include/cgps.h); host code only decides sizes/offsets and
 // enqueues kernels on the caller's stream: nothing here allocates, copies to the host or synchronises.
 #include "cgps_host.h"
 #include "cgps_leg_perturb.h"
+#include "cgps_leg_replicate.h"
 #include "cgps_sample_tile.h"
 
 using namespace cgps_host;
@@ -89,6 +91,44 @@ int run_perturbation(const T* ts, int64_t R, const T* G, const int64_t* roff, co
                      stream_id, out, info);
   return check_launch("leg_perturbation_seg");
 }
+
+template <typename T, int D, int HSRC>
+int run_perturbation_models(const T* ts, int64_t R, int64_t M, const T* G, const int64_t* roff, const int64_t* ids, int64_t B,
+                            const T* hterm, int entries, int obs, const unsigned char* rows, const T* v, int64_t nrhs,
+                            uint64_t seed, const int64_t* stream_ids, T* out, int* info, hipStream_t st) {
+  constexpr int GC = cgps::RngGroup<T>::COLS;
+  const int64_t groups = (nrhs + GC - 1) / GC, nb = (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+  const int64_t chunks = (groups + cgps::PERT_CHUNK_GROUPS - 1) / cgps::PERT_CHUNK_GROUPS;
+  const size_t hstride = (size_t)D * obs * (HSRC == cgps::PERT_H_TABLE ? (size_t)entries : HSRC == cgps::PERT_H_ROWS ? (size_t)R : 1);
+  (void)hipMemsetAsync(info, 0, sizeof(int), st);
+  hipLaunchKernelGGL((cgps::leg_perturbation_models_kernel<T, D, HSRC>),
+                     dim3((unsigned)nb, (unsigned)(chunks < 65535 ? chunks : 65535), (unsigned)M), dim3(cgps::LEG_THREADS), 0, st,
+                     ts, R, G, roff, ids, B, hterm, hstride, entries, obs, rows, v, nrhs, groups, seed, stream_ids, out, info);
+  return check_launch("leg_perturbation_models");
+}
+
+template <typename T>
+int run_observations(const T* z, const uint8_t* pattern, const T* noise, const int64_t* roff, const int64_t* ids, int64_t B,
+                     int64_t R, int64_t M, const T* Bmat, const T* LLT, int d, int obs, int64_t nrhs, uint64_t seed,
+                     const int64_t* stream_ids, T* x, int* info, hipStream_t st) {
+  constexpr int GC = cgps::RngGroup<T>::COLS;
+  const int64_t groups = (nrhs + GC - 1) / GC, nb = (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
+  const int64_t chunks = (groups + cgps::REPL_CHUNK_GROUPS - 1) / cgps::REPL_CHUNK_GROUPS;
+  const dim3 grid((unsigned)nb, (unsigned)(chunks < 65535 ? chunks : 65535), (unsigned)M), block(cgps::LEG_THREADS);
+  (void)hipMemsetAsync(info, 0, sizeof(int), st);
+#define CGPS_REPL_LAUNCH(OV)                                                                                               \
+  hipLaunchKernelGGL((cgps::leg_observations_kernel<T, OV>), grid, block, 0, st, z, R, d, Bmat, LLT, obs, pattern, noise, roff, \
+                     ids, B, nrhs, groups, seed, stream_ids, x, info)
+  switch (obs) {
+    case 1: CGPS_REPL_LAUNCH(1); break;
+    case 2: CGPS_REPL_LAUNCH(2); break;
+    case 3: CGPS_REPL_LAUNCH(3); break;
+    case 4: CGPS_REPL_LAUNCH(4); break;
+    default: CGPS_REPL_LAUNCH(8); break;
+  }
+#undef CGPS_REPL_LAUNCH
+  return check_launch("leg_observations");
+}
 }  // namespace
 
 extern "C" {
@@ -159,6 +199,69 @@ int cgps_leg_perturbation_seg(const void* ts, int64_t R, const void* G, int d, i
       default: return run(std::integral_constant<int, cgps::PERT_H_ROWS>{});
     }
   });
+}
+
+int cgps_leg_perturbation_models(const void* ts, int64_t R, int64_t M, const void* G, int d, int dtype,
+                                 const int64_t* row_offsets, const int64_t* series_ids, int64_t B, int hsource,
+                                 const void* hterm, int entries, int obs, const unsigned char* rows, const void* v, int64_t nrhs,
+                                 uint64_t seed, const int64_t* stream_ids, void* out, int* info, void* stream) {
+  if (B < 0 || R < 0) return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: B < 0 or R < 0");
+  if (M < 1 || M > 65535) return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: M = %lld models, outside 1..65535", (long long)M);
+  if (B == 0 || R == 0) return CGPS_OK;
+  if (nrhs < 1 || !ts || !G || !row_offsets || !series_ids || !stream_ids || !out || !info)
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: null pointer or nrhs < 1");
+  if (hsource < CGPS_H_NONE || hsource > CGPS_H_ROWS)
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: hsource = %d, outside 0..3", hsource);
+  if (hsource != CGPS_H_NONE && (!hterm || obs < 1 || obs > 8))
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: null hterm or obs = %d outside 1..8", obs);
+  if (hsource == CGPS_H_TABLE && (!rows || entries < 1 || entries > 256))
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: null pattern or %d table entries, outside 1..256", entries);
+  if (B > 0x7fffffffLL || (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS > 0x7fffffffLL)
+    return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: B = %lld series or R = %lld rows, too many for one launch",
+                (long long)B, (long long)R);
+  if (nrhs > (int64_t)1 << 32) return fail(CGPS_ERR_ARG, "cgps_leg_perturbation_models: more than 2^32 columns");
+  if (d < 1 || d > 8) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_perturbation_models: block size d=%d outside 1..8", d);
+  if (dtype != CGPS_F32 && dtype != CGPS_F64) return fail(CGPS_ERR_UNSUPPORTED, "dtype %d not supported", dtype);
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    auto run = [&](auto hs) {
+      return run_perturbation_models<T, D, decltype(hs)::value>((const T*)ts, R, M, (const T*)G, row_offsets, series_ids, B,
+                                                                (const T*)hterm, entries, obs, rows, (const T*)v, nrhs, seed,
+                                                                stream_ids, (T*)out, info, (hipStream_t)stream);
+    };
+    switch (hsource) {
+      case CGPS_H_NONE: return run(std::integral_constant<int, cgps::PERT_H_NONE>{});
+      case CGPS_H_PLAIN: return run(std::integral_constant<int, cgps::PERT_H_PLAIN>{});
+      case CGPS_H_TABLE: return run(std::integral_constant<int, cgps::PERT_H_TABLE>{});
+      default: return run(std::integral_constant<int, cgps::PERT_H_ROWS>{});
+    }
+  });
+}
+
+int cgps_leg_observations(const void* z, const uint8_t* pattern, const void* noise_var, const int64_t* row_offsets,
+                          const int64_t* series_ids, int64_t B, int64_t R, int64_t M, const void* Bmat, const void* LLT, int d,
+                          int obs, int dtype, int64_t nrhs, uint64_t seed, const int64_t* stream_ids, void* x, int* info,
+                          void* stream) {
+  if (B < 0 || R < 0) return fail(CGPS_ERR_ARG, "cgps_leg_observations: B = %lld series, R = %lld rows", (long long)B, (long long)R);
+  if (M < 1 || M > 65535) return fail(CGPS_ERR_ARG, "cgps_leg_observations: M = %lld models, outside 1..65535", (long long)M);
+  if (B == 0 || R == 0) return CGPS_OK;
+  if (nrhs < 1 || !z || !row_offsets || !series_ids || !Bmat || !LLT || !stream_ids || !x || !info)
+    return fail(CGPS_ERR_ARG, "cgps_leg_observations: null pointer or nrhs < 1");
+  if (B > 0x7fffffffLL || (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS > 0x7fffffffLL)
+    return fail(CGPS_ERR_ARG, "cgps_leg_observations: B = %lld series or R = %lld rows, too many for one launch", (long long)B,
+                (long long)R);
+  if (nrhs > (int64_t)1 << 32) return fail(CGPS_ERR_ARG, "cgps_leg_observations: more than 2^32 columns");
+  if (d < 1 || d > 8) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_observations: d = %d outside 1..8", d);
+  if (obs < 1 || obs > 8) return fail(CGPS_ERR_UNSUPPORTED, "cgps_leg_observations: obs = %d outside 1..8", obs);
+  if (dtype != CGPS_F32 && dtype != CGPS_F64) return fail(CGPS_ERR_UNSUPPORTED, "dtype %d not supported", dtype);
+  if (dtype == CGPS_F32)
+    return run_observations<float>((const float*)z, pattern, (const float*)noise_var, row_offsets, series_ids, B, R, M,
+                                   (const float*)Bmat, (const float*)LLT, d, obs, nrhs, seed, stream_ids, (float*)x, info,
+                                   (hipStream_t)stream);
+  return run_observations<double>((const double*)z, pattern, (const double*)noise_var, row_offsets, series_ids, B, R, M,
+                                  (const double*)Bmat, (const double*)LLT, d, obs, nrhs, seed, stream_ids, (double*)x, info,
+                                  (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -71,6 +71,10 @@ _SIGNATURES = {
     "cgps_leg_intercast_models": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cgps_leg_perturbation_seg": (_int, [_vp, _i64, _vp, _int, _int, _vp, _vp, _i64, _int, _vp, _int, _int, _vp, _vp, _i64,
                                          ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp]),
+    "cgps_leg_perturbation_models": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _i64, _int, _vp, _int, _int, _vp, _vp,
+                                            _i64, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "cgps_leg_observations": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _int, _i64,
+                                     ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "cgps_leg_loo": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp,
                             _vp, _vp, _vp]),
     "cgps_record_elems": (_int, [_int, _int, ctypes.POINTER(_i64)]),

@@ -2373,6 +2373,11 @@ def _solve_columns(K_Rs, K_Os, rhs, plan):
             raise
         b, r = _series_of_row(plan, row)
         raise cr.NotPSDError("LEG batch: series %d: a block near its row %d is not positive definite" % (b, r)) from None
+    return _solve_factor_columns(dec, rhs)
+
+
+def _solve_factor_columns(dec, rhs):
+    """``cr.solve`` of rhs [rows, d, S] on a given factor, in column chunks of ``_sample_column_chunk(d)`` columns."""
     S, chunk = rhs.shape[2], _sample_column_chunk(rhs.shape[1])
     if S <= chunk:
         return cr.solve(dec, rhs)
@@ -2479,6 +2484,347 @@ def sample_from_prior_batch(m, ts, num_samples, seed, lengths=None, series_ids=N
         Rs, Os = _peg_precision_seg(tsc, G, plan.cut)
         out = cr._back(_solve_columns(Rs, Os, rhs, plan), like)
         return out.reshape(shape + (d, S)) if dense else out
+
+
+# ---- sample paths and replicated observations under many models -----------------------------------
+# The models axis of perturb and solve: the right-hand sides of the system "model 0's batch, then model 1's batch, ..."
+# come from ONE cgps_leg_perturbation_models launch, every model under a stream word of its own, and one factorisation
+# of the concatenated system solves them all.  A model owns four consecutive words: w (latent noise), w + 1
+# (observation noise of the perturbation), w + 2 (replicated observations, cgps_leg_observations), w + 3 (spare).
+MAX_STREAM_WORD = (1 << 32) - 4
+MODEL_STREAM_STRIDE = 4
+
+
+def _model_stream_words(M, stream, model_streams):
+    """The M stream words of a ``*_models`` sampler as a list of ints, each in 0 .. 2^32 - 4 (ValueError otherwise):
+    ``model_streams`` (a list or a 1-d integer tensor of M words) or stream + 4 k."""
+    if model_streams is None:
+        words = [int(stream) + MODEL_STREAM_STRIDE * k for k in range(M)]
+    else:
+        if isinstance(model_streams, torch.Tensor):
+            if model_streams.dim() != 1 or model_streams.dtype.is_floating_point or model_streams.dtype == torch.bool:
+                raise ValueError("model_streams must be a list or a 1-d integer tensor")
+            model_streams = model_streams.tolist()
+        words = [int(w) for w in model_streams]
+        if len(words) != M:
+            raise ValueError("model_streams names %d words, there are %d models" % (len(words), M))
+    bad = [(k, w) for k, w in enumerate(words) if not 0 <= w <= MAX_STREAM_WORD]
+    if bad:
+        raise ValueError("model %d: stream word %d outside 0 .. 2^32 - 4" % bad[0])
+    return words
+
+
+def _sampling_kernels_built(d, obs, dt):
+    if not 1 <= d <= 8 or dt not in (torch.float32, torch.float64) or obs > MAX_PATTERN_OBS:
+        raise ValueError("batched sampling is built for rank 1..8, obs_dim <= 8, float32 / float64")
+
+
+def _models_on_gpu(ms, *tensors):
+    """``_on_gpu`` for a list of models that share a device."""
+    dev = ms[0].N.device if ms[0].N.is_cuda else cr._device()
+    return [m if m.N.is_cuda else m.to(dev) for m in ms], tuple(None if t is None else t.to(dev) for t in tensors)
+
+
+def _models_noise_factors(ms, observed=None, noise_var=None):
+    """``observation_noise_factors`` of every model, stacked: [M, rank, obs] (neither argument), [M, 2^obs, rank, obs]
+    (``observed``) or [M, n, rank, obs] (``noise_var``).  Model k's slice is ``observation_noise_factors(ms[k], ...)``
+    itself, evaluated on that model alone -- see ``_models_sampling_operands``."""
+    return torch.stack([observation_noise_factors(m, observed, noise_var) for m in ms]).contiguous()
+
+
+def _models_sampling_operands(ms, ts, xs, observed, noise_var):
+    """What the samplers over many models read, stacked: (G [M, d, d], source, term, rows, v [M, R, d], hsource, hterm,
+    pattern) -- (source, term, rows) for ``_posterior_blocks_models``, (hsource, hterm, pattern) for
+    ``_perturbation_models``.  Slot k of a ``*_models`` sampler is promised to be the one-model call's right-hand sides
+    BIT FOR BIT, so every operand the perturbation kernel reads must carry the one-model path's own rounding: G, v and
+    the H factors are evaluated by that path's functions (``LEGMatrices.G``, ``_posterior_operands_batch``,
+    ``observation_noise_factors``), model by model on unchanged shapes, and stacked.  The elementwise stacked forms of
+    ``_models_posterior_operands`` round differently from those GEMM-based ones: they agree to an
+    ulp, not to the bit.  The cost is a few dozen small launches per model, independent of the batch."""
+    dt = ms[0].N.dtype
+    parts = [_posterior_operands_batch(m, ts, xs, observed, noise_var) for m in ms]
+    source = parts[0][0]
+    G = torch.stack([m.G for m in ms]).contiguous()
+    term = torch.stack([p[1] for p in parts])
+    v = torch.stack([p[3] for p in parts])
+    rows = torch.stack([p[2] for p in parts]) if source == _hip.ROWS_WEIGHTED else parts[0][2]
+    if noise_var is not None:
+        hsource, pattern = _hip.H_ROWS, None
+    elif observed is not None:
+        hsource, pattern = _hip.H_TABLE, rows                                 # observation_tables' pattern byte
+    else:
+        hsource, pattern = _hip.H_PLAIN, None
+    return G, source, term, rows, v, hsource, _models_noise_factors(ms, observed, noise_var).to(dt), pattern
+
+
+def _perturbation_models(ts, G, plan, ids, hsource, hterm, pattern, v, S, seed, words, k0=0):
+    """rhs [m R, d, S] of cgps_leg_perturbation_models for the models of one chunk (the first of them model k0 of the
+    call): G [m, d, d], hterm [m, ...] by source, v [m, R, d] or None, words device int64 [m]; contiguous operands of G's
+    dtype.  With ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming model, series and row."""
+    m, d, R, dt = G.shape[0], G.shape[1], plan.R, G.dtype
+    out = torch.empty(m * R, d, S, dtype=dt, device=G.device)
+    info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    entries = hterm.shape[1] if hsource == _hip.H_TABLE else 0
+    obs = hterm.shape[-1] if hsource != _hip.H_NONE else 0
+    _hip.check(_hip.lib().cgps_leg_perturbation_models(
+        _hip.ptr(ts), R, m, _hip.ptr(G), d, _hip.dtype_code(dt), _hip.ptr(plan.offsets), _hip.ptr(ids), plan.B, hsource,
+        _hip.ptr(hterm), entries, obs, _hip.ptr(pattern), _hip.ptr(v), S, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(words),
+        _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = int(info.item())
+        if bad:
+            k, b, r = _models_row(plan, bad - 1)
+            raise cr.NotPSDError("LEG models: model %d, series %d: the time gap next to its row %d is singular "
+                                 "(zero-length gap?)" % (k0 + k, b, r))
+    return out
+
+
+def _solve_columns_models(K_Rs, K_Os, rhs, plan, m, k0):
+    """``_solve_columns`` on the concatenated system of m models (the first of them model k0 of the call): a failed
+    factorisation names model, series and local row as ``_posterior_models_chunks`` does."""
+    try:
+        dec = cr.decompose(K_Rs, K_Os)
+    except cr.NotPSDError as e:
+        row = getattr(e, "row", None)
+        if row is None:
+            raise
+        k, b, r = _failed_model_series(plan, m, K_Rs, K_Os, row)
+        raise cr.NotPSDError("LEG models: model %d, series %d: a block near its row %d is not positive definite"
+                             % (k0 + k, b, r)) from None
+    return _solve_factor_columns(dec, rhs)
+
+
+def _model_chunks(M, R):
+    """(k0, k1) of the chunks of whole models of at most MODELS_POSTERIOR_MAX_ROWS concatenated rows (one model at least)."""
+    per = max(1, MODELS_POSTERIOR_MAX_ROWS // R)
+    return [(k0, min(M, k0 + per)) for k0 in range(0, M, per)]
+
+
+def _stack_model_chunks(parts, M, R):
+    """[M, R, ...] from the chunks' [m R, ...] results (a view when there is one chunk)."""
+    out = parts[0] if len(parts) == 1 else torch.cat(parts)
+    return out.view((M, R) + tuple(out.shape[1:]))
+
+
+def _perturbation_models_call(ms, ts, xs, num_samples, seed, lengths, observed, noise_var, series_ids, stream,
+                              model_streams, solve):
+    like = ts
+    ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
+                                                                                      noise_var)
+    S = _sample_count(num_samples)
+    M, d, obs, dt = len(ms), mats[0].shape[1], mats[2].shape[1], mats[0].dtype
+    _sampling_kernels_built(d, obs, dt)
+    if noise_var is not None and noise_var.dim() == 2 and noise_var.shape[1] != obs:
+        raise ValueError("noise_var must have %d channels, got %s" % (obs, tuple(noise_var.shape)))
+    words = _model_stream_words(M, stream, model_streams)
+    if not lengths:
+        _series_ids_arg(series_ids, lengths, d, obs, "cpu")
+        return torch.empty(((M, 0, bn[1], d, S) if dense else (M, 0, d, S)), dtype=dt, device=like.device)
+    ms, (ts, xs, observed, noise_var) = _models_on_gpu(ms, ts, xs, observed, noise_var)
+    dev = ms[0].N.device
+    ids = _series_ids_arg(series_ids, lengths, d, obs, dev)
+    plan = _cached_batch_plan(lengths, dev)
+    R = plan.R
+    G, source, term, rows, v, hsource, hterm, pattern = _models_sampling_operands(ms, ts, xs, observed, noise_var)
+    tsc, wd = ts.to(dt).contiguous(), torch.tensor(words, dtype=torch.int64).to(dev)
+    parts = []
+    for k0, k1 in _model_chunks(M, R):
+        m = k1 - k0
+        rhs = _perturbation_models(tsc, G[k0:k1], plan, ids, hsource, hterm[k0:k1], pattern, v[k0:k1], S, seed, wd[k0:k1], k0)
+        if solve:
+            K_Rs, K_Os, info = _posterior_blocks_models(tsc, G[k0:k1], plan.cut, source, term[k0:k1],
+                                                        rows if source != _hip.ROWS_WEIGHTED else rows[k0:k1])
+            # (a singular gap was named by the perturbation already: both kernels evaluate the gaps the same way)
+            rhs = _solve_columns_models(K_Rs, K_Os, rhs, plan, m, k0)
+            del K_Rs, K_Os
+        parts.append(rhs)
+    out = cr._back(_stack_model_chunks(parts, M, R), like)
+    return out.reshape(M, bn[0], bn[1], d, S) if dense else out
+
+
+def posterior_perturbation_models(ms, ts, xs, num_samples, seed, lengths=None, observed=None, noise_var=None,
+                                  series_ids=None, stream=0, model_streams=None):
+    """The right-hand sides of ``sample_from_posterior_models``: [M, B, n, rank, S] (dense) or [M, R, rank, S] (ragged),
+    slot k ``posterior_perturbation_batch(ms[k], ..., stream=w_k)`` bit for bit, from ONE cgps_leg_perturbation_models
+    launch per chunk of whole models.  Arguments as ``sample_from_posterior_models`` without ``observations``.  For a
+    caller with a factor of the concatenated system of their own."""
+    with torch.no_grad():
+        return _perturbation_models_call(ms, ts, xs, num_samples, seed, lengths, observed, noise_var, series_ids, stream,
+                                         model_streams, False)
+
+
+def sample_from_posterior_models(ms, ts, xs, num_samples, seed, lengths=None, observed=None, noise_var=None,
+                                 series_ids=None, stream=0, model_streams=None, observations=False):
+    """``sample_from_posterior_batch`` of M LEG models for the same B series in one call: joint latent paths under
+    every random start of a fit, every chain of a population, every point of a grid or every component of a mixture.
+    Returns [M, B, n, rank, S] (dense) or [M, R, rank, S] (ragged); slot k is
+    ``sample_from_posterior_batch(ms[k], ..., stream=w_k)`` -- bitwise on the right-hand sides
+    (``posterior_perturbation_models``), to the accuracy of the solve on the draws.  No autograd graph.
+
+    ``ms``, ``ts`` / ``xs`` / ``lengths``, ``observed`` and ``noise_var``: exactly those of ``insample_posterior_models``,
+    with its ValueErrors; the mask and the variances belong to the data and are shared by the models.  ``series_ids``
+    as in ``sample_from_posterior_batch``.  The stream words: ``model_streams`` (a list or an integer tensor of M words,
+    each in 0 .. 2^32 - 4; read on the host) gives w_k; equal words give the models common random numbers (the same
+    noise pushed through every model: what a comparison of models wants).  Otherwise w_k = ``stream`` + 4 k, a
+    ValueError if that leaves the range: a model owns w_k (latent noise), w_k + 1 (observation noise) and w_k + 2
+    (replicated observations), so models with the default words are independent.  Every ValueError is raised before
+    anything is launched; B = 0 returns empty tensors with leading dimension M.
+
+    ``observations=True`` returns (z, x) with x = ``sample_observations_models(ms, z, seed, ...)`` on the same words:
+    one replicated data set per path, [M, B, n, obs_dim, S] or [M, R, obs_dim, S].
+
+    How: every model's operands from the one-model path's own functions, stacked (``_models_sampling_operands``: that
+    is what makes slot k bitwise); then per chunk of whole models (MODELS_POSTERIOR_MAX_ROWS) ONE
+    cgps_leg_perturbation_models, ONE cgps_leg_posterior_blocks_models, ONE ``cr.decompose`` and ``cr.solve`` on column
+    chunks.  Every rank 1..8, obs_dim <= 8, both precisions.  With ``cr.CHECK_POSITIVE_DEFINITE`` a
+    zero-length gap or a block that is not positive definite raises ``cr.NotPSDError`` naming the model, the series and
+    its local row (a zero-length gap belongs to the data: the first model of the call meets it).  CPU tensors: the work
+    runs on the GPU and the result comes back to the CPU."""
+    with torch.no_grad():
+        ms = list(ms)
+        z = _perturbation_models_call(ms, ts, xs, num_samples, seed, lengths, observed, noise_var, series_ids, stream,
+                                      model_streams, True)
+        if not observations:
+            return z
+        words = _model_stream_words(len(z), stream, model_streams)
+        return z, sample_observations_models(ms, z, seed, lengths, observed, noise_var, series_ids, model_streams=words)
+
+
+def sample_from_prior_models(ms, ts, num_samples, seed, lengths=None, series_ids=None, stream=0, model_streams=None):
+    """``sample_from_prior_batch`` of M LEG models at the same B series' times in one call: ts [B, n] ->
+    [M, B, n, rank, S], or ts [R] with host ``lengths`` -> [M, R, rank, S]; slot k is
+    ``sample_from_prior_batch(ms[k], ..., stream=w_k)``, the stream words as in ``sample_from_posterior_models``.  K is
+    the prior precision of every model (cgps_peg_precision_models where that kernel is built, otherwise
+    cgps_leg_posterior_blocks_models with a zero plain term), there is no v and no observation noise.  No autograd
+    graph."""
+    with torch.no_grad():
+        like = ts
+        ms, mats = _models_operands(ms)
+        dense = lengths is None
+        shape = tuple(ts.shape)
+        ts, _, lengths = _batch_layout(ts, ts.new_zeros(shape + (1,)) if dense else ts.new_zeros(shape[0] if shape else 0, 1),
+                                       lengths)
+        S = _sample_count(num_samples)
+        M, d, dt = len(ms), mats[0].shape[1], mats[0].dtype
+        _sampling_kernels_built(d, 1, dt)
+        words = _model_stream_words(M, stream, model_streams)
+        if not lengths:
+            _series_ids_arg(series_ids, lengths, d, 1, "cpu")
+            return torch.empty(((M, 0, shape[1], d, S) if dense else (M, 0, d, S)), dtype=dt, device=like.device)
+        ms, (ts,) = _models_on_gpu(ms, ts)
+        dev = ms[0].N.device
+        ids = _series_ids_arg(series_ids, lengths, d, 1, dev)
+        plan = _cached_batch_plan(lengths, dev)
+        R = plan.R
+        G = torch.stack([m.G for m in ms]).contiguous()
+        tsc, wd = ts.to(dt).contiguous(), torch.tensor(words, dtype=torch.int64).to(dev)
+        peg = batch_supported(tsc, G[0])                           # (cgps_peg_precision_models: d <= 7, not fp64 d = 6)
+        parts = []
+        for k0, k1 in _model_chunks(M, R):
+            m = k1 - k0
+            rhs = _perturbation_models(tsc, G[k0:k1], plan, ids, _hip.H_NONE, None, None, None, S, seed, wd[k0:k1], k0)
+            if peg:
+                Rs, Os = _peg_precision_models(tsc, G[k0:k1], plan.cut)
+            else:
+                Rs, Os, _ = _posterior_blocks_models(tsc, G[k0:k1], plan.cut, _hip.ROWS_PLAIN,
+                                                     torch.zeros(m, d, d, dtype=dt, device=dev))
+            parts.append(_solve_columns_models(Rs, Os, rhs, plan, m, k0))
+            del Rs, Os
+        out = cr._back(_stack_model_chunks(parts, M, R), like)
+        return out.reshape((M,) + shape + (d, S)) if dense else out
+
+
+# Replicated observations: data sets drawn from the observation model given latent paths -- from the posterior
+# predictive when the paths are posterior draws: what a posterior predictive check compares the data with.
+def _observations_rows(z, pattern, noise_var, plan, ids, Bm, LLT, seed, words):
+    """x [M R, obs, S] of cgps_leg_observations: z [M R, d, S], pattern uint8 [R] or None, noise_var [R, obs] or None,
+    Bm [M, obs, d], LLT [M, obs, obs], words device int64 [M]; contiguous, of one dtype.  Returns (x, info)."""
+    (M, obs, d), S, R, dt = Bm.shape, z.shape[2], plan.R, z.dtype
+    x = torch.empty(M * R, obs, S, dtype=dt, device=z.device)
+    info = torch.zeros(1, dtype=torch.int32, device=z.device)
+    _hip.check(_hip.lib().cgps_leg_observations(
+        _hip.ptr(z), _hip.ptr(pattern), _hip.ptr(noise_var), _hip.ptr(plan.offsets), _hip.ptr(ids), plan.B, R, M, _hip.ptr(Bm),
+        _hip.ptr(LLT), d, obs, _hip.dtype_code(dt), S, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(words), _hip.ptr(x),
+        _hip.ptr(info), _hip.stream_ptr()))
+    return x, info
+
+
+def _observations_call(ms, z, seed, lengths, observed, noise_var, series_ids, words, models):
+    """``sample_observations_models`` (``models``: z has the leading model axis) and ``sample_observations_batch``."""
+    like = z
+    lead = 1 if models else 0
+    ms, mats = _models_operands(ms)
+    M, d, obs, dt = len(ms), mats[0].shape[1], mats[2].shape[1], mats[0].dtype
+    _sampling_kernels_built(d, obs, dt)
+    dense = lengths is None
+    if not isinstance(z, torch.Tensor) or not z.dtype.is_floating_point or z.dim() != lead + (4 if dense else 3):
+        raise ValueError("z must be a floating-point tensor %s[B, n, rank, S] (dense) or %s[sum(lengths), rank, S] (ragged)"
+                         % (("[M]",) * 2 if models else ("",) * 2))
+    if (models and z.shape[0] != M) or z.shape[-2] != d or z.shape[-1] < 1:
+        raise ValueError("z %s does not fit %d models of rank %d with at least one sample" % (tuple(z.shape), M, d))
+    S = z.shape[-1]
+    rows_shape = tuple(z.shape[lead:-2])                           # (B, n) or (R,)
+    xs_shape = rows_shape + (obs,)
+    # (the layout checks of the other batched calls, on storage-free stand-ins for ts and xs of the right shapes)
+    _, _, lengths = _batch_layout(torch.empty(rows_shape, device="meta"), torch.empty(xs_shape, device="meta"), lengths)
+    if observed is not None:
+        observed = _observed_2d(_batch_like_xs(observed, _OBSERVED, xs_shape, dense), obs)
+    if noise_var is not None:
+        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
+        if noise_var.dim() == 2 and noise_var.shape[1] != obs:
+            raise ValueError("noise_var must have %d channels, got %s" % (obs, tuple(noise_var.shape)))
+    out_shape = tuple(z.shape[:-2]) + (obs, S)
+    if not lengths:
+        _series_ids_arg(series_ids, lengths, d, obs, "cpu")
+        return torch.empty(out_shape, dtype=dt, device=like.device)
+    ms, (z, observed, noise_var) = _models_on_gpu(ms, z, observed, noise_var)
+    dev = ms[0].N.device
+    ids = _series_ids_arg(series_ids, lengths, d, obs, dev)
+    plan = _cached_batch_plan(lengths, dev)
+    _, pattern, nv = _loo_data(z.new_zeros(0, obs), observed, noise_var, dt)
+    Bm = mats[2].to(dev).contiguous()
+    LLT = torch.stack([m.LLT for m in ms]).to(dt).contiguous()     # (each model's own LLT, as the one-model calls form it)
+    wd = torch.tensor(words, dtype=torch.int64).to(dev)
+    x, info = _observations_rows(z.to(dt).reshape(M * plan.R, d, S).contiguous(), pattern, nv, plan, ids, Bm, LLT, seed, wd)
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = int(info.item())
+        if bad:
+            k, b, r = _models_row(plan, bad - 1)
+            raise cr.NotPSDError("LEG replicated observations: model %d, series %d: the noise covariance of its row %d is "
+                                 "not positive definite (a negative noise_var?)" % (k, b, r))
+    return cr._back(x, like).reshape(out_shape)
+
+
+def sample_observations_batch(m, z, seed, lengths=None, observed=None, noise_var=None, series_ids=None, stream=0):
+    """Replicated observations of latent paths of B series, in one launch: z [B, n, rank, S] (dense) or [R, rank, S]
+    with host ``lengths`` (the samplers' layouts) -> x [B, n, obs_dim, S] or [R, obs_dim, S],
+    x = B z + T eps'' with T T^T = Lambda Lambda^T + 1e-9 I + diag(s_row): the distribution of the data at EVERY row,
+    observed or not, given the paths -- with z from ``sample_from_posterior_batch`` a draw from the posterior
+    predictive, the replicated data sets of a posterior predictive check.  ``noise_var`` ([.., obs_dim] or one value
+    per row) adds the row's own variances where ``observed`` (bool, same layouts; None: everywhere) says the entry was
+    measured; at unobserved entries s is 0 and noise_var is not read (NaN included).  ``series_ids`` as in the
+    samplers.  The noise is generated in registers (cgps_leg_observations) under stream word ``stream`` + 2: with the
+    ``stream`` of the sampler that made z it is independent of the two words that draw used, and a series' replicate
+    depends only on (seed, stream, its id, its rows, s) -- not on its place in the batch or on S, bitwise.  No autograd
+    graph.  CPU tensors run on the GPU and come back."""
+    with torch.no_grad():
+        if not isinstance(m, LEGMatrices):
+            raise ValueError("m is not a LEGMatrices")
+        return _observations_call([m], z, seed, lengths, observed, noise_var, series_ids, _model_stream_words(1, stream, None),
+                                  False)
+
+
+def sample_observations_models(ms, z, seed, lengths=None, observed=None, noise_var=None, series_ids=None, stream=0,
+                               model_streams=None):
+    """``sample_observations_batch`` under M models in ONE launch: z [M, B, n, rank, S] or [M, R, rank, S] (what
+    ``sample_from_posterior_models`` returns) -> x [M, B, n, obs_dim, S] or [M, R, obs_dim, S]; slot k is
+    ``sample_observations_batch(ms[k], z[k], ..., stream=w_k)`` bit for bit, w_k from ``model_streams`` or
+    ``stream`` + 4 k as in ``sample_from_posterior_models``.  The mask and the variances belong to the data and are
+    shared by the models."""
+    with torch.no_grad():
+        ms = list(ms)
+        return _observations_call(ms, z, seed, lengths, observed, noise_var, series_ids,
+                                  _model_stream_words(len(ms), stream, model_streams), True)
 
 
 # ---- the config-5 workload -----------------------------------------------------------------

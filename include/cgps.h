@@ -476,6 +476,45 @@ int cgps_leg_perturbation_seg(const void* ts, int64_t R, const void* G, int d, i
                               const unsigned char* rows, const void* v, int64_t nrhs, uint64_t seed, uint32_t stream_id,
                               void* out, int* info, void* stream);
 
+/* cgps_leg_perturbation_seg for the same R rows under M models: the right-hand sides v + w of the block-diagonal system
+ * "model 0's batch, then model 1's batch, ..." (cgps_leg_posterior_blocks_models' system), out[M R][d][nrhs], in ONE
+ * launch with the model as a grid axis (grid (ceil(R / 64), column chunks, M)).  ts[R], row_offsets[B+1], series_ids[B]
+ * and the pattern bytes rows[R] of the table source belong to the data and are shared.  Model k brings G[k] of
+ * G[M][d][d], v[k] of v[M][R][d] (v may be NULL: zero, the prior), its factors hterm[k] of hterm[M][d][obs] (CGPS_H_PLAIN),
+ * hterm[M][entries][d][obs] (CGPS_H_TABLE) or hterm[M][R][d][obs] (CGPS_H_ROWS; CGPS_H_NONE: nothing) and its own
+ * stream word stream_ids[k]: int64 DEVICE memory [M], every value in 0 .. 2^32 - 4 (the caller checks the range; the
+ * words stream_ids[k], + 1 and + 2 are the model's: cgps_leg_observations takes the third).  Rows k R .. (k+1) R - 1 of
+ * out equal, bit for bit, what cgps_leg_perturbation_seg writes for (ts, G[k], ..., hterm[k], v[k], seed,
+ * stream_ids[k]), whatever M, the other models, nrhs or the launch geometry are.  info: 0, or 1 + a row of the
+ * concatenated system next to a singular gap.  B < 0, R < 0, M outside 1..65535, nrhs < 1, a null pointer, an unknown
+ * hsource, obs or entries outside their ranges: CGPS_ERR_ARG before anything is launched; B = 0 or R = 0: CGPS_OK,
+ * nothing launched; d outside 1..8 or an unknown dtype: CGPS_ERR_UNSUPPORTED.  Built for every d in 1..8, both
+ * precisions, all four sources.  No workspace. */
+int cgps_leg_perturbation_models(const void* ts, int64_t R, int64_t M, const void* G, int d, int dtype,
+                                 const int64_t* row_offsets, const int64_t* series_ids, int64_t B, int hsource,
+                                 const void* hterm, int entries, int obs, const unsigned char* rows, const void* v,
+                                 int64_t nrhs, uint64_t seed, const int64_t* stream_ids, void* out, int* info,
+                                 void* stream);
+
+/* Replicated observations: data sets drawn from the observation model given latent paths, for B concatenated series
+ * under M models in one launch, one lane per (row, model), grid (ceil(R / 64), column chunks, M):
+ *     x[k][i][c][s] = sum_j Bmat[k][c][j] z[k][i][j][s] + sum_c' T[c][c'] eps''[c'][s],   T T^T = LLT[k] + diag(s_i)
+ * (T lower, factored in registers by the row's lane), z[M R][d][nrhs], Bmat[M][obs][d], LLT[M][obs][obs],
+ * x[M R][obs][nrhs].  s_i[c] = noise_var[i][c] where bit c of pattern[i] is set and 0 elsewhere; noise_var[R][obs] is
+ * never read at an unobserved entry; pattern == NULL: every entry is observed; noise_var == NULL: all zeros.  The
+ * pattern only selects variances: every row and channel gets a value, observed or not.  eps''[c'], column s, is element
+ * (series_ids[b] 2^40 + r obs + c', s) of cgps_normal_fill's generator, key seed, stream word stream_ids[k] + 2 (the
+ * two words below it are those of cgps_leg_perturbation_models' draw of the same model), r the row's index inside its
+ * series b (row_offsets[B+1], series_ids[B], stream_ids[M]: int64 DEVICE memory, ranges as there).  A value depends
+ * only on (seed, stream_ids[k], the series' id, r, the row's operands, the column): not on the series' place in the
+ * batch, on M, nrhs or the launch geometry, bit for bit.  info: 0, or 1 + a row k R + i whose T has a pivot that is not
+ * positive.  B < 0, R < 0, M outside 1..65535, nrhs < 1 or a null pointer: CGPS_ERR_ARG; B = 0 or R = 0: CGPS_OK,
+ * nothing launched; d or obs outside 1..8 or an unknown dtype: CGPS_ERR_UNSUPPORTED.  No workspace. */
+int cgps_leg_observations(const void* z, const uint8_t* pattern, const void* noise_var, const int64_t* row_offsets,
+                          const int64_t* series_ids, int64_t B, int64_t R, int64_t M, const void* Bmat, const void* LLT,
+                          int d, int obs, int dtype, int64_t nrhs, uint64_t seed, const int64_t* stream_ids, void* x,
+                          int* info, void* stream);
+
 /* Leave-one-out predictives of B concatenated LEG series under M models, from the posterior of the latent
  * (cgps_decompose_solve + cgps_inverse_blocks of cgps_leg_posterior_blocks_seg / _models' system): one lane per
  * (row, model), grid (ceil(R / 256), M), then one workgroup per (model, series) for the scores, in the same call.
