@@ -16,8 +16,8 @@
 //     (own rows of SdR / SoR / SdL and the column pairs (2q, 2q+1) of SoR come straight from the slots)
 //   Sigma[2k+1, 2k] = -M1 leaves by rows, Sigma[2k, 2k-1] = -M2^T by column pairs;
 //   Sigma[2k, 2k] = D^-T D^-1 + A^T M1 + B^T M2: every lane sums the outer products of ITS two rows of
-//   (A, M1) and (B, M2) into a full lower triangle, two quad exchanges add the four partial sums, the
-//   lane keeps its two rows.
+//   (A, M1) and (B, M2) into a full lower triangle (the average of the product's two triangles: sym_note in
+//   cgps_inverse_tile.h), two quad exchanges add the four partial sums, the lane keeps its two rows.
 #pragma once
 #include "cgps_inverse_tile.h"
 
@@ -240,6 +240,11 @@ struct QuadRow {
         T p = T(0);
 #pragma unroll
         for (int t = 0; t < RP; ++t) p = fmaT(Ak[t][i], M1[t][j], fmaT(Bk[t][i], M2[t][j], p));
+        if (i != j) {                              // the average of the product's two triangles (sym_note, cgps_inverse_tile.h)
+#pragma unroll
+          for (int t = 0; t < RP; ++t) p = fmaT(Ak[t][j], M1[t][i], fmaT(Bk[t][j], M2[t][i], p));
+          p *= T(0.5);
+        }
         p = quad_sum<T>(p);
 #pragma unroll
         for (int m = i; m < D; ++m) p = fmaT(Di[m][i], Di[m][j], p);
@@ -265,7 +270,9 @@ struct QuadRow {
 // per SIMD), and the next round's factor blocks (of the next level too) requested before the current round's
 // algebra.  Big pass of config 3 (fp32): 1 250 us; a 256-thread workgroup per tile 1 698 us (three of its four
 // waves idle at level 2, two at level 1); two waves per tile at 256 registers 2 400 us (344 bytes of scratch per
-// lane); one lane per row (inverse_tile_lds_kernel) 1 556 us.
+// lane); one lane per row (inverse_tile_lds_kernel) 1 556 us.  (These timings, and those further down, were taken
+// before Sigma[2k, 2k] took the symmetrised product, sym_note: the whole op is 6 - 7 % slower with it at d = 8,
+// DESIGN.md 2.1.)
 template <typename T, int NT>
 __global__ __launch_bounds__(NT, 1) void inverse_tile_quad_kernel(
     const T* __restrict__ Dp, const T* __restrict__ Fp, const T* __restrict__ Gp, InverseLevels lv,

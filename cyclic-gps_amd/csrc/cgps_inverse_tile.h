@@ -38,6 +38,14 @@ __device__ __forceinline__ void set_identity(T (&A)[D][D]) {
     for (int j = 0; j < D; ++j) A[i][j] = (i == j) ? T(1) : T(0);
 }
 
+// sym_note: Sigma[2k,2k] = D^-T D^-1 + A^T M + B^T M' is symmetric, and only its lower triangle is computed, kept and
+// handed on.  Neither product is symmetric on its own (M = Sigma~ A + So~ B: the cross term A^T So~ B of the first is
+// the transpose of the cross term of the second), only their sum is, and that only in exact arithmetic: with an
+// ill-conditioned Sigma~ the two computed triangles of the sum differ, and a result that keeps one of them and mirrors
+// it is off by far more than either triangle alone -- at cond 1e12 (fp64) 1e3 .. 1e6 times the error of the full
+// product, in every form of this pass.  The average of the two triangles is as accurate as the full product, and
+// symmetrising is linear, so each term adds the lower triangle of (X^T Y + Y^T X) / 2
+// (tests/test_range_conditioning.py).
 // Even row 2k of one level.  Dl = D_k (dense lower Cholesky factor), F = F_k (if has_odd),
 // G = G_k-1 (if has_left); SdR / SdL = Sigma~ of the right / left odd neighbour (coarse rows k and
 // k-1), SoR = Sigma~[k, k-1].  Out: See = Sigma[2k,2k], oR = Sigma[2k+1,2k], oL = Sigma[2k,2k-1].
@@ -88,15 +96,20 @@ __device__ __forceinline__ void inverse_even_row(const T (&Dl)[D][D], const T (&
         C[i][j] = sacc;
       }
   };
-  auto acc_lower_tn = [&](const T (&X)[D][D], const T (&Y)[D][D]) {   // lower(See) += lower(X^T Y)
+  auto acc_lower_tn = [&](const T (&X)[D][D], const T (&Y)[D][D]) {   // lower(See) += lower(sym(X^T Y)), see sym_note
 #pragma unroll
     for (int i = 0; i < D; ++i)
 #pragma unroll
       for (int j = 0; j <= i; ++j) {
-        T sacc = See[i][j];
+        T sacc = T(0);
 #pragma unroll
         for (int m = 0; m < D; ++m) sacc = fmaT(X[m][i], Y[m][j], sacc);
-        See[i][j] = sacc;
+        if (i != j) {
+#pragma unroll
+          for (int m = 0; m < D; ++m) sacc = fmaT(X[m][j], Y[m][i], sacc);
+          sacc *= T(0.5);
+        }
+        See[i][j] += sacc;
       }
   };
   // C (+)= S X with S symmetric, only its lower triangle read: the callers then never need (nor
@@ -191,15 +204,20 @@ __device__ __forceinline__ void inverse_even_row_stream(bool has_odd, bool has_l
         C[i][j] = sacc;
       }
   };
-  auto acc_lower_tn = [&](const T (&X)[D][D], const T (&Y)[D][D]) {   // lower(See) += lower(X^T Y)
+  auto acc_lower_tn = [&](const T (&X)[D][D], const T (&Y)[D][D]) {   // lower(See) += lower(sym(X^T Y)), see sym_note
 #pragma unroll
     for (int i = 0; i < D; ++i)
 #pragma unroll
       for (int j = 0; j <= i; ++j) {
-        T sacc = See[i][j];
+        T sacc = T(0);
 #pragma unroll
         for (int m = 0; m < D; ++m) sacc = fmaT(X[m][i], Y[m][j], sacc);
-        See[i][j] = sacc;
+        if (i != j) {
+#pragma unroll
+          for (int m = 0; m < D; ++m) sacc = fmaT(X[m][j], Y[m][i], sacc);
+          sacc *= T(0.5);
+        }
+        See[i][j] += sacc;
       }
   };
   auto sym_times = [&](T (&C)[D][D], const T (&S)[D][D], const T (&X)[D][D]) {   // C = S X, lower(S) read

@@ -37,7 +37,12 @@ __global__ __launch_bounds__(LEVEL_THREADS) void level_kernel(
     load_block<T, D>(R + e * DD, A);
     double piv = chol_lower<T, D>(A, c, fail);
     if (fail) report_fail(info, ((e + 1) << lvl) - 1);
-    logp = log(piv);
+    if (piv >= 2.2250738585072014e-308 && piv <= 1.7976931348623157e308) {
+      logp = log(piv);
+    } else {      // a determinant outside the normal range has lost bits, or all of them: from the factor's diagonal
+#pragma unroll
+      for (int j = 0; j < D; ++j) logp += 2.0 * log((double)c.l[j][j]);
+    }
     T x[D];
     if constexpr (RHS) {
       load_vec<T, D>(y + e * D, x);
@@ -327,6 +332,12 @@ __device__ __forceinline__ void inverse_level_row(
       for (int j = 0; j < D; ++j) negT[i][j] = -M[j][i];
     store_block<T, D>(So + (e - 1) * DD, negT);         // Sig[2k,2k-1]
   }
+  // the passes that follow read the lower triangle only: hand on the average of the two computed triangles
+  // (sym_note, cgps_inverse_tile.h)
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < i; ++j) See[i][j] = See[j][i] = T(0.5) * (See[i][j] + See[j][i]);
   store_block<T, D>(Sd + e * DD, See);
 }
 

@@ -98,9 +98,11 @@ struct Chol {
 // sets fail when a pivot is not strictly positive (or NaN).
 template <typename T, int D>
 __device__ __forceinline__ double chol_lower(const T (&A)[D][D], Chol<T, D>& c, bool& fail) {
-  // product of the pivots: in the block's own precision while that cannot overflow (fp64 always;
-  // fp32: the float product is kept when it stays well inside the range, otherwise -- very large or
-  // very small blocks -- the product is redone in double from the factor's diagonal)
+  // product of the pivots, in the block's own precision.  fp64: exact to rounding while the block's determinant is a
+  // normal double; beyond that the product is inf, 0 or a denormal that has lost bits, and the callers that sum
+  // log-determinants take the factor's diagonal instead (PivotLog::mul; DESIGN.md "Numerical range and
+  // conditioning").  fp32: the float product is kept when it stays well inside the range, otherwise -- very large or
+  // very small blocks -- the product is redone in double from the factor's diagonal.
   T piv = T(1);
 #pragma unroll
   for (int j = 0; j < D; ++j) {

@@ -134,12 +134,47 @@ constexpr size_t stage_lds_bytes(int ntile, int nthr) {
 }
 
 // Running product of pivots with a rare fold into a log sum: one log() per lane
-// instead of one per eliminated row.
+// instead of one per eliminated row.  prod stays inside [1e-150, 1e150]; p is one block's determinant and may lie
+// anywhere (prod * p itself may overflow or underflow): the fold takes the factors apart exactly (mantissas in
+// [1/2, 1), exponents summed) and costs one log().  A block determinant that is no normal double -- overflowed, zero or
+// a denormal that lost bits in chol_lower's product -- is taken from the factor's diagonal instead, mul(p, c); where
+// no factor is at hand, mul(p), the log-determinant becomes NaN rather than finite and wrong.
 struct PivotLog {
   double prod = 1.0, logsum = 0.0;
+  static __device__ __forceinline__ bool normal(double p) { return p >= 2.2250738585072014e-308 && p <= 1.7976931348623157e308; }
+  // logsum += log(m 2^e); e ln2 in two parts: the high part has 32 trailing zero bits, so e * hi is exact
+  __device__ __forceinline__ void fold(double m, int e) {
+    const double ed = (double)e;
+    logsum += __builtin_fma(ed, 6.93147180369123816490e-01, __builtin_fma(ed, 1.90821492927058770002e-10, log(m)));
+    prod = 1.0;
+  }
+  // det2(md, ed): the block's determinant as md 2^ed, asked for only when p is no normal double
+  template <class F>
+  __device__ __forceinline__ void mul_with(double p, F&& det2) {
+    const double q = prod * p;
+    if (__builtin_expect(q > 1e-150 && q < 1e150, 1)) { prod = q; return; }
+    int e, e1;
+    double m = frexp(prod, &e), md;
+    if (normal(p)) md = frexp(p, &e1);
+    else det2(md, e1);
+    fold(m * md, e + e1);
+  }
   __device__ __forceinline__ void mul(double p) {
-    prod *= p;
-    if (!(prod > 1e-150 && prod < 1e150)) { logsum += log(prod); prod = 1.0; }
+    mul_with(p, [](double& md, int& ed) { md = __builtin_nan(""); ed = 0; });
+  }
+  template <typename T, int D>
+  __device__ __forceinline__ void mul(double p, const Chol<T, D>& c) {
+    mul_with(p, [&](double& md, int& ed) {      // det = prod_j l_jj^2, mantissas and exponents apart
+      double ml = 1.0;
+      int el = 0, ej;
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        ml *= frexp((double)c.l[j][j], &ej);
+        el += ej;
+      }
+      md = ml * ml;                              // >= 2^-2D
+      ed = 2 * el;
+    });
   }
   // (most lanes of the narrow record stages never saw a pivot: no log for them)
   __device__ __forceinline__ double value() const { return prod == 1.0 ? logsum : logsum + log(prod); }
@@ -182,7 +217,7 @@ __device__ __forceinline__ void eliminate_forward(T (&Rc)[D][D], T (&yc)[D], T (
                                                   T (&dya)[D], T (&On)[D][D], T (&Rn)[D][D], T (&yn)[D],
                                                   PivotLog& pl, double& mah, bool& fail) {
   Chol<T, D> c;
-  pl.mul(chol_lower<T, D>(Rc, c, fail));
+  pl.mul(chol_lower<T, D>(Rc, c, fail), c);
   fwd_subst<T, D>(c, yc);                      // x = D^-1 y
 #pragma unroll
   for (int i = 0; i < D; ++i) mah += (double)yc[i] * (double)yc[i];
@@ -344,7 +379,7 @@ __device__ __forceinline__ int tile_cr(LdsTile<T, D>& t, int n_real, PivotLog& p
           fwd_subst<T, D>(c, x);
         }
         if (role == 0) {
-          pl.mul(piv);
+          pl.mul(piv, c);
           fail = fail || f;
 #pragma unroll
           for (int i = 0; i < D; ++i) mah += (double)x[i] * (double)x[i];
@@ -1272,7 +1307,7 @@ __device__ __forceinline__ void record_reduce_body(char* smem, unsigned tile_ind
       T A[D][D], x[D];
       Chol<T, D> c;
       LdsTile<T, D>::load_blk(sm.t.R, n_real - 1, A);
-      pl.mul(chol_lower<T, D>(A, c, fail));
+      pl.mul(chol_lower<T, D>(A, c, fail), c);
       load_vec<T, D>(sm.t.y + (n_real - 1) * D, x);
       fwd_subst<T, D>(c, x);
 #pragma unroll

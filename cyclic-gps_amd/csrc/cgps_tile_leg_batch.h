@@ -156,7 +156,7 @@ __global__ __launch_bounds__(NW, 1) void leg_batch_kernel(const T* __restrict__ 
     T A[D][D], x[D];
     Chol<T, D> c;
     LdsTile<T, D>::load_blk(sm.t.R, n_real - 1, A);
-    pl.mul(chol_lower<T, D>(A, c, fail));
+    pl.mul(chol_lower<T, D>(A, c, fail), c);
     load_vec<T, D>(sm.t.y + (n_real - 1) * D, x);
     fwd_subst<T, D>(c, x);
 #pragma unroll

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(NT, (sizeof(T) == 4 ? 2 : 1)) void chunk_reduce_ml_
       MG::gather_lower(Rown, Rf);
       bool f = false;
       const double piv = chol_lower<T, D>(Rf, c, f);
-      if (q == 0) { pl.mul(piv); fail = fail || f; }
+      if (q == 0) { pl.mul(piv, c); fail = fail || f; }
       MG::gather_vec(yown, x);
       fwd_subst<T, D>(c, x);
       if (q == 0) {                        // one row's sum of squares in the block's precision, then into the fp64 sum

@@ -119,7 +119,7 @@ __device__ __forceinline__ void tile_cr_level_quad(LdsTile<T, D>& t, int tid, in
         for (int i = 0; i < D; ++i) x[i] = quad_from<T>(ye[i % RP], i / RP);
         fwd_subst<T, D>(c, x);
         if (q == 0) {
-          pl.mul(piv);
+          pl.mul(piv, c);
           fail = fail || f;
 #pragma unroll
           for (int i = 0; i < D; ++i) mah += (double)x[i] * (double)x[i];
