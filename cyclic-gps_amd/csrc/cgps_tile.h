@@ -263,6 +263,8 @@ __device__ __forceinline__ void eliminate_forward(T (&Rc)[D][D], T (&yc)[D], T (
 // On return slot K holds the tile's boundary row, Oc[0] its coupling to the row left of the
 // tile and the slots 2^l - 1 of the executed levels what is owed to that row; returns the
 // number of executed levels.
+// first: the level the reduction starts at, the slots holding what levels 0 .. first-1 would have left (a full
+// tile whose first levels ran in the streaming lanes' registers, cgps_tile_wave.h); the count starts there too.
 // dev-only: clock stamps per (level pass, wave, phase); no stamp executes in the library build
 #ifdef CGPS_TILE_STAMPS
 // stamps live in LDS (a global store here would sit in the vm queue the next barrier drains);
@@ -301,7 +303,7 @@ __device__ __forceinline__ void eliminate_forward(T (&Rc)[D][D], T (&yc)[D], T (
 #endif
 template <typename T, int D, int NTHR, int MW = CGPS_MFMA_WIDE>
 __device__ __forceinline__ int tile_cr(LdsTile<T, D>& t, int n_real, PivotLog& pl, double& mah, bool& fail,
-                                       long long* stamps = nullptr) {
+                                       long long* stamps = nullptr, int first = 0) {
   int stamp_pass = 0;
   (void)stamp_pass;
   static_assert(NTHR % 256 == 0, "tile_cr wants a multiple of four waves");
@@ -315,7 +317,7 @@ __device__ __forceinline__ int tile_cr(LdsTile<T, D>& t, int n_real, PivotLog& p
   int opaque_tid = threadIdx.x;                 // (cgps_tile_quad.h: keeps the quad levels' addressing out of the caller's loops)
   if constexpr (D == 8 || D == 4) asm volatile("" : "+v"(opaque_tid));
 #pragma unroll 1
-  for (int s = 1; (s - 1) < K; s <<= 1, ++levels) {
+  for (int s = 1 << first; (s - 1) < K; s <<= 1, ++levels) {
     const int M = (K + 1) / s, h = s >> 1;
     const int n_elim = (M + 1) / 2;             // upper bound on this level's eliminations
     if constexpr (D == 8 && CGPS_TILE_QUAD) {
@@ -530,10 +532,10 @@ struct RecordLayout {
 
 
 // Thread 0: add what the executed levels owe the row left of the tile to (dRa, dya) (which
-// already hold the streaming stage's share, as negative sums).
+// already hold the streaming stage's share, as negative sums).  first: tile_cr's first level.
 template <typename T, int D>
-__device__ __forceinline__ void collect_left_updates(LdsTile<T, D>& t, int levels, T (&dRa)[D][D], T (&dya)[D]) {
-  for (int l = 0; l < levels; ++l) {
+__device__ __forceinline__ void collect_left_updates(LdsTile<T, D>& t, int levels, T (&dRa)[D][D], T (&dya)[D], int first = 0) {
+  for (int l = first; l < first + levels; ++l) {
     const int slot = (1 << l) - 1;
     T P[D][D], p[D];
     LdsTile<T, D>::load_blk(t.R, slot, P);
@@ -638,12 +640,21 @@ __device__ __forceinline__ void absorb_right_neighbour_update(T (&Rc)[D][D], T (
 // this tile's record (thread 0).  Lanes >= n_real carry nothing (zero updates, not stored).
 template <typename T, int D, int NT>
 __device__ __forceinline__ void reduce_staged_tile_and_emit(LdsTile<T, D>& t, int n_real, T* xch, T* __restrict__ rec_out,
-                                                            PivotLog& pl, double& mah, bool& fail);
+                                                            PivotLog& pl, double& mah, bool& fail, int first = 0);
+template <typename T, int D, int NT>
+__device__ __forceinline__ void stage_kept_rows(LdsTile<T, D>& t, T (&Rc)[D][D], T (&yc)[D], T (&Cc)[D][D],
+                                                T (&dRa)[D][D], T (&dya)[D], int n_real, T* xch);
 template <typename T, int D, int NT>
 __device__ __forceinline__ void reduce_tile_and_emit(LdsTile<T, D>& t, T (&Rc)[D][D], T (&yc)[D], T (&Cc)[D][D],
                                                      T (&dRa)[D][D], T (&dya)[D], int n_real, T* xch,
                                                      T* __restrict__ rec_out, PivotLog& pl, double& mah, bool& fail) {
-  using RL = RecordLayout<T, D>;
+  stage_kept_rows<T, D, NT>(t, Rc, yc, Cc, dRa, dya, n_real, xch);
+  reduce_staged_tile_and_emit<T, D, NT>(t, n_real, xch, rec_out, pl, mah, fail);
+}
+// First half: every lane's kept row, with what its right neighbour owes it, into the LDS tile.
+template <typename T, int D, int NT>
+__device__ __forceinline__ void stage_kept_rows(LdsTile<T, D>& t, T (&Rc)[D][D], T (&yc)[D], T (&Cc)[D][D],
+                                                T (&dRa)[D][D], T (&dya)[D], int n_real, T* xch) {
   const int tid = threadIdx.x;
   absorb_right_neighbour_update<T, D, NT>(Rc, yc, dRa, dya, xch, n_real);
   if (tid < n_real) {
@@ -662,20 +673,20 @@ __device__ __forceinline__ void reduce_tile_and_emit(LdsTile<T, D>& t, T (&Rc)[D
       xch[D * D + i] = dya[i];
     }
   }
-  reduce_staged_tile_and_emit<T, D, NT>(t, n_real, xch, rec_out, pl, mah, fail);
 }
 
 // Second half: the rows are in the LDS tile (slot i = row i, Oc[i] = its coupling to row i-1, Oc[0]
 // to the row left of the tile) and xch holds the tile's own share for that row (lower triangle at
 // xch[i*D+j], vector at xch[D*D+i]).  Barrier, cyclic reduction, then thread 0 writes the record.
+// first > 0: the tile holds the state of level `first` (tile_cr) and xch the share of the levels before it too.
 template <typename T, int D, int NT>
 __device__ __forceinline__ void reduce_staged_tile_and_emit(LdsTile<T, D>& t, int n_real, T* xch, T* __restrict__ rec_out,
-                                                            PivotLog& pl, double& mah, bool& fail) {
+                                                            PivotLog& pl, double& mah, bool& fail, int first) {
   using RL = RecordLayout<T, D>;
   const int tid = threadIdx.x;
   __syncthreads();
   CGPS_KSTAMP(8);
-  const int levels = tile_cr<T, D, NT>(t, n_real, pl, mah, fail);
+  const int levels = tile_cr<T, D, NT>(t, n_real, pl, mah, fail, nullptr, first);
   CGPS_KSTAMP(9);
   // the record, one block element per lane (every parked block is stored symmetric): D*D lanes of
   // wave 0 instead of thread 0 walking the levels one after the other
@@ -690,7 +701,7 @@ __device__ __forceinline__ void reduce_staged_tile_and_emit(LdsTile<T, D>& t, in
     };
     T dra = (i >= j) ? xch[i * D + j] : xch[j * D + i];
     T dyv = xch[D * D + i];
-    for (int l = 0; l < levels; ++l) {
+    for (int l = first; l < first + levels; ++l) {
       const int slot = (1 << l) - 1;
       dra -= elem(t.R, slot);
       dyv -= t.y[slot * D + i];
@@ -756,8 +767,10 @@ struct FoldArgs {
   size_t pair_ws_stride;
   const unsigned char* obs_pattern; // SRC = 2: [N] table entry of each row's diagonal term, and the table's length
   int obs_entries;                 // (SRC = 3 reads the same two fields as its weights [N][Kb], of type T, and Kb)
+  int wave_levels;                 // 4 x 4 fp64, SRC = 0: non-zero = a full tile's first CGPS_WAVE_LEVELS levels in the streaming lanes' registers
 };
 #include "cgps_tile_rec.h"
+#include "cgps_tile_wave.h"
 template <typename T, int D, int NTILE, int NT, bool FINAL, bool INL = false>
 __device__ __forceinline__ void record_reduce_body(char* smem, unsigned tile_index, const T* __restrict__ rin, int64_t n,
                                                    int rc, T* __restrict__ rout, double* __restrict__ partial_out,
@@ -1083,8 +1096,25 @@ __global__ __launch_bounds__(NW, (NW > NT ? 1 : stage1_min_waves<T, D>())) void 
   const bool fail_stream = fail;                 // (what fails later may be a consequence of this)
   int64_t nreal64 = (N + C - 1) / C - lane0;     // lanes of this tile that hold real rows
   const int n_real = nreal64 > NT ? NT : (int)nreal64;
-  reduce_tile_and_emit<T, D, NW>(sm.t, Rc, yc, Cc, dRa, dya, n_real, sm.xch, rec + (size_t)blockIdx.x * RecordLayout<T, D>::STRIDE,
-                                 pl, mah, fail);
+  if constexpr (SRC == 0 && std::is_same<T, double>::value && D == 4 && CGPS_WAVE_LEVELS > 0) {
+    // a full tile: its first levels are further steps of the loop above, lane to lane (cgps_tile_wave.h);
+    // ONE copy of the in-LDS reduction behind both ways of filling the tile
+    int first = 0;
+    if (fold.wave_levels != 0 && n_real == NT) {                 // (workgroup-uniform)
+      int otid = tid;
+      asm volatile("" : "+v"(otid));                             // (keeps the levels' lane arithmetic below the streaming loop)
+      wave_levels_and_hand_over<CGPS_WAVE_LEVELS, NT>(sm.t, otid, Rc, yc, Cc, dRa, dya, sm.xch, pl, mah, fail);
+      CGPS_KSTAMP(10);
+      first = CGPS_WAVE_LEVELS;
+    } else {
+      stage_kept_rows<T, D, NW>(sm.t, Rc, yc, Cc, dRa, dya, n_real, sm.xch);
+    }
+    reduce_staged_tile_and_emit<T, D, NW>(sm.t, n_real, sm.xch, rec + (size_t)blockIdx.x * RecordLayout<T, D>::STRIDE, pl, mah,
+                                          fail, first);
+  } else {
+    reduce_tile_and_emit<T, D, NW>(sm.t, Rc, yc, Cc, dRa, dya, n_real, sm.xch, rec + (size_t)blockIdx.x * RecordLayout<T, D>::STRIDE,
+                                   pl, mah, fail);
+  }
   CGPS_KSTAMP(2);
   int64_t frow = r0 < N ? r0 : N - 1;
   write_partial<NW>(mah, pl.value(), fail_code(fail_stream, fail, frow), partial + PARTIAL_STRIDE * (size_t)blockIdx.x, sm.red, sm.sfail);
@@ -1460,6 +1490,16 @@ inline bool fold_reg_enabled() {            // CGPS_FOLD_REG=0: the in-launch re
   return on;
 }
 
+inline bool wave_levels_enabled() {         // CGPS_WAVE_LEVELS=0: every tile through the staged path (cross-check / A-B timing)
+  static const bool on = [] { const char* e = getenv("CGPS_WAVE_LEVELS"); return !(e && e[0] == '0'); }();
+  return on;
+}
+// the launch's FoldArgs with the run-time switch of the in-register levels filled in
+inline FoldArgs with_wave_levels(FoldArgs fa) {
+  fa.wave_levels = wave_levels_enabled() ? CGPS_WAVE_LEVELS : 0;
+  return fa;
+}
+
 // Slot of the arrival counters that belongs to this (device, workspace).  The counters are device data of THIS
 // translation unit (static __device__ above), so the map is too (internal linkage, not `inline`).  A slot's
 // counters are zero whenever no launch that uses it is in flight (the arrival that completes a count wraps it to
@@ -1587,25 +1627,25 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
     const int slot = (tiles > 1 && tiles <= (int64_t)FOLD_GROUP * FOLD_MAX_GROUPS && fold_final_enabled()) ? fold_slot_for(ws) : -1;
     const size_t ldsw = stage_lds_bytes<T, D>(Cfg::NG1, 2 * Cfg::NT1);
     if (slot >= 0 && clong > 0) {
-      const FoldArgs fa{slot, recB, out2, info, shard_record, shard_partial, clong};
+      const FoldArgs fa = with_wave_levels(FoldArgs{slot, recB, out2, info, shard_record, shard_partial, clong});
       hipLaunchKernelGGL((chunk_reduce_kernel<T, D, 0, Cfg::NT1, 2 * Cfg::NT1, true>), dim3((unsigned)tiles),
                          dim3(2 * Cfg::NT1), ldsw, st, Rs, Os, x, N, Oleft, recA, partial, fa);
       if (ev_stop) (void)hipEventRecord(ev_stop, st);
       return 0;
     }
     if (slot >= 0) {
-      const FoldArgs fa{slot, recB, out2, info, shard_record, shard_partial};
+      const FoldArgs fa = with_wave_levels(FoldArgs{slot, recB, out2, info, shard_record, shard_partial});
       hipLaunchKernelGGL((chunk_reduce_kernel<T, D, Cfg::C, Cfg::NT1, 2 * Cfg::NT1, true>), dim3((unsigned)tiles),
                          dim3(2 * Cfg::NT1), ldsw, st, Rs, Os, x, N, Oleft, recA, partial, fa);
       if (ev_stop) (void)hipEventRecord(ev_stop, st);
       return 0;
     }
     hipLaunchKernelGGL((chunk_reduce_kernel<T, D, Cfg::C, Cfg::NT1, 2 * Cfg::NT1>), dim3((unsigned)tiles),
-                       dim3(2 * Cfg::NT1), ldsw, st, Rs, Os, x, N, Oleft, recA, partial, FoldArgs{});
+                       dim3(2 * Cfg::NT1), ldsw, st, Rs, Os, x, N, Oleft, recA, partial, with_wave_levels(FoldArgs{}));
   } else if (clong > 0) {
     // more rows than one round of the chip: one round of longer chunks (see long_chunk_target_tiles)
     const int slot = fold_slot_for(ws);
-    const FoldArgs fa{slot, recB, out2, info, shard_record, shard_partial, clong};
+    const FoldArgs fa = with_wave_levels(FoldArgs{slot, recB, out2, info, shard_record, shard_partial, clong});
     bool wide = false;
     if constexpr (stage1_min_waves<T, D>() == 2) {
       if (!long_chunk_narrow()) {
@@ -1625,7 +1665,7 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
     // no faster on the GPU's clock than two launches (measured 2^14 .. 2^19 rows), but one node in a
     // caller's HIP graph and one launch on the host; a single tile (N <= 2048) finishes in place
     const int slot = (fold_final_enabled() && !(shard_record != nullptr && tiles == 1)) ? fold_slot_for(ws) : -1;
-    const FoldArgs fa{slot, recB, out2, info, shard_record, shard_partial};
+    const FoldArgs fa = with_wave_levels(FoldArgs{slot, recB, out2, info, shard_record, shard_partial});
     auto launch = [&](auto cs) {
       constexpr int CS = decltype(cs)::value;
       if (slot >= 0)
@@ -1633,7 +1673,7 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
                            lds1, st, Rs, Os, x, N, Oleft, recA, partial, fa);
       else
         hipLaunchKernelGGL((chunk_reduce_kernel<T, D, CS, Cfg::NT1>), dim3((unsigned)tiles), dim3(Cfg::NT1), lds1, st,
-                           Rs, Os, x, N, Oleft, recA, partial, FoldArgs{});
+                           Rs, Os, x, N, Oleft, recA, partial, with_wave_levels(FoldArgs{}));
     };
     if (csel == 1) launch(std::integral_constant<int, 1>{});
     else if (csel == 4) launch(std::integral_constant<int, 4>{});
@@ -1647,7 +1687,7 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
     // up to FOLD_GROUP * FOLD_MAX_GROUPS stage-1 workgroups: the record stages run inside the
     // launch (fold_final), for a whole system and for one shard of a larger one alike
     const int slot = (tiles > 1 && tiles <= (int64_t)FOLD_GROUP * FOLD_MAX_GROUPS && fold_final_enabled()) ? fold_slot_for(ws) : -1;
-    const FoldArgs fa{slot, recB, out2, info, shard_record, shard_partial};
+    const FoldArgs fa = with_wave_levels(FoldArgs{slot, recB, out2, info, shard_record, shard_partial});
     bool wide = false;
     if constexpr (stage1_min_waves<T, D>() == 2) {
       // at most one workgroup per CU: give each a second set of role waves for its LDS reduction
@@ -1659,7 +1699,7 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
                              dim3(2 * Cfg::NT1), ldsw, st, Rs, Os, x, N, Oleft, recA, partial, fa);
         else
           hipLaunchKernelGGL((chunk_reduce_kernel<T, D, Cfg::C, Cfg::NT1, 2 * Cfg::NT1>), dim3((unsigned)tiles),
-                             dim3(2 * Cfg::NT1), ldsw, st, Rs, Os, x, N, Oleft, recA, partial, FoldArgs{});
+                             dim3(2 * Cfg::NT1), ldsw, st, Rs, Os, x, N, Oleft, recA, partial, with_wave_levels(FoldArgs{}));
       }
     }
     if (!wide) {
@@ -1668,7 +1708,7 @@ int run_tile_mahal_logdet(const T* Rs, const T* Os, const T* x, int64_t N, char*
                            lds1, st, Rs, Os, x, N, Oleft, recA, partial, fa);
       else
         hipLaunchKernelGGL((chunk_reduce_kernel<T, D, Cfg::C, Cfg::NT1>), dim3((unsigned)tiles), dim3(Cfg::NT1), lds1, st,
-                           Rs, Os, x, N, Oleft, recA, partial, FoldArgs{});
+                           Rs, Os, x, N, Oleft, recA, partial, with_wave_levels(FoldArgs{}));
     }
     if (slot >= 0) {
       if (ev_stop) (void)hipEventRecord(ev_stop, st);

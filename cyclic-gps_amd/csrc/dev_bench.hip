@@ -1,6 +1,8 @@
 // Developer micro-benchmarks for the fused path (not part of the library).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o cyclic-gps_amd/lib/dev_bench cyclic-gps_amd/csrc/dev_bench.hip
 // Run on the GPU box: ./cyclic-gps_amd/lib/dev_bench [log2N]
+//   dev_bench 20 1: tile_cr alone | 20 2 1: stamps inside the one-launch pipeline | 20 3: one record stage alone |
+//   20 4: a full tile's first levels, staged in LDS against in the streaming lanes' registers (cgps_tile_wave.h)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -234,6 +236,151 @@ void run_tilecr(int grid, hipStream_t st) {
   CK(hipFree(sums));
 }
 
+// ---- the first L levels of one full 256-row tile alone: staged in LDS + L quad levels of tile_cr against the same
+// levels in the streaming lanes' registers + hand-over (cgps_tile_wave.h).  One workgroup of NTHR threads; every lane
+// carries a kept row, its coupling and an update owed to the row on its left, regenerated before every repetition;
+// thread 0 stamps each form between two barriers.  After the last repetition the LDS state the in-register form
+// leaves is compared with what the staged form left, as level L reads it: survivors' rows and right-hand sides LESS
+// what is parked for them (the staged levels take earlier levels' updates off a row as they go and park only the
+// last level's, the in-register levels park the sum: only the difference is defined), their couplings, and the share
+// of the row left of the tile (largest relative difference, elements of size >= 1e-3).
+template <int L, int NTHR>
+__global__ __launch_bounds__(NTHR) void wave_levels_bench_kernel(int reps, long long* ticks, double* diff, double* sums, double* snap) {
+  constexpr int D = 4, NT = 256, S = 1 << L;
+  using LT = LdsTile<double, D>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  StageSmem<double, D, NT, NTHR> sm(smem);
+  const int tid = threadIdx.x;
+  long long acc[2] = {0, 0};
+  double mahs[2] = {0.0, 0.0}, logs[2] = {0.0, 0.0};
+  double worst = 0.0;
+  for (int rep = 0; rep < reps; ++rep) {
+#pragma unroll
+    for (int form = 0; form < 2; ++form) {
+      double Rc[D][D], yc[D], Cc[D][D], dRa[D][D], dya[D];
+      unsigned h = (unsigned)((tid + 977 * rep) * 2654435761u) ^ 0x9e3779b9u;
+      auto rnd = [&]() { h = h * 1664525u + 1013904223u; return (double)((h >> 8) & 0xffff) / 65536.0 - 0.5; };
+      for (int a = 0; a < D; ++a) {
+        for (int b = 0; b <= a; ++b) {
+          const double v = (a == b) ? 2.5 + 0.2 * rnd() : 0.1 * rnd(), u = (a == b) ? -0.2 - 0.1 * rnd() : 0.02 * rnd();
+          Rc[a][b] = v; Rc[b][a] = v; dRa[a][b] = u; dRa[b][a] = u;
+        }
+        for (int b = 0; b < D; ++b) Cc[a][b] = 0.3 * rnd();
+        yc[a] = rnd();
+        dya[a] = 0.1 * rnd();
+      }
+      if (tid >= NT) { set_zero<double, D>(Rc); set_zero<double, D>(yc); set_zero<double, D>(Cc); set_zero<double, D>(dRa); set_zero<double, D>(dya); }
+      PivotLog pl;
+      double mah = 0.0;
+      bool fail = false;
+      __syncthreads();
+      const long long t0 = wall_clock64();
+      if (form == 0) {
+        stage_kept_rows<double, D, NTHR>(sm.t, Rc, yc, Cc, dRa, dya, NT, sm.xch);
+        __syncthreads();
+        for (int s = 1; s < S; s <<= 1) tile_cr_level_quad<double, D, NTHR>(sm.t, tid, NT - 1, NT / s, s, pl, mah, fail);
+      } else {
+        wave_levels_and_hand_over<L, NT>(sm.t, tid, Rc, yc, Cc, dRa, dya, sm.xch, pl, mah, fail);
+        __syncthreads();
+      }
+      const long long t1 = wall_clock64();
+      acc[form] += t1 - t0;
+      mahs[form] += mah;
+      logs[form] += pl.value();
+      if (rep == reps - 1 && tid < NT && wave_levels::survives(tid, L)) {
+        double A[D][D], B[D][D], P[D][D], a[D], p[D];
+        LT::load_blk(sm.t.R, tid, A);
+        LT::load_blk(sm.t.Oc, wave_levels::coupling_slot(tid, L), B);
+        load_vec<double, D>(sm.t.y + tid * D, a);
+        if (tid + (S >> 1) < NT - 1) {            // pending for this row: parked by the survivor on its right
+          double Q[D][D], q[D];
+          LT::load_blk(sm.t.R, tid + (S >> 1), Q);
+          load_vec<double, D>(sm.t.y + (tid + (S >> 1)) * D, q);
+          for (int i = 0; i < D; ++i) {
+            a[i] -= q[i];
+            for (int j = 0; j < D; ++j) A[i][j] -= Q[i][j];
+          }
+        }
+        if (wave_levels::parking_slot(tid, L) >= 0) {
+          set_zero<double, D>(P);
+          set_zero<double, D>(p);
+        } else {                                  // the share of the row left of the tile, as the record would take it
+          for (int i = 0; i < D; ++i) {
+            p[i] = sm.xch[D * D + i];
+            for (int j = 0; j < D; ++j) P[i][j] = (i >= j) ? sm.xch[i * D + j] : sm.xch[j * D + i];
+          }
+          if (form == 0)
+            for (int l = 0; l < L; ++l) {
+              double Q[D][D], q[D];
+              LT::load_blk(sm.t.R, (1 << l) - 1, Q);
+              load_vec<double, D>(sm.t.y + ((1 << l) - 1) * D, q);
+              for (int i = 0; i < D; ++i) {
+                p[i] -= q[i];
+                for (int j = 0; j < D; ++j) P[i][j] -= Q[i][j];
+              }
+            }
+        }
+        // the staged form's state goes to memory, the in-register form's is compared with it
+        auto emit = [&](int idx, double v) {
+          double* q = snap + (size_t)tid * (3 * D * D + 2 * D) + idx;
+          if (form == 0) { *q = v; return; }
+          const double ref = fabs(*q), rel = fabs(v - *q) / (ref >= 1e-3 ? ref : 1e-3);
+          worst = (rel > worst || rel != rel) ? rel : worst;
+        };
+        for (int i = 0; i < D; ++i) {
+          emit(3 * D * D + i, a[i]);
+          emit(3 * D * D + D + i, p[i]);
+          for (int j = 0; j < D; ++j) {
+            emit(i * D + j, A[i][j]);
+            emit(D * D + i * D + j, B[i][j]);
+            emit(2 * D * D + i * D + j, P[i][j]);
+          }
+        }
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_down(worst, off, 64);
+    worst = (o > worst || o != o) ? o : worst;
+  }
+  if ((tid & 63) == 0) diff[tid >> 6] = worst;
+  for (int form = 0; form < 2; ++form) {
+    __syncthreads();
+    double m = mahs[form], g = logs[form];
+    block_sum2<NTHR>(m, g, sm.red);
+    if (tid == 0) { ticks[form] = acc[form]; sums[2 * form] = m; sums[2 * form + 1] = g; }
+  }
+}
+
+template <int L, int NTHR>
+static void run_wave_levels(hipStream_t st) {
+  const size_t lds = stage_lds_bytes<double, 4>(256, NTHR);
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wave_levels_bench_kernel<L, NTHR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  long long* ticks;
+  double *diff, *sums, *snap;
+  CK(hipMalloc(&snap, 256 * 56 * sizeof(double)));
+  CK(hipMalloc(&ticks, 2 * sizeof(long long)));
+  CK(hipMalloc(&diff, 8 * sizeof(double)));
+  CK(hipMalloc(&sums, 4 * sizeof(double)));
+  const int reps = 200;
+  for (int pass = 0; pass < 2; ++pass)        // the second launch is the one reported
+    hipLaunchKernelGGL((wave_levels_bench_kernel<L, NTHR>), dim3(1), dim3(NTHR), lds, st, reps, ticks, diff, sums, snap);
+  CK(hipStreamSynchronize(st));
+  long long t[2];
+  double d[8], s[4], worst = 0.0;
+  CK(hipMemcpy(t, ticks, sizeof(t), hipMemcpyDeviceToHost));
+  CK(hipMemcpy(d, diff, sizeof(d), hipMemcpyDeviceToHost));
+  CK(hipMemcpy(s, sums, sizeof(s), hipMemcpyDeviceToHost));
+  for (int w = 0; w < NTHR / 64; ++w) worst = (d[w] > worst || d[w] != d[w]) ? d[w] : worst;
+  printf("first %d levels of a full 256-row tile, %d threads: staged + quad levels %6.0f ns | in registers + hand-over %6.0f ns"
+         "  (per level %.0f ns)  largest relative difference of the LDS state %.3g  [sums %.12g %.12g | %.12g %.12g]\n",
+         L, NTHR, (double)t[0] / reps * 10.0, (double)t[1] / reps * 10.0, (double)t[1] / reps * 10.0 / L, worst, s[0], s[1], s[2], s[3]);
+  CK(hipFree(ticks));
+  CK(hipFree(diff));
+  CK(hipFree(sums));
+  CK(hipFree(snap));
+}
+
 // ---- one record stage alone: n records -> one record (or the two scalars), LDS form against register form ----
 // One workgroup of 512 threads, as in the headline launch; the records are read with coherent loads every repetition
 // (never from this CU's L1), the time is stamped by thread 0 around the stage.
@@ -419,9 +566,12 @@ int main(int argc, char** argv) {
           printf("\n   stream end by block index (us):");
           for (int b = 0; b < 256; b += 17) printf(" b%d:%.1f", b, (ks[b][1] - t0) * 0.01);
           printf("\n");
-          const char* names[10] = {"start", "streamed", "tile reduced+emitted", "partial written", "arrived(group)",
-                                   "group reduced", "arrived(top)", "final done", "rows staged in LDS", "tile_cr done"};
-          for (int k = 0; k < 10; ++k) {
+          const char* names[11] = {"start", "streamed", "tile reduced+emitted", "partial written", "arrived(group)",
+                                   "group reduced", "arrived(top)", "final done", "rows staged in LDS", "tile_cr done",
+                                   "in-register levels"};
+          const int order[11] = {0, 1, 10, 8, 9, 2, 3, 4, 5, 6, 7};   // in the order a workgroup passes them
+          for (int ki = 0; ki < 11; ++ki) {
+            const int k = order[ki];
             long long lo = 1LL << 62, hi = 0;
             int cnt = 0;
             for (int b = 0; b < 256; ++b) {
@@ -446,6 +596,18 @@ int main(int argc, char** argv) {
     hipStream_t s3;
     CK(hipStreamCreate(&s3));
     run_record_stages(s3);
+    return 0;
+  }
+  if (argc > 2 && atoi(argv[2]) == 4) {           // dev_bench 20 4: a full tile's first levels, staged against in registers
+    hipStream_t s4;
+    CK(hipStreamCreate(&s4));
+    run_wave_levels<1, 512>(s4);
+    run_wave_levels<2, 512>(s4);
+    run_wave_levels<3, 512>(s4);
+    run_wave_levels<4, 512>(s4);
+    run_wave_levels<2, 256>(s4);
+    run_wave_levels<3, 256>(s4);
+    run_wave_levels<4, 256>(s4);
     return 0;
   }
   if (argc > 2 && atoi(argv[2]) == 1) {           // dev_bench 20 1: only the in-LDS reduction timings
