@@ -77,7 +77,8 @@ _SIGNATURES = {
                                      ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "cgps_leg_loo": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp,
                             _vp, _vp, _vp]),
-    "cgps_record_elems": (_int, [_int, _int, ctypes.POINTER(_i64)]),
+    "cgps_leg_filter": (_int, [_vp] * 5 + [_i64] * 3 + [_vp] * 3 + [_int] * 3 + [_vp] * 13),
+    "cgps_record_elems":(_int, [_int, _int, ctypes.POINTER(_i64)]),
     "cgps_shard_reduce": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp, _vp, _vp]),
     "cgps_finish_records": (_int, [_vp, _sz, _vp, _sz, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
 }

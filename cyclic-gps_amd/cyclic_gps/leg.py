@@ -2250,6 +2250,247 @@ def loo_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=Non
         return LooPredictive(om, ov, ol, score)
 
 
+# ---- one-step-ahead predictives and filtered states ------------------------------------------------------------------
+# The causal quantities of a series: the distribution of row i's observation given the rows BEFORE it, the log density
+# of what was seen under it (the terms whose sum is the log-likelihood), and the state z_i given the rows up to and
+# including i.  The smoother's kernels cannot supply them -- cyclic reduction eliminates rows in even / odd order, and the
+# pivot that carries x_<=i exists only under forward elimination -- so cgps_leg_filter walks every series forward, one
+# lane per (series, model), everything in registers.
+FilterPredictive = collections.namedtuple("FilterPredictive", ["mean", "cov", "logpdf", "z_mean", "z_cov", "loglik", "state"])
+FilterState = collections.namedtuple("FilterState", ["t", "mean", "cov"])
+
+_FILTER_FAILED = ("its one-step-ahead predictive does not exist (the covariance of its observed channels is not positive "
+                  "definite -- a negative noise_var? --, its gap is negative, or a result is not finite)")
+
+
+def _filter_init(init, lead, d, ts, starts, dt):
+    """``init`` checked against the batch: (t0 [B], m0 lead + [d], P0 lead + [d, d]) of dtype ``dt``, contiguous, or None.
+    ``lead`` is (B,) or (M, B); ``starts`` the first row of every series.  ValueError for the wrong kind, shape or device
+    and for a state later than the first row of its series."""
+    if init is None:
+        return None
+    if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
+        raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
+    t0, m0, P0 = init
+    B = lead[-1]
+    want = ((B,), tuple(lead) + (d,), tuple(lead) + (d, d))
+    got = tuple(tuple(t.shape) for t in (t0, m0, P0))
+    if got != want:
+        raise ValueError("init wants t %s, mean %s and cov %s, got %s, %s and %s" % (want + got))
+    if any(t.device != ts.device for t in (t0, m0, P0)) or not all(t.dtype.is_floating_point for t in (t0, m0, P0)):
+        raise ValueError("init must hold floating-point tensors on the device of ts")
+    t0 = t0.to(dt).contiguous()
+    if B and bool((t0 > ts.to(dt)[torch.as_tensor(starts, device=ts.device)]).any()):
+        raise ValueError("init.t lies after the first row of its series (the gap to the first row may be zero, not negative)")
+    return t0, m0.to(dt).contiguous(), P0.to(dt).contiguous()
+
+
+def _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init):
+    """cgps_leg_filter: ts [R], xs [R, obs], pattern uint8 [R] or None, noise_var [R, obs] or None, offsets device int64
+    [B + 1] (shared by the models), G [M, d, d], Bm [M, obs, d], LLT [M, obs, obs], init (t0 [B], m0 [M, B, d], P0
+    [M, B, d, d]) or None, all contiguous and of one dtype.  Returns (mean [M, R, obs], cov [M, R, obs, obs], logpdf
+    [M, R], z_mean [M, R, d], z_cov [M, R, d, d], loglik [M, B] fp64, m_end [M, B, d], P_end [M, B, d, d], info int32
+    [1]: 0 or 1 + the smallest failing row of the M R).  Nothing is read on the host."""
+    if not (ts.is_cuda and xs.is_cuda and G.is_cuda and Bm.is_cuda):
+        raise _hip.CgpsError("one-step-ahead predictives run on the GPU (there is no CPU implementation)")
+    M, obs, d = Bm.shape
+    R, B, dt, dev = xs.shape[0], offsets.shape[0] - 1, G.dtype, G.device
+    assert tuple(G.shape) == (M, d, d) and tuple(LLT.shape) == (M, obs, obs) and tuple(ts.shape) == (R,)
+    assert tuple(xs.shape) == (R, obs) and all(t.dtype == dt for t in (ts, xs, Bm, LLT))
+    assert pattern is None or (pattern.dtype == torch.uint8 and tuple(pattern.shape) == (R,))
+    assert noise_var is None or (noise_var.dtype == dt and tuple(noise_var.shape) == (R, obs))
+    assert offsets.dtype == torch.int64 and offsets.is_cuda
+    t0, m0, P0 = init if init is not None else (None, None, None)
+    assert init is None or (tuple(t0.shape) == (B,) and tuple(m0.shape) == (M, B, d) and tuple(P0.shape) == (M, B, d, d)
+                            and all(t.dtype == dt and t.is_cuda for t in init))
+    e = lambda *shape: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+    mean, cov, lp, zm, zc = e(M, R, obs), e(M, R, obs, obs), e(M, R), e(M, R, d), e(M, R, d, d)
+    m_end, P_end = e(M, B, d), e(M, B, d, d)
+    loglik = torch.zeros(M, B, dtype=torch.float64, device=dev)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    c = lambda t: None if t is None else t.contiguous()      # noqa: E731
+    ts, xs, pattern, noise_var, G, Bm, LLT, t0, m0, P0 = (c(t) for t in (ts, xs, pattern, noise_var, G, Bm, LLT, t0, m0, P0))
+    _hip.check(_hip.lib().cgps_leg_filter(
+        _hip.ptr(ts), _hip.ptr(xs), _hip.ptr(pattern), _hip.ptr(noise_var), _hip.ptr(offsets), B, R, M, _hip.ptr(G),
+        _hip.ptr(Bm), _hip.ptr(LLT), d, obs, _hip.dtype_code(dt), _hip.ptr(t0), _hip.ptr(m0), _hip.ptr(P0), _hip.ptr(mean),
+        _hip.ptr(cov), _hip.ptr(lp), _hip.ptr(zm), _hip.ptr(zc), _hip.ptr(loglik), _hip.ptr(m_end), _hip.ptr(P_end),
+        _hip.ptr(info), _hip.stream_ptr()))
+    return mean, cov, lp, zm, zc, loglik, m_end, P_end, info
+
+
+def _filter_empty(lead, obs, d, dt, device):
+    """Empty per-row results with the leading dimensions ``lead`` (one of them the empty one) in front of the row axes."""
+    e = lambda *shape: torch.empty(tuple(lead) + shape, dtype=dt, device=device)      # noqa: E731
+    return e(obs), e(obs, obs), e(), e(d), e(d, d)
+
+
+def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named):
+    """The filter of the stacked models ``mats`` over a validated, non-empty batch: (the eight tensors of
+    ``_filter_rows``, the times of the series' last rows [B]).  ``init`` has the models' axis.  ``named``: whether a
+    failure's message names the model."""
+    Nm, Rm, Bm, Lm = mats
+    M, obs, d, dt = Nm.shape[0], Bm.shape[1], Nm.shape[1], Nm.dtype
+    if obs > MAX_PATTERN_OBS:
+        raise ValueError("the filter's channel axis is built for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, obs))
+    off = [0]
+    for n in lengths:
+        off.append(off[-1] + n)
+    init = _filter_init(init, (M, len(lengths)), d, ts, off[:-1], dt)
+    if not (ts.is_cuda and xs.is_cuda and Nm.is_cuda):
+        raise _hip.CgpsError("one-step-ahead predictives run on the GPU (there is no CPU implementation)")
+    plan = _cached_batch_plan(lengths, Nm.device)
+    G = (_contract(Nm, Nm.transpose(1, 2)) + (Rm - Rm.transpose(1, 2)) + _scaled_eye(d, 1e-5, dt, Nm.device)).contiguous()
+    LLT = (_contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(obs, 1e-9, dt, Nm.device)).contiguous()
+    xs_c, pattern, nv = _loo_data(xs, observed, noise_var, dt)
+    ts_c = ts.to(dt).contiguous()
+    out = _filter_rows(ts_c, xs_c, pattern, nv, plan.offsets, G, Bm.contiguous(), LLT, init)
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = int(out[8].item())
+        if bad:
+            k, b, r = _models_row(plan, bad - 1)
+            where = ("model %d, series %d" % (k, b)) if named else ("series %d" % b)
+            raise cr.NotPSDError("LEG filter: %s: row %d: %s" % (where, r, _FILTER_FAILED))
+    return out[:8], ts_c[plan.offsets[1:] - 1]
+
+
+def _stack1(m):
+    return tuple(t.unsqueeze(0) for t in (m.N, m.R, m.B, m.Lambda))
+
+
+def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None):
+    """One-step-ahead predictives and filtered states of one series: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
+    loglik, state)``.
+
+    For every row i: ``mean`` [n, obs_dim] and ``cov`` [n, obs_dim, obs_dim], the Gaussian of the row's observation (all
+    channels) given the rows BEFORE it, p(x_i | x_<i); ``logpdf`` [n], the log density of the row's observed entries
+    under it (0 for a row that observes nothing); ``z_mean`` [n, d] and ``z_cov`` [n, d, d], the state z_i given the rows
+    up to and including i -- the only estimate available while the data are still arriving.  ``loglik`` (0-d fp64) is the
+    sum of ``logpdf`` in row order: ``log_likelihood`` of the series.  T^-1 (x_o - mean_o) with cov[o, o] = T T^T are the
+    standardised innovations.  ``observed`` and ``noise_var`` as in ``log_likelihood``; what xs and noise_var hold at
+    unobserved entries is ignored, NaN included.
+
+    ``state`` is the ``FilterState(t, mean, cov)`` after the last row.  Pass it as ``init=`` of a later call on the rows
+    that FOLLOW to continue without refiltering; the gap from ``init.t`` to the first row may be zero but not negative
+    (ValueError).  ``init=None``: the prior N(0, I) at the first row.
+
+    The work is SERIAL in the series' rows (cgps_leg_filter, DESIGN.md 4.22: one lane per (series, model) walks its
+    rows): one series of 2^20 rows is one lane's chain of 2^20 steps.  The batched calls are what the kernel is for.
+    Inference only: runs under ``torch.no_grad``.  Ranks 1..8, obs_dim <= 8, both precisions.  With
+    ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming it; with the
+    check off that row, all later rows and ``loglik`` are NaN.  CPU tensors behave as ``insample_posterior`` does (there
+    is no CPU implementation)."""
+    with torch.no_grad():
+        obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
+        if ts.dim() != 1 or xs.dim() != 2 or xs.shape[0] != ts.shape[0] or xs.shape[1] != obs:
+            raise ValueError("one series wants ts[n] and xs[n, %d], got %s and %s" % (obs, tuple(ts.shape), tuple(xs.shape)))
+        n = ts.shape[0]
+        if observed is not None:
+            observed = _observed_2d(observed, obs)
+            if observed.shape[0] != n:
+                raise ValueError("observed has %d rows, xs has %d" % (observed.shape[0], n))
+        if noise_var is not None:
+            if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
+                raise ValueError("noise_var must be a floating-point tensor")
+            if noise_var.dim() not in (1, 2) or noise_var.shape[0] != n or (noise_var.dim() == 2 and noise_var.shape[1] != obs):
+                raise ValueError("noise_var must be [n] or [n, %d], got %s" % (obs, tuple(noise_var.shape)))
+        if init is not None:
+            if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
+                raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
+            if tuple(init[0].shape) != () or tuple(init[1].shape) != (d,) or tuple(init[2].shape) != (d, d):
+                raise ValueError("one series wants init with t 0-d, mean [%d] and cov [%d, %d], got %s, %s and %s"
+                                 % ((d, d, d) + tuple(tuple(t.shape) for t in init)))
+            init = FilterState(init[0].reshape(1), init[1].reshape(1, 1, d), init[2].reshape(1, 1, d, d))
+        if n == 0:
+            state = FilterState(*(t.reshape(s).to(dt) for t, s in zip(init, ((), (d,), (d, d))))) if init is not None else None
+            return FilterPredictive(*_filter_empty((0,), obs, d, dt, ts.device),
+                                    torch.zeros((), dtype=torch.float64, device=ts.device), state)
+        out, t_end = _filter_models(_stack1(m), ts, xs, [n], observed, noise_var, init, False)
+        return FilterPredictive(*(t[0] for t in out[:5]), out[5][0, 0], FilterState(t_end[0], out[6][0, 0], out[7][0, 0]))
+
+
+def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None, init=None):
+    """``filter_predictive`` of B independent series in one call: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
+    loglik, state)`` with ``loglik`` [B] (fp64) and ``state = FilterState(t [B], mean [B, d], cov [B, d, d])``.
+
+    Layouts, ``lengths``, ``observed`` and ``noise_var``: those of ``insample_posterior_batch``, with its checks and
+    ValueErrors, raised before anything is launched.  Dense (``lengths=None``): the per-row results are [B, n, ...];
+    ragged: [R, ...] over the concatenated rows.  B = 0 returns empty tensors (and ``state`` = ``init``).  ``init``: a
+    ``FilterState`` of B states, as a previous call's ``state``, to continue every series on the rows that follow; a
+    state later than its series' first row is a ValueError.
+
+    How: ONE cgps_leg_filter, one lane per series, 64-lane workgroups, no workspace, nothing read on the host unless
+    ``cr.CHECK_POSITIVE_DEFINITE``.  The work is SERIAL in a series' rows and parallel across series: 1 024 series of 502
+    rows fill 16 CUs for 502 steps; one series of 2^20 rows is one lane's chain of 2^20 steps (a time-parallel scan is
+    not built).  A series' results do not depend on its place in the batch, bit for bit.
+
+    Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming
+    the series and its local row; with the check off that row, the later rows of THAT series, its ``loglik`` and its
+    ``state`` are NaN and every other series is untouched.  CPU tensors behave as ``insample_posterior_batch`` does
+    (there is no CPU implementation)."""
+    with torch.no_grad():
+        ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
+        if init is not None:
+            if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
+                raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
+            B = len(lengths)
+            if tuple(init[1].shape) != (B, d) or tuple(init[2].shape) != (B, d, d):
+                raise ValueError("a batch of %d series wants init with t [%d], mean [%d, %d] and cov [%d, %d, %d], got %s, %s "
+                                 "and %s" % ((B, B, B, d, B, d, d) + tuple(tuple(t.shape) for t in init)))
+            init = FilterState(init[0], init[1].unsqueeze(0), init[2].unsqueeze(0))
+        if not lengths:
+            if init is not None and tuple(init[0].shape) != (0,):
+                raise ValueError("init wants t [0] for an empty batch, got %s" % (tuple(init[0].shape),))
+            lead = (0, bn[1]) if dense else (0,)
+            state = FilterState(init[0], init[1][0], init[2][0]) if init is not None else None
+            return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
+                                    torch.empty(0, dtype=torch.float64, device=ts.device), state)
+        out, t_end = _filter_models(_stack1(m), ts, xs, lengths, observed, noise_var, init, False)
+        rows = [t[0] for t in out[:5]]
+        if dense:
+            rows = [t.reshape(bn + tuple(t.shape[1:])) for t in rows]
+        return FilterPredictive(*rows, out[5][0], FilterState(t_end, out[6][0], out[7][0]))
+
+
+def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=None, init=None):
+    """``filter_predictive_batch`` of M LEG models for the same B series in one call: slot k of every result is
+    ``filter_predictive_batch(ms[k], ...)``, bit for bit; ``loglik`` is [M, B] (fp64) and ``state =
+    FilterState(t [B], mean [M, B, d], cov [M, B, d, d])``.  ``logpdf`` [M, ...] holds the terms from which the running
+    posterior weights of the M models over time follow (a cumulative sum along the rows and a softmax over the models):
+    online model averaging.
+
+    ``ms``, ``ts`` / ``xs`` / ``lengths``, ``observed`` and ``noise_var``: exactly those of ``insample_posterior_models``,
+    with its ValueErrors, raised before anything is launched; the mask, the variances and ``init.t`` belong to the data
+    and are shared by all models.  Dense: [M, B, n, ...]; ragged: [M, R, ...]; an empty batch gives empty tensors with
+    leading dimension M.
+
+    How: ONE cgps_leg_filter with grid (ceil(B / 64), M): one lane per (series, model).  The work is SERIAL in a
+    series' rows: one series of 2^20 rows is one lane's chain of 2^20 steps under every model.
+
+    Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming
+    the model, the series and its local row; with the check off that row and the later rows of that series under THAT
+    model, its ``loglik`` and its ``state`` are NaN, and every other series and model is untouched.  CPU tensors raise
+    as ``filter_predictive_batch`` does (there is no CPU implementation)."""
+    with torch.no_grad():
+        ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
+                                                                                          noise_var)
+        M, obs, d, dt = len(ms), mats[2].shape[1], mats[0].shape[1], mats[0].dtype
+        if init is not None and not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
+            raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
+        if not lengths:
+            if init is not None and (tuple(init[0].shape), tuple(init[1].shape), tuple(init[2].shape)) != ((0,), (M, 0, d), (M, 0, d, d)):
+                raise ValueError("init wants t [0], mean [%d, 0, %d] and cov [%d, 0, %d, %d] for an empty batch" % (M, d, M, d, d))
+            lead = (M, 0, bn[1]) if dense else (M, 0)
+            return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
+                                    torch.empty(M, 0, dtype=torch.float64, device=ts.device),
+                                    FilterState(*init) if init is not None else None)
+        out, t_end = _filter_models(mats, ts, xs, lengths, observed, noise_var, init, True)
+        rows = list(out[:5])
+        if dense:
+            rows = [t.reshape((M,) + bn + tuple(t.shape[2:])) for t in rows]
+        return FilterPredictive(*rows, out[5], FilterState(t_end, out[6], out[7]))
+
+
 # ---- drawing from the process -----------------------------------------------------------------------
 def sample_observations(m, z, seed, stream=1):
     """Observations of latent paths z [n, rank, S]: x = B z + Lambda eps' [n, obs, S], eps' =

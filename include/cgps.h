@@ -543,6 +543,33 @@ int cgps_leg_loo(const void* xs, const uint8_t* pattern, const void* noise_var, 
                  const void* ip_cov_diag, int leave, void* out_mean, void* out_var, void* out_logpdf, double* out_score,
                  int* info, void* stream);
 
+/* One-step-ahead predictives and filtered states of B concatenated LEG series under M models: one lane per
+ * (series, model) walks the series' rows, grid (ceil(B / 64), M); the work is serial in a series' rows.  A launch of one
+ * lane per (row, model) first leaves exp(-1/2 gap G) of the gap before every row in the row's slot of z_cov, where the
+ * walking lane reads it before it stores the row's z_cov over it.
+ * ts[R], xs[R][obs], pattern[R], noise_var[R][obs] and row_offsets[B+1] describe the data as for cgps_leg_loo and are
+ * shared by the models; model k brings G[k] of G[M][d][d], Bmat[k] of Bmat[M][obs][d] and LLT[k] of LLT[M][obs][obs]
+ * (Lambda Lambda^T + 1e-9 I).  t0[B], m0[M][B][d], P0[M][B][d][d]: the state N(m0, P0) of every (model, series) at the
+ * time t0[b] <= the series' first time stamp, from which the series continues; all three NULL: the prior N(0, I) at the
+ * first row.  With E = exp(-1/2 gap G), (m^-, P^-) = (E m, I + E (P - I) E^T) the state carried to row i, o the row's k
+ * observed channels, e = x_o - Bmat_o m^- and S = (Bmat P^- Bmat^T + LLT + diag(s))[o][o] = T T^T:
+ *   pred_mean[M][R][obs] = Bmat m^-,  pred_cov[M][R][obs][obs] = Bmat P^- Bmat^T + LLT + diag(s on o)  (ALL channels),
+ *   logpdf[M][R] = -1/2 |T^-1 e|^2 - sum log T_cc - k/2 log 2 pi  (0 for a row that observes nothing),
+ *   z_mean[M][R][d], z_cov[M][R][d][d] = the state after the row:  m^- + K e,  P^- - K S K^T,  K = P^- Bmat_o^T S^-1,
+ *   loglik[M][B] (double) = the sum of the series' logpdf in row order,  m_end[M][B][d], P_end[M][B][d][d] = the state
+ *   after the series' last row (that of t0 for a series without rows).
+ * A gap that is negative or not finite, a pivot of S that is not positive, or a result that is not finite fails the
+ * row: it and all later rows of that series under that model are NaN, so are loglik, m_end and P_end of that (model,
+ * series), and info holds 1 + the smallest failing k R + i, else 0; other series and models are untouched.  Built for
+ * every d in 1..8 and obs in 1..8 in both precisions.  B < 0, R < 0, M outside 1..65535, some but not all of t0, m0,
+ * P0, or a null pointer with work to do: CGPS_ERR_ARG; d or obs outside 1..8 or an unknown dtype:
+ * CGPS_ERR_UNSUPPORTED; B = 0 or R = 0: CGPS_OK, nothing launched.  No workspace. */
+int cgps_leg_filter(const void* ts, const void* xs, const uint8_t* pattern, const void* noise_var,
+                    const int64_t* row_offsets, int64_t B, int64_t R, int64_t M, const void* G, const void* Bmat,
+                    const void* LLT, int d, int obs, int dtype, const void* t0, const void* m0, const void* P0,
+                    void* pred_mean, void* pred_cov, void* logpdf, void* z_mean, void* z_cov, double* loglik, void* m_end,
+                    void* P_end, int* info, void* stream);
+
 /* ---- time-axis sharding (one shard per GPU / rank) -----------------------------------------
  * The reference has no distributed code; this is the multi-GPU form BASELINE.json asks for.
  * A shard is n_loc consecutive block rows: Rs[n_loc], Os[n_loc-1] (couplings INSIDE the shard),
