@@ -273,13 +273,16 @@ class _BatchPlan:
     def per_row(self, g):
         return g.repeat_interleave(self.lens, output_size=self.R)
 
-    def boundary_rows(self):
-        """Device int64 [B-1]: the gaps (rows of an off-diagonal array) that lie between two series.  Built at the first
-        use (a copy from the host: not inside a graph capture) and kept."""
-        rows = getattr(self, "_boundary_rows", None)
-        if rows is None:
-            rows = self._boundary_rows = (torch.tensor(self.starts[1:-1], dtype=torch.int64) - 1).to(self.offsets.device)
-        return rows
+    def boundary_rows(self, m=1):
+        """Device int64 [m B - 1]: the entries of the off-diagonal array of m models' concatenated batches (m = 1: of the
+        batch) that lie between two series or two models.  Computed on the device from the offsets (nothing copied from
+        the host) at the first use and kept: a call that is to be captured builds it in its warm-up."""
+        kept = self.__dict__.setdefault("_boundary_rows", {})
+        idx = kept.get(m)
+        if idx is None:
+            ends = self.offsets[1:] - 1
+            idx = kept[m] = (torch.arange(m, device=ends.device).unsqueeze(1) * self.R + ends).reshape(-1)[:-1].contiguous()
+        return idx
 
 
 PLAN_CACHE_SIZE = 8
@@ -323,7 +326,7 @@ def _cached_batch_plan(lengths, device, make=None):
 
 def _leg_pair_raw(ts, G, source, term, rows, v):
     """The pair of reductions of one series, (out4 fp64, info2), nothing read on the host.  ``source`` names where a
-    row's diagonal term comes from, as in ``_posterior_blocks_seg``: _hip.ROWS_PLAIN (term [d, d], rows None:
+    row's diagonal term comes from, as in ``_posterior_blocks_models``: _hip.ROWS_PLAIN (term [d, d], rows None:
     cgps_leg_mahal_logdet_pair), ROWS_TABLE (term [P, d, d], rows = pattern bytes [n]: cgps_leg_mahal_logdet_pair_obs) or
     ROWS_WEIGHTED (term = basis [Kb, d, d], rows = weights [n, Kb]: cgps_leg_mahal_logdet_pair_w)."""
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
@@ -466,88 +469,237 @@ def leg_loglik_batch_reductions_w(ts, G, basis, weights, v, q, plan):
     return _leg_rows_reductions(ts, G, _hip.ROWS_WEIGHTED, basis.contiguous(), weights.contiguous(), v, q, plan)
 
 
-def _raise_batch_not_pd(info):
+# ---- one model or many: the drivers of the concatenated system ------------------------------------------------------
+# Everything below that takes G follows ``_leg_rows_reductions``: G [d, d] means no model axis -- one model's batch, the
+# _seg / _batch entry points, failures named "LEG batch: series b" -- and G [M, d, d] the system "model 0's batch, then
+# model 1's batch, ...", the _models entry points, failures named "LEG models: model k, series b".  The other operands
+# carry the same leading axis or none.
+MODELS_BACKWARD_MAX_ROWS = 1 << 22
+"""The backward of ``log_likelihood_models`` runs in chunks of whole models whose concatenated rows stay under this
+(a chunk always holds at least one model): about ten [rows, d, d] arrays are live at once, 0.84 GB each for a full
+chunk at d = 5 in fp64."""
+
+
+def _model_chunks(G, R, max_rows):
+    """The chunks of whole models of at most ``max_rows`` concatenated rows (one model at least) as (k0, k1, sel), ``sel``
+    the slice that takes the chunk's models out of a stacked operand.  G [d, d]: the one chunk (0, 1, None), whose
+    operands are taken as they are (``_take``)."""
+    if G.dim() == 2:
+        return [(0, 1, None)]
+    M, per = G.shape[0], max(1, max_rows // R)
+    return [(k0, min(M, k0 + per), slice(k0, min(M, k0 + per))) for k0 in range(0, M, per)]
+
+
+def _take(t, sel):
+    """The chunk's models of a stacked operand; without a model axis the operand itself (not even a view is made: a
+    one-model call is bound by its launches)."""
+    return t if sel is None else t[sel]
+
+
+def _cat_chunks(parts):
+    """The chunks' results along the model axis (the one chunk itself when there is no other: no copy)."""
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def _locate_row(plan, row):
+    """(model of the chunk, series, local row) of a row of the concatenated system of one or several models' batches."""
+    import bisect
+    k, row = divmod(row, plan.R)
+    b = min(max(bisect.bisect_right(plan.starts, row) - 1, 0), plan.B - 1)
+    return k, b, row - plan.starts[b]
+
+
+_NOT_PD = "a block near its row %d is not positive definite"
+_NOT_PD_OR_GAP = _NOT_PD + " (or a time gap has zero length)"
+_GAP_BLOCK = "the time gap next to its row %d gives a singular PEG block (zero-length gap?)"
+_GAP_NOISE = "the time gap next to its row %d is singular (zero-length gap?)"
+
+
+def _not_pd_error(k, b, text):
+    """The NotPSDError that names series b of one model's batch (k None) or of model k."""
+    where = ("LEG batch: series %d" % b) if k is None else ("LEG models: model %d, series %d" % (k, b))
+    return cr.NotPSDError("%s: %s" % (where, text))
+
+
+def _row_error(plan, row, k0, text):
+    """``_not_pd_error`` for a row of the concatenated system; ``k0`` is None without a model axis and otherwise the
+    first model of the chunk.  ``text`` takes the local row."""
+    k, b, r = _locate_row(plan, row)
+    return _not_pd_error(None if k0 is None else k0 + k, b, text % r)
+
+
+def _check_gaps(info, plan, k0, text):
+    """Under ``cr.CHECK_POSITIVE_DEFINITE``: the info word of an assembly kernel read on the host, a singular gap named."""
+    if cr.CHECK_POSITIVE_DEFINITE:
+        bad = int(info.item())
+        if bad:
+            raise _row_error(plan, bad - 1, k0, text)
+
+
+def _raise_not_pd(info):
+    """The first failed system of the reductions' info words [B, 2] or [M, B, 2], named."""
     bad = info.cpu()
-    rows = torch.nonzero(bad.amax(1)).flatten().tolist()
-    if rows:
-        b = rows[0]
-        code = int(bad[b, 0]) or int(bad[b, 1])
-        raise cr.NotPSDError("LEG batch: series %d: a block near its row %d is not positive definite "
-                             "(or a time gap has zero length)" % (b, code - 1))
+    hits = torch.nonzero(bad.amax(-1)).tolist()
+    if hits:
+        k, b = hits[0] if info.dim() == 3 else (None, hits[0][0])
+        code = bad[tuple(hits[0])].tolist()
+        raise _not_pd_error(k, b, _NOT_PD_OR_GAP % ((code[0] or code[1]) - 1))
 
 
-def _peg_precision_seg(ts, G, cut):
-    """Blocks of the block-diagonal PEG precision of concatenated series (cgps_peg_precision_seg).  No autograd graph."""
-    n, d = ts.shape[0], G.shape[0]
+def _peg_precision_models(ts, G, cut, info=None):
+    """Blocks of the block-diagonal PEG precision of concatenated series (cgps_peg_precision_seg) or, with G [m, d, d], of
+    the same rows model after model (cgps_peg_precision_models): Rs [m R, d, d], Os [m R - 1, d, d] with zero blocks
+    between two models.  ``info``: an int32 word to receive the kernel's (1 + the row of a singular gap).  No autograd
+    graph."""
+    R, d, lib = ts.shape[0], G.shape[-1], _hip.lib()
+    fn, count = (lib.cgps_peg_precision_models, (R, G.shape[0])) if G.dim() == 3 else (lib.cgps_peg_precision_seg, (R,))
+    n = math.prod(count)
     Rs = torch.empty(n, d, d, dtype=G.dtype, device=G.device)
     Os = torch.empty(max(n - 1, 0), d, d, dtype=G.dtype, device=G.device)
-    info = torch.zeros(1, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_peg_precision_seg(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), n, d, _hip.dtype_code(G.dtype),
-                                                 _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
+    if info is None:
+        info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), *count, d, _hip.dtype_code(G.dtype), _hip.ptr(Rs), _hip.ptr(Os),
+                  _hip.ptr(info), _hip.stream_ptr()))
     return Rs, Os
 
 
-def _peg_precision_adjoint_seg(ts, G, cut, gRs, gOs, want_ts):
-    """(d loss / d G, d loss / d ts or None) through cgps_peg_precision_adjoint_seg."""
-    n, d = ts.shape[0], G.shape[0]
-    if n < 2:
+_peg_precision_seg = _peg_precision_models        # the same function: the name of its form without a model axis
+
+
+def _peg_precision_adjoint_models(ts, G, cut, gRs, gOs, want_ts):
+    """(d loss / d G, d loss / d ts [R] or None) through cgps_peg_precision_adjoint_seg or, with G [m, d, d],
+    cgps_peg_precision_adjoint_models: every model's partial sums added per model, the models' gradients in ts added
+    over the models."""
+    R, d = ts.shape[0], G.shape[-1]
+    if R < 2:
         return torch.zeros_like(G), (torch.zeros_like(ts) if want_ts else None)
-    part = torch.empty((n - 1 + 63) // 64, d, d, dtype=G.dtype, device=G.device)
-    gtau = torch.empty(n - 1, dtype=G.dtype, device=G.device) if want_ts else None
-    _hip.check(_hip.lib().cgps_peg_precision_adjoint_seg(
-        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), n, d, _hip.dtype_code(G.dtype), _hip.ptr(gRs.contiguous()),
-        _hip.ptr(gOs.contiguous()), _hip.ptr(part), _hip.ptr(gtau), _hip.stream_ptr()))
+    lead = tuple(G.shape[:-2])
+    part = torch.empty(lead + ((R - 1 + 63) // 64, d, d), dtype=G.dtype, device=G.device)
+    gtau = torch.empty(lead + (R - 1,), dtype=G.dtype, device=G.device) if want_ts else None
+    lib = _hip.lib()
+    fn, count = (lib.cgps_peg_precision_adjoint_models, (R,) + lead) if lead else (lib.cgps_peg_precision_adjoint_seg, (R,))
+    _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), *count, d, _hip.dtype_code(G.dtype), _hip.ptr(gRs.contiguous()),
+                  _hip.ptr(gOs.contiguous()), _hip.ptr(part), _hip.ptr(gtau), _hip.stream_ptr()))
     gts = None
     if want_ts:
-        z = gtau.new_zeros(1)
-        gts = torch.cat([z, gtau]) - torch.cat([gtau, z])
-    return part.sum(0), gts
+        z = gtau.new_zeros(lead + (1,))
+        gts = torch.cat([z, gtau], -1) - torch.cat([gtau, z], -1)
+        if lead:
+            gts = gts.sum(0)
+    return part.sum(-3), gts
 
 
-def _rows_product(a, b, rows=4096):
-    """a^T b of two tall matrices a [R, p] and b [R, q] (contiguous) as batched products over chunks of ``rows`` rows,
-    added up by one reduction in a fixed order, plus the product of the remainder.  One ``a.T @ b`` with R in the
-    hundreds of thousands and p, q of a few dozen is a single GEMM tile's worth of output with all of R as its inner
-    dimension: 55 ms at R = 514 048, p = 1, q = 25 on an MI355X."""
-    R = a.shape[0]
+def _mm(a, b):
+    """a b of two matrices or of two stacks of matrices, by the call that each case has always made: ``torch.matmul``
+    reshapes a stack on its way to ``bmm``, which for an axis of length 1 can pick another kernel and another last bit."""
+    return torch.bmm(a, b) if a.dim() == 3 else torch.mm(a, b)
+
+
+def _rows_product_models(a, b, rows=4096):
+    """a^T b of two tall matrices a [R, p] and b [R, q] (contiguous), or per model of a [m, R, p] and b [m, R, q], as
+    batched products over chunks of ``rows`` rows, added up by one reduction in a fixed order, plus the product of the
+    remainder.  One ``a.T @ b`` with R in the hundreds of thousands and p, q of a few dozen is a single GEMM tile's worth
+    of output with all of R as its inner dimension: 55 ms at R = 514 048, p = 1, q = 25 on an MI355X."""
+    R, p, q = a.shape[-2], a.shape[-1], b.shape[-1]
     C = R // rows
-    out = a[C * rows:].T @ b[C * rows:]
+    out = _mm(a[..., C * rows:, :].transpose(-1, -2), b[..., C * rows:, :])
     if C:
-        out = out + torch.bmm(a[:C * rows].reshape(C, rows, -1).transpose(1, 2), b[:C * rows].reshape(C, rows, -1)).sum(0)
+        out = out + torch.bmm(a[..., :C * rows, :].reshape(-1, rows, p).transpose(1, 2),
+                              b[..., :C * rows, :].reshape(-1, rows, q)).view(tuple(a.shape[:-2]) + (C, p, q)).sum(-3)
     return out
 
 
-def _batch_diag(source, G, term, rows, need_term, need_rows):
-    """What a batch's backward has to know about where the rows' diagonal terms come from, as a pair of functions:
-    diag_term() is what K's diagonal adds to Rs, and diag_grads(gR) sends the rows' block gradients gR [R, d, d] back as
-    (d loss / d term, d loss / d rows).  (source, term, rows) as in ``_leg_pair_raw``."""
-    d = G.shape[0]
-    if source == _hip.ROWS_PLAIN:                                # the one block A, broadcast over the rows
-        return (lambda: term), (lambda gR: (gR.sum(0), None))
+_rows_product = _rows_product_models        # the same function: the name of its form without a model axis
+
+
+def _models_diag(source, G, term, rows, need_term, need_rows):
+    """What the backward has to know about where the rows' diagonal terms come from, as a pair of functions over a chunk
+    of models (``sel`` of ``_model_chunks``): diag_term(sel) is what K's diagonal adds to the chunk's Rs [.., R, d, d],
+    and diag_grads(sel, gR) sends its block gradients gR [.., R, d, d] back as (d loss / d term, d loss / d rows) of the
+    chunk, None where not wanted.  (source, term, rows) as in ``_leg_pair_raw``."""
+    d, dd = G.shape[-1], G.shape[-1] * G.shape[-1]
+    if source == _hip.ROWS_PLAIN:                                # a model's one block, broadcast over its rows
+        return (lambda sel: _take(term, sel).unsqueeze(-3)), (lambda sel, gR: (gR.sum(-3), None))
     if source == _hip.ROWS_TABLE:
         # row i adds A_table[idx[i]]; the gradient of A_table is the per-pattern sum of the rows' block gradients, taken as
-        # a matrix product with the one-hot matrix of the pattern (no scatter: ``index_add_`` on the GPU adds with atomics,
-        # in no fixed order)
-        P = term.shape[0]
+        # a matrix product with the one-hot matrix of the pattern, which all models share (no scatter: ``index_add_`` on
+        # the GPU adds with atomics, in no fixed order)
+        P = term.shape[-3]
         idx = rows.long().clamp(max=P - 1)                       # the kernel's clamp
 
-        def table_grads(gR):
+        def table_grads(sel, gR):
+            lead = tuple(gR.shape[:-3])
             codes = torch.arange(P, device=idx.device).unsqueeze(1)
             step = max(1024, (1 << 24) // P)                     # rows per product: the one-hot matrix stays small
-            gA = torch.zeros(P, d * d, dtype=G.dtype, device=G.device)
-            for s in range(0, gR.shape[0], step):                # (one product unless P * R > 2^24)
-                gA = gA + (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype) @ gR[s:s + step].reshape(-1, d * d)
-            return gA.reshape(P, d, d), None
-        return (lambda: term[idx]), table_grads
+            gA = torch.zeros(lead + (P, dd), dtype=G.dtype, device=G.device)
+            for s in range(0, gR.shape[-3], step):               # (one product unless P * R > 2^24)
+                onehot = (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype)
+                gA = gA + torch.matmul(onehot, gR[..., s:s + step, :, :].reshape(lead + (-1, dd)))
+            return gA.view(lead + (P, d, d)), None
+        return (lambda sel: _take(term, sel)[..., idx, :, :]), table_grads
     # row i adds sum_k weights[i, k] basis[k]; gR_i goes to the basis as sum_i weights[i, k] gR_i and to the weights as
-    # <gR_i, basis[k]>, both plain matrix products
-    Kb = term.shape[0]
+    # <gR_i, basis[k]>, both plain matrix products (per model)
+    Kb = term.shape[-3]
 
-    def weighted_grads(gR):
-        gb = _rows_product(rows, gR.reshape(-1, d * d)).reshape(Kb, d, d) if need_term else None
-        gw = gR.reshape(-1, d * d) @ term.reshape(Kb, d * d).T if need_rows else None
+    def weighted_grads(sel, gR):
+        lead = tuple(gR.shape[:-3])
+        gR = gR.reshape(lead + (-1, dd))
+        gb = _rows_product_models(_take(rows, sel), gR).view(lead + (Kb, d, d)) if need_term else None
+        gw = _mm(gR, _take(term, sel).reshape(lead + (Kb, dd)).transpose(-1, -2)) if need_rows else None
         return gb, gw
-    return (lambda: torch.einsum("nk,kij->nij", rows, term)), weighted_grads
+    return (lambda sel: torch.einsum("...nk,...kij->...nij", _take(rows, sel), _take(term, sel))), weighted_grads
+
+
+def _models_backward(needs, plan, source, ts, G, term, rows, v, gout):
+    """The backward of ``_LegModelsFn`` on the concatenated system -- block-diagonal over series, and over models when there
+    are several (zero coupling between them) -- in chunks of whole models (MODELS_BACKWARD_MAX_ROWS; without a model
+    axis the one chunk is the operands themselves): series-aware assembly, decompose_solve + inverse_blocks of K (its
+    diagonal Rs + the source's term, ``_models_diag``) and of Sigma^-1, block gradients weighted per row by the systems'
+    upstream gradients, series-aware adjoint.  Returns (gts, gG, gterm, grows, gv, gq) for ``needs``, the six
+    needs_input_grad of those inputs."""
+    need_ts, need_G, need_term, need_rows, need_v, need_q = needs
+    need_diag = need_term or need_rows
+    d, R = G.shape[-1], plan.R
+    gout = gout.to(G.dtype)
+    diag_term, diag_grads = _models_diag(source, G, term, rows, need_term, need_rows)
+
+    def spread(g, c):                                 # column c of [.., B, 4], spread over the rows of the chunk
+        return g[..., c].repeat_interleave(plan.lens, dim=-1, output_size=R).reshape(-1)
+
+    gq = spread(gout, 3).view(tuple(gout.shape[:-2]) + (R,)) if need_q else None
+    gts, gG, gterm, grows, gv = None, [], [], [], []
+    if need_ts or need_G or need_diag or need_v:
+        for _, _, sel in _model_chunks(G, R, MODELS_BACKWARD_MAX_ROWS):
+            g, Gc = _take(gout, sel), _take(G, sel)
+            lead = tuple(Gc.shape[:-2])
+            Rs, Os = _peg_precision_models(ts, Gc, plan.cut)
+            gm, gl = spread(g, 0), spread(g, 1)
+            dec, w = cr.decompose_solve((Rs.view(lead + (R, d, d)) + diag_term(sel)).view(-1, d, d), Os, _take(v, sel).reshape(-1, d))
+            if need_v:
+                gv.append((2 * gm.unsqueeze(-1) * w).view(lead + (R, d)))
+            if need_ts or need_G or need_diag:
+                Sd, So = cr.inverse_blocks(dec)
+                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
+                if need_diag:
+                    gt, gr = diag_grads(sel, gR.view(lead + (R, d, d)))
+                    gterm.append(gt)
+                    grows.append(gr)
+                if need_ts or need_G:
+                    # (the entries of gO between two models hold whatever the zero coupling gives: never read)
+                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
+                    if Rs.shape[0] > 1:      # (one row: its block is I whatever G and ts are)
+                        gs = spread(g, 2)
+                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
+                        gR = gR + gs.view(-1, 1, 1) * Sd0
+                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
+                    gGc, gtsc = _peg_precision_adjoint_models(ts, Gc, plan.cut, gR, gO, need_ts)
+                    if need_G:
+                        gG.append(gGc)
+                    if need_ts:
+                        gts = gtsc if gts is None else gts + gtsc          # chunks in ascending order
+    gG, gv = (_cat_chunks(p) if p else None for p in (gG, gv))
+    gterm, grows = (_cat_chunks(p) if p and p[0] is not None else None for p in (gterm, grows))
+    return gts, gG, gterm, grows, gv, gq
 
 
 def _reductions_by_source(forms, ts, G, source, term, rows, v, q, plan):
@@ -558,57 +710,29 @@ def _reductions_by_source(forms, ts, G, source, term, rows, v, q, plan):
     return forms[source](ts, G, term, rows, v, q, plan)
 
 
-class _LegBatchFn(torch.autograd.Function):
-    """``apply(ts, G, term, rows, v, q, source, plan)``, with (source, term, rows) as in ``_leg_pair_raw``.  Forward: the
-    batched reductions of that source (one launch).  Backward: the concatenated system of all series, which is
-    block-diagonal (zero coupling between series): series-aware assembly, decompose_solve + inverse_blocks of K (its
-    diagonal Rs + the source's term, ``_batch_diag``) and of Sigma^-1, block gradients weighted per row by the series'
-    upstream gradients, series-aware adjoint.  ``rows`` gets a gradient for the weighted source alone."""
+class _LegModelsFn(torch.autograd.Function):
+    """``apply(ts, G, term, rows, v, q, source, plan)``, with (source, term, rows) as in ``_leg_pair_raw`` and, for M
+    models over the batch, a leading model axis on G, term, v, q and on the weights.  Forward: the batched reductions of
+    that source, every (model, series) in one launch.  Backward: ``_models_backward``.  ``rows`` gets a gradient for the
+    weighted source alone."""
 
     @staticmethod
     def forward(ctx, ts, G, term, rows, v, q, source, plan):
         ctx.plan, ctx.source = plan, source
         ctx.save_for_backward(ts, G, term, rows, v)
-        forms = (leg_loglik_batch_reductions, leg_loglik_batch_reductions_obs, leg_loglik_batch_reductions_w)
+        forms = ((leg_loglik_models_reductions, leg_loglik_models_reductions_obs, leg_loglik_models_reductions_w)
+                 if G.dim() == 3 else
+                 (leg_loglik_batch_reductions, leg_loglik_batch_reductions_obs, leg_loglik_batch_reductions_w))
         out, info = _reductions_by_source(forms, ts.detach(), G.detach(), source, term.detach(),
                                           None if rows is None else rows.detach(), v.detach(), q.detach(), plan)
         if cr.CHECK_POSITIVE_DEFINITE:
-            _raise_batch_not_pd(info)
+            _raise_not_pd(info)
         return out.to(G.dtype)
 
     @staticmethod
     def backward(ctx, gout):
         ts, G, term, rows, v = ctx.saved_tensors
-        plan = ctx.plan
-        need_ts, need_G, need_term, need_rows, need_v, need_q = ctx.needs_input_grad[:6]
-        need_diag = need_term or need_rows
-        gts = gG = gterm = grows = gv = gq = None
-        gout = gout.to(G.dtype)
-        if need_q:
-            gq = plan.per_row(gout[:, 3])
-        if need_ts or need_G or need_diag or need_v:
-            diag_term, diag_grads = _batch_diag(ctx.source, G, term, rows, need_term, need_rows)
-            Rs, Os = _peg_precision_seg(ts, G, plan.cut)
-            gm, gl = plan.per_row(gout[:, 0]), plan.per_row(gout[:, 1])
-            dec, w = cr.decompose_solve(Rs + diag_term(), Os, v)
-            if need_v:
-                gv = 2 * gm.unsqueeze(-1) * w
-            if need_ts or need_G or need_diag:
-                Sd, So = cr.inverse_blocks(dec)
-                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
-                if need_diag:
-                    gterm, grows = diag_grads(gR)
-                if need_ts or need_G:
-                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
-                    if plan.R > 1:           # (one row: its block is I whatever G and ts are)
-                        gs = plan.per_row(gout[:, 2])
-                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
-                        gR = gR + gs.view(-1, 1, 1) * Sd0
-                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
-                    gG, gts = _peg_precision_adjoint_seg(ts, G, plan.cut, gR, gO, need_ts)
-                    if not need_G:
-                        gG = None
-        return gts, gG, gterm, grows, gv, gq, None, None
+        return _models_backward(ctx.needs_input_grad[:6], ctx.plan, ctx.source, ts, G, term, rows, v, gout) + (None, None)
 
 
 def _log_likelihood_per_series(m, ts, xs, lengths, observed=None, noise_var=None):
@@ -647,6 +771,24 @@ def _batch_like_xs(t, spec, xs_shape, dense):
     return t
 
 
+def _batch_args(obs, ts, xs, lengths, observed, noise_var, flat=False):
+    """Everything a batched call on a model of ``obs`` channels checks before it launches anything: (ts [R], xs [R, obs],
+    lengths, observed [R, obs] or None, noise_var [R, obs] / [R] or None, dense, (B, n) of the dense layout or None).
+    ``flat``: a wrong channel count prints the shape of xs [R, obs] (the text of the many-model calls), not the caller's."""
+    dense = lengths is None
+    xs_shape = tuple(xs.shape)
+    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    if observed is not None:
+        observed = _batch_like_xs(observed, _OBSERVED, xs_shape, dense)
+    if noise_var is not None:
+        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
+    if xs.shape[1] != obs:
+        raise ValueError("xs must have %d channels, got %s" % (obs, tuple(xs.shape) if flat else xs_shape))
+    if observed is not None:
+        observed = _observed_2d(observed, obs)
+    return ts, xs, lengths, observed, noise_var, dense, (xs_shape[:2] if dense else None)
+
+
 def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None):
     """log p(xs_b | ts_b) of the LEG model for B independent series (models.py:301-372 for each), as a [B] tensor of
     the model's dtype; ``out.sum()`` is what a training step over the batch minimises.
@@ -678,18 +820,10 @@ def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None)
     is built in registers from obs_dim (obs_dim + 1) / 2 numbers; ``observation_weights`` for the operands),
     differentiable in noise_var as well, the same fallbacks and errors, and nothing read on the host when
     ``cr.CHECK_POSITIVE_DEFINITE`` is off."""
-    dense = lengths is None
-    xs_shape = xs.shape
-    ts, xs, lengths = _batch_layout(ts, xs, lengths)
-    if observed is not None or noise_var is not None:
-        if observed is not None:
-            observed = _batch_like_xs(observed, _OBSERVED, xs_shape, dense)
-        if noise_var is not None:
-            noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
-        if xs.shape[1] != m.B.shape[0]:
-            raise ValueError("xs must have %d channels, got %s" % (m.B.shape[0], tuple(xs_shape)))
-        if observed is not None:
-            observed = _observed_2d(observed, xs.shape[1])
+    if observed is None and noise_var is None:
+        ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    else:
+        ts, xs, lengths, observed, noise_var = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)[:5]
     G = m.G
     dt = G.dtype
     if not lengths:
@@ -716,7 +850,7 @@ def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None)
         v = (xl @ m.B).to(dt).contiguous()
         q = (xl * xs).sum(-1).to(dt).contiguous()
         source, term, rows = _hip.ROWS_PLAIN, (m.B.T @ Li @ m.B).to(dt).contiguous(), None
-    red = _LegBatchFn.apply(ts.to(dt).contiguous(), G.contiguous(), term, rows, v, q, source, plan)
+    red = _LegModelsFn.apply(ts.to(dt).contiguous(), G.contiguous(), term, rows, v, q, source, plan)
     if source == _hip.ROWS_PLAIN:
         llt_det = torch.log(2 * math.pi * LLT[0, 0]) if LLT.shape[0] == 1 else torch.logdet(2 * math.pi * LLT)
         n = plan.lens.to(dt)
@@ -729,12 +863,6 @@ def log_likelihood_batch(m, ts, xs, lengths=None, observed=None, noise_var=None)
 # the components of a mixture) on the same B series.  Forward: grid (B, 2, M) of cgps_leg_loglik_models, one launch.
 # Backward: the block-diagonal system "model 0's batch, then model 1's batch, ..." of M R rows, assembled by
 # cgps_peg_precision_models from the one ts and the M generators, and its adjoint cgps_peg_precision_adjoint_models.
-MODELS_BACKWARD_MAX_ROWS = 1 << 22
-"""The backward of ``log_likelihood_models`` runs in chunks of whole models whose concatenated rows stay under this
-(a chunk always holds at least one model): about ten [rows, d, d] arrays are live at once, 0.84 GB each for a full
-chunk at d = 5 in fp64."""
-
-
 def _contract(a, b):
     """a [..., p, q] times b [..., q, r] for a small q, as q outer products added up in ascending order with plain
     elementwise multiplies and adds: every entry is rounded the same way whatever the other dimensions are, so a
@@ -761,36 +889,6 @@ def _spd_inverse_logdet(S):
         aug = aug - aug[:, :, j, None] * row.unsqueeze(1)        # clears column j everywhere, row j included
         aug = torch.cat([aug[:, :j], row.unsqueeze(1), aug[:, j + 1:]], 1)
     return aug[:, :, o:], logdet
-
-
-def _peg_precision_models(ts, G, cut):
-    """Blocks of the PEG precision of the same rows under G[m, d, d], model after model (cgps_peg_precision_models):
-    Rs [m R, d, d], Os [m R - 1, d, d] with zero blocks between two models.  No autograd graph."""
-    m, d, R = G.shape[0], G.shape[1], ts.shape[0]
-    Rs = torch.empty(m * R, d, d, dtype=G.dtype, device=G.device)
-    Os = torch.empty(m * R - 1, d, d, dtype=G.dtype, device=G.device)
-    info = torch.zeros(1, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_peg_precision_models(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), R, m, d, _hip.dtype_code(G.dtype),
-                                                    _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
-    return Rs, Os
-
-
-def _peg_precision_adjoint_models(ts, G, cut, gRs, gOs, want_ts):
-    """(d loss / d G[m, d, d], d loss / d ts [R] or None) through cgps_peg_precision_adjoint_models: every model's
-    partial sums added per model, the models' gradients in ts added over the models."""
-    m, d, R = G.shape[0], G.shape[1], ts.shape[0]
-    if R < 2:
-        return torch.zeros_like(G), (torch.zeros_like(ts) if want_ts else None)
-    part = torch.empty(m, (R - 1 + 63) // 64, d, d, dtype=G.dtype, device=G.device)
-    gtau = torch.empty(m, R - 1, dtype=G.dtype, device=G.device) if want_ts else None
-    _hip.check(_hip.lib().cgps_peg_precision_adjoint_models(
-        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), R, m, d, _hip.dtype_code(G.dtype), _hip.ptr(gRs.contiguous()),
-        _hip.ptr(gOs.contiguous()), _hip.ptr(part), _hip.ptr(gtau), _hip.stream_ptr()))
-    gts = None
-    if want_ts:
-        z = gtau.new_zeros(m, 1)
-        gts = (torch.cat([z, gtau], 1) - torch.cat([gtau, z], 1)).sum(0)
-    return part.sum(1), gts
 
 
 def _check_models_rhs(v, q, M, R, d):
@@ -840,138 +938,6 @@ def leg_loglik_models_reductions_w(ts, G, basis, weights, v, q, plan):
     _check_models_rhs(v, q, M, plan.R, d)
     _check_basis_weights(basis, weights, dt)
     return _leg_rows_reductions(ts, G, _hip.ROWS_WEIGHTED, basis.contiguous(), weights.contiguous(), v, q, plan)
-
-
-def _raise_models_not_pd(info):
-    bad = info.cpu()
-    hits = torch.nonzero(bad.amax(2)).tolist()
-    if hits:
-        k, b = hits[0]
-        code = int(bad[k, b, 0]) or int(bad[k, b, 1])
-        raise cr.NotPSDError("LEG models: model %d, series %d: a block near its row %d is not positive definite "
-                             "(or a time gap has zero length)" % (k, b, code - 1))
-
-
-def _rows_product_models(a, b, rows=4096):
-    """``_rows_product`` per model: a [m, R, p] and b [m, R, q] give a^T b [m, p, q], the rows in chunks of ``rows`` added
-    up by one reduction in a fixed order, plus the product of the remainder."""
-    m, R = a.shape[0], a.shape[1]
-    C = R // rows
-    out = torch.bmm(a[:, C * rows:].transpose(1, 2), b[:, C * rows:])
-    if C:
-        out = out + torch.bmm(a[:, :C * rows].reshape(m * C, rows, -1).transpose(1, 2),
-                              b[:, :C * rows].reshape(m * C, rows, -1)).view(m, C, a.shape[2], b.shape[2]).sum(1)
-    return out
-
-
-def _models_diag(source, G, term, rows, R, need_term, need_rows):
-    """``_batch_diag`` for the chunked backward over whole models: diag_term(k0, k1) is what K's diagonal adds to
-    Rs [m, R, d, d] for the models k0 .. k1 - 1, diag_grads(k0, k1, gR) files the chunk's block gradients gR [m, R, d, d]
-    into the third and fourth value, d loss / d term and d loss / d rows (None where not wanted)."""
-    d = G.shape[1]
-    gterm = torch.empty_like(term) if need_term else None
-    if source == _hip.ROWS_PLAIN:                                # model k's one block, broadcast over its rows
-        def plain_grads(k0, k1, gR):
-            gterm[k0:k1] = gR.sum(1)
-        return (lambda k0, k1: term[k0:k1].unsqueeze(1)), plain_grads, gterm, None
-    if source == _hip.ROWS_TABLE:
-        # row i of model k adds A_table[k][idx[i]]; the gradient of A_table[k] is the per-pattern sum of model k's row
-        # gradients, a product with the one-hot matrix of the pattern that all models share (no scatter: ``index_add_``
-        # adds with atomics, in no fixed order)
-        P = term.shape[1]
-        idx = rows.long().clamp(max=P - 1)                       # the kernel's clamp
-        codes = torch.arange(P, device=idx.device).unsqueeze(1)
-        step = max(1024, (1 << 24) // P)                         # rows per product: the one-hot matrix stays small
-
-        def table_grads(k0, k1, gR):
-            acc = torch.zeros(k1 - k0, P, d * d, dtype=G.dtype, device=G.device)
-            for s in range(0, R, step):                          # (one product unless P * R > 2^24)
-                onehot = (idx[s:s + step].unsqueeze(0) == codes).to(G.dtype)
-                acc = acc + torch.matmul(onehot, gR[:, s:s + step].reshape(k1 - k0, -1, d * d))
-            gterm[k0:k1] = acc.view(k1 - k0, P, d, d)
-        return (lambda k0, k1: term[k0:k1][:, idx]), table_grads, gterm, None
-    # row i of model k adds sum_j weights[k, i, j] basis[k, j]; model k's gR_i go to its basis as sum_i weights[k, i, j]
-    # gR_i and to its weights as <gR_i, basis[k, j]>, both plain matrix products per model
-    Kb = term.shape[1]
-    grows = torch.empty_like(rows) if need_rows else None
-
-    def weighted_grads(k0, k1, gR):
-        gR = gR.reshape(k1 - k0, R, d * d)
-        if need_term:
-            gterm[k0:k1] = _rows_product_models(rows[k0:k1], gR).view(k1 - k0, Kb, d, d)
-        if need_rows:
-            grows[k0:k1] = torch.bmm(gR, term[k0:k1].reshape(k1 - k0, Kb, d * d).transpose(1, 2))
-    return (lambda k0, k1: torch.einsum("mrk,mkij->mrij", rows[k0:k1], term[k0:k1])), weighted_grads, gterm, grows
-
-
-def _models_backward(needs, plan, source, ts, G, term, rows, v, gout):
-    """``_LegBatchFn``'s backward on the concatenated system of all models' batches, block-diagonal over models and series,
-    in chunks of whole models (MODELS_BACKWARD_MAX_ROWS).  K's diagonal is Rs + the source's term (``_models_diag``).
-    Returns (gts, gG, gterm, grows, gv, gq) for ``needs``, the six needs_input_grad of those inputs."""
-    need_ts, need_G, need_term, need_rows, need_v, need_q = needs
-    need_diag = need_term or need_rows
-    M, d, R = G.shape[0], G.shape[1], plan.R
-    gout = gout.to(G.dtype)
-    diag_term, diag_grads, gterm, grows = _models_diag(source, G, term, rows, R, need_term, need_rows)
-
-    def spread(g, c):                                 # column c of a chunk's [m, B, 4], spread over the m R rows
-        return g[:, :, c].repeat_interleave(plan.lens, dim=1, output_size=R).reshape(-1)
-
-    gq = spread(gout, 3).view(M, R) if need_q else None
-    gts = torch.zeros_like(ts) if need_ts else None
-    gG = torch.empty_like(G) if need_G else None
-    gv = torch.empty_like(v) if need_v else None
-    if need_ts or need_G or need_diag or need_v:
-        per = max(1, MODELS_BACKWARD_MAX_ROWS // R)
-        for k0 in range(0, M, per):
-            k1 = min(M, k0 + per)
-            m, g, Gc = k1 - k0, gout[k0:k1], G[k0:k1]
-            Rs, Os = _peg_precision_models(ts, Gc, plan.cut)
-            gm, gl = spread(g, 0), spread(g, 1)
-            dec, w = cr.decompose_solve((Rs.view(m, R, d, d) + diag_term(k0, k1)).view(m * R, d, d), Os,
-                                        v[k0:k1].reshape(m * R, d))
-            if need_v:
-                gv[k0:k1] = (2 * gm.unsqueeze(-1) * w).view(m, R, d)
-            if need_ts or need_G or need_diag:
-                Sd, So = cr.inverse_blocks(dec)
-                gR = gl.view(-1, 1, 1) * Sd - gm.view(-1, 1, 1) * (w.unsqueeze(-1) * w.unsqueeze(-2))
-                if need_diag:
-                    diag_grads(k0, k1, gR.view(m, R, d, d))
-                if need_ts or need_G:
-                    # (the entries of gO between two models hold whatever the zero coupling gives: never read)
-                    gO = 2 * (gl[1:].view(-1, 1, 1) * So - gm[1:].view(-1, 1, 1) * (w[1:].unsqueeze(-1) * w[:-1].unsqueeze(-2)))
-                    if m * R > 1:        # (one row: its block is I whatever G and ts are)
-                        gs = spread(g, 2)
-                        Sd0, So0 = cr.inverse_blocks(cr.decompose(Rs, Os))     # the prior precision's log-det
-                        gR = gR + gs.view(-1, 1, 1) * Sd0
-                        gO = gO + 2 * gs[1:].view(-1, 1, 1) * So0
-                    gGc, gtsc = _peg_precision_adjoint_models(ts, Gc, plan.cut, gR, gO, need_ts)
-                    if need_G:
-                        gG[k0:k1] = gGc
-                    if need_ts:
-                        gts = gts + gtsc                      # chunks in ascending order
-    return gts, gG, gterm, grows, gv, gq
-
-
-class _LegModelsFn(torch.autograd.Function):
-    """``_LegBatchFn`` for M models over one batch, called the same way with a leading model axis on G, term, v, q and on
-    the weights.  Forward: the reductions of every (model, series) in one launch.  Backward: ``_models_backward``."""
-
-    @staticmethod
-    def forward(ctx, ts, G, term, rows, v, q, source, plan):
-        ctx.plan, ctx.source = plan, source
-        ctx.save_for_backward(ts, G, term, rows, v)
-        forms = (leg_loglik_models_reductions, leg_loglik_models_reductions_obs, leg_loglik_models_reductions_w)
-        out, info = _reductions_by_source(forms, ts.detach(), G.detach(), source, term.detach(),
-                                          None if rows is None else rows.detach(), v.detach(), q.detach(), plan)
-        if cr.CHECK_POSITIVE_DEFINITE:
-            _raise_models_not_pd(info)
-        return out.to(G.dtype)
-
-    @staticmethod
-    def backward(ctx, gout):
-        ts, G, term, rows, v = ctx.saved_tensors
-        return _models_backward(ctx.needs_input_grad[:6], ctx.plan, ctx.source, ts, G, term, rows, v, gout) + (None, None)
 
 
 def _models_pattern_tables(Bm, LLT, o, dt):
@@ -1038,25 +1004,20 @@ def _models_operands(ms):
     return ms, tuple(torch.stack([getattr(m, name) for m in ms]) for name in ("N", "R", "B", "Lambda"))
 
 
+def _models_args(ms, ts, xs, lengths, observed, noise_var):
+    """``_batch_args`` of a call over many models: (ms, (N, R, B, Lambda) stacked), then its seven values."""
+    ms, mats = _models_operands(ms)
+    return (ms, mats) + _batch_args(mats[2].shape[1], ts, xs, lengths, observed, noise_var, flat=True)
+
+
 def _models_setup(ms, ts, xs, lengths, observed=None, noise_var=None):
     """What ``log_likelihood_models`` and ``log_likelihood_models_observed`` do first: the stacked matrices, the layout and
     its checks, and the two ways a call ends early -- an empty batch, and the block sizes and devices without a batched
     kernel, which take one ``log_likelihood_batch`` per model.  Returns (result, None) then, and otherwise
     (None, (ts, xs, observed, noise_var, plan, Bm, G, LLT)) with xs [R, obs], observed [R, obs] or None, noise_var [R, obs],
     [R] or None, and the models' G [M, d, d] and LLT [M, obs, obs]."""
-    ms, (Nm, Rm, Bm, Lm) = _models_operands(ms)
-    dense = lengths is None
-    xs_shape = xs.shape
-    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    ms, (Nm, Rm, Bm, Lm), ts, xs, lengths, observed, noise_var = _models_args(ms, ts, xs, lengths, observed, noise_var)[:7]
     M, d, o, dt = len(ms), Nm.shape[1], Bm.shape[1], Nm.dtype
-    if observed is not None:
-        observed = _batch_like_xs(observed, _OBSERVED, xs_shape, dense)
-    if noise_var is not None:
-        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
-    if xs.shape[1] != o:
-        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
-    if observed is not None:
-        observed = _observed_2d(observed, o)
     if not lengths:
         return torch.empty(M, 0, dtype=dt, device=ts.device), None
     if not batch_supported(ts, Nm[0]):
@@ -1616,22 +1577,17 @@ def insample_posterior(m, ts, xs, observed=None, noise_var=None):
     return mean, cr.inverse_blocks(dec)
 
 
-# ---- the posterior of many series at once ------------------------------------------------------------------------
-def _batch_posterior_args(m, ts, xs, lengths, observed, noise_var):
-    """Everything ``insample_posterior_batch`` checks before it launches anything: (ts [R], xs [R, obs], lengths,
-    observed [R, obs] or None, noise_var [R, obs] / [R] or None, dense, (B, n) of the dense layout or None)."""
-    dense = lengths is None
-    xs_shape = tuple(xs.shape)
-    ts, xs, lengths = _batch_layout(ts, xs, lengths)
-    if xs.shape[1] != m.B.shape[0]:
-        raise ValueError("xs must have %d channels, got %s" % (m.B.shape[0], xs_shape))
-    if observed is not None:
-        observed = _observed_2d(_batch_like_xs(observed, _OBSERVED, xs_shape, dense), xs.shape[1])
-    if noise_var is not None:
-        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
-        if noise_var.dim() == 2 and noise_var.shape[1] != xs.shape[1]:
-            raise ValueError("noise_var must have %d channels, got %s" % (xs.shape[1], tuple(noise_var.shape)))
-    return ts, xs, lengths, observed, noise_var, dense, (xs_shape[:2] if dense else None)
+# ---- the posterior of many series at once, under one model or many -------------------------------------------------
+# The concatenated system of all series is block-diagonal, and so is the system "model 0's batch, then model 1's batch,
+# ..." that the backward of ``log_likelihood_models`` already reduces: one factorisation and one selected inverse of it
+# are the posterior of every (model, series).  cgps_leg_posterior_blocks_seg / _models assemble it with every model's own
+# row terms, cgps_leg_intercast_seg / _models (predict.py) predict from it.
+MODELS_POSTERIOR_MAX_ROWS = MODELS_BACKWARD_MAX_ROWS
+"""``insample_posterior_models`` and the predictions built on it run in chunks of whole models whose concatenated rows
+stay under this (a chunk always holds at least one model).  Live per row of a chunk: K's two block arrays [rows, d, d],
+the factor's three packed arrays of about the same size together with the reduction's workspace, the two covariance
+arrays [rows, d, d], and v and the mean [rows, d] -- about eight [rows, d, d] arrays, 0.84 GB each for a full chunk at
+d = 5 in fp64; with ``noise_var`` the weights [rows, obs_dim (obs_dim + 1) / 2] of all models as well."""
 
 
 def _posterior_batch_supported(ts, G):
@@ -1639,32 +1595,111 @@ def _posterior_batch_supported(ts, G):
     return G.is_cuda and ts.is_cuda and G.dtype in (torch.float32, torch.float64) and 1 <= G.shape[0] <= 8
 
 
-def _series_of_row(plan, row):
-    """(series, local row) of a row of the concatenated batch."""
-    import bisect
-    b = min(max(bisect.bisect_right(plan.starts, row) - 1, 0), plan.B - 1)
-    return b, row - plan.starts[b]
-
-
-def _posterior_blocks_seg(ts, G, cut, source, term, rows=None):
+def _posterior_blocks_models(ts, G, cut, source, term, rows=None):
     """(K_Rs, Os, info) of concatenated series with every row's term added inside the assembly kernel
     (cgps_leg_posterior_blocks_seg): K's diagonal blocks are written once.  source: _hip.ROWS_PLAIN (term [d, d]),
-    ROWS_TABLE (term [entries, d, d], rows = pattern bytes [n]) or ROWS_WEIGHTED (term = basis [Kb, d, d], rows = weights
-    [n, Kb]); cut may be None (one series).  Contiguous operands of G's dtype.  No autograd graph."""
-    n, d = ts.shape[0], G.shape[0]
-    entries = 0 if source == _hip.ROWS_PLAIN else term.shape[0]
+    ROWS_TABLE (term [entries, d, d], rows = pattern bytes [R]) or ROWS_WEIGHTED (term = basis [Kb, d, d], rows = weights
+    [R, Kb]); cut may be None (one series).  With G [m, d, d] the same rows under every model
+    (cgps_leg_posterior_blocks_models): K_Rs [m R, d, d], Os [m R - 1, d, d] with zero blocks between two models, term and
+    the weights with a leading model axis, the pattern bytes shared by the models.  Contiguous operands of G's dtype.
+    No autograd graph."""
+    R, d, lib = ts.shape[0], G.shape[-1], _hip.lib()
+    fn, count = ((lib.cgps_leg_posterior_blocks_models, (R, G.shape[0])) if G.dim() == 3 else
+                 (lib.cgps_leg_posterior_blocks_seg, (R,)))
+    n = math.prod(count)
+    entries = 0 if source == _hip.ROWS_PLAIN else term.shape[-3]
     K_Rs = torch.empty(n, d, d, dtype=G.dtype, device=G.device)
     Os = torch.empty(max(n - 1, 0), d, d, dtype=G.dtype, device=G.device)
     info = torch.zeros(1, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_posterior_blocks_seg(
-        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), n, d, _hip.dtype_code(G.dtype), source, _hip.ptr(term), entries,
-        _hip.ptr(rows), _hip.ptr(K_Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
+    _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), *count, d, _hip.dtype_code(G.dtype), source, _hip.ptr(term),
+                  entries, _hip.ptr(rows), _hip.ptr(K_Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
     return K_Rs, Os, info
+
+
+_posterior_blocks_seg = _posterior_blocks_models        # the same function: the name of its form without a model axis
+
+
+def _posterior_blocks_composed(ts, G, cut, source, term, rows=None):
+    """What ``_posterior_blocks_models`` replaces for one model, for A/B timing (CGPS_LEG_BLOCKS_COMPOSED=1):
+    cgps_peg_precision_seg, then the gather or einsum and the add as torch passes."""
+    info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    Rs, Os = _peg_precision_models(ts, G, cut, info)
+    if source == _hip.ROWS_WEIGHTED:
+        return Rs.add_(torch.einsum("nk,kij->nij", rows, term)), Os, info
+    if source == _hip.ROWS_TABLE:
+        return Rs.add_(term[rows.long().clamp(max=term.shape[0] - 1)]), Os, info
+    return Rs.add_(term.unsqueeze(0)), Os, info
+
+
+def _posterior_system_rows(plan, ts, G, source, term, rows, k0):
+    """(K_Rs, K_Os) of the concatenated posterior system of one model's batch or of a chunk of models: the series-aware
+    assembly (zero coupling across a series boundary, the gap there never evaluated) with the rows' terms added inside it
+    (``_posterior_blocks_models``).  With G [d, d], CGPS_LEG_BLOCKS_COMPOSED=1 takes the composition it replaces instead,
+    for A/B timing.  With ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series (k0 as
+    in ``_row_error``)."""
+    composed = G.dim() == 2 and os.environ.get("CGPS_LEG_BLOCKS_COMPOSED") == "1"
+    blocks = _posterior_blocks_composed if composed else _posterior_blocks_models
+    K_Rs, K_Os, info = blocks(ts, G, plan.cut, source, term, rows)
+    _check_gaps(info, plan, k0, _GAP_BLOCK)
+    return K_Rs, K_Os
+
+
+def _failed_model_series(plan, m, K_Rs, K_Os, row):
+    """(model of the chunk, series, local row) of a factorisation that failed near ``row`` of the concatenated system.
+    The factor's info word is the SMALLEST row whose pivot was not positive, and once a block has failed its NaN climbs the
+    levels of the concatenated reduction through the zero couplings (0 * NaN) and fails pivots of earlier series and
+    models too: the word can name a row in front of the one that broke.  So, on this path only, every (model, series) is
+    reduced on its own (``cr.mahal_and_det_batch``: one workgroup per system, systems never meet) and the first that
+    fails is named; if none does there, ``row`` is mapped through ``_locate_row``."""
+    try:
+        cr.mahal_and_det_batch(K_Rs, K_Os, None, lengths=list(plan.lengths) * m)
+    except cr.NotPSDError as e:
+        system = getattr(e, "system", None)
+        if system is not None:
+            return system // plan.B, system % plan.B, e.row
+    return _locate_row(plan, row)
+
+
+def _factor_error(e, plan, K_Rs, K_Os, k0):
+    """The NotPSDError ``e`` of a factorisation of the concatenated system (k0 as in ``_row_error``) with its system
+    named; ``e`` itself when it names no row."""
+    row = getattr(e, "row", None)
+    if row is None:
+        return e
+    if k0 is None:                       # (kept as it is: one model's batch maps the factor's word, many models re-reduce)
+        return _row_error(plan, row, None, _NOT_PD)
+    k, b, r = _failed_model_series(plan, K_Rs.shape[0] // plan.R, K_Rs, K_Os, row)
+    return _not_pd_error(k0 + k, b, _NOT_PD % r)
+
+
+def _posterior_models_chunks(plan, ts, G, source, term, rows, v):
+    """The posterior of the batch under every model in chunks of whole models (MODELS_POSTERIOR_MAX_ROWS): yields (k0, k1,
+    mean [m R, d], cov_diag [m R, d, d], cov_off [m R - 1, d, d]) of the models k0 .. k1 - 1, the entries of cov_off
+    between two series or two models exactly zero.  One assembly launch, one ``cr.decompose_solve`` and one
+    ``cr.inverse_blocks`` per chunk.  G [d, d]: the one chunk (0, 1, ...) of one model's batch, whose assembly
+    CGPS_LEG_BLOCKS_COMPOSED=1 composes from torch passes.  With ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap or a
+    block that is not positive definite raises NotPSDError naming its (model and) series."""
+    named = G.dim() == 3
+    for k0, k1, sel in _model_chunks(G, plan.R, MODELS_POSTERIOR_MAX_ROWS):
+        K_Rs, K_Os = _posterior_system_rows(plan, ts, _take(G, sel), source, _take(term, sel),
+                                            rows if source != _hip.ROWS_WEIGHTED else _take(rows, sel), k0 if named else None)
+        try:
+            dec, mean = cr.decompose_solve(K_Rs, K_Os, _take(v, sel).reshape(K_Rs.shape[0], -1))
+        except cr.NotPSDError as e:
+            raise _factor_error(e, plan, K_Rs, K_Os, k0 if named else None) from None
+        if named:                        # many models: room for the inverse and for the next chunk.  One model's batch keeps
+            del K_Rs, K_Os               # its blocks to the end: freed here, the allocator carves them up for the smaller
+        Sd, So = cr.inverse_blocks(dec)  # tensors that follow, and the launch-bound B = 1 call measured 10-20 us slower
+        if named:
+            del dec
+        if (k1 - k0) * plan.B > 1:
+            So.index_fill_(0, plan.boundary_rows(k1 - k0), 0)      # (zero up to its sign or a failed system's NaN: exactly zero)
+        yield k0, k1, mean, Sd, So
 
 
 def _posterior_operands_batch(m, ts, xs, observed, noise_var):
     """(source, term, rows, v) of the concatenated posterior system: where the assembly takes a row's diagonal term from
-    (``_posterior_blocks_seg``) and the right-hand side v [R, d], contiguous and of G's dtype."""
+    (``_posterior_blocks_models``) and the right-hand side v [R, d], contiguous and of G's dtype."""
     dt = m.N.dtype
     if noise_var is not None:
         basis, weights, _, xl, _ = _noise_operands(m, ts, xs, observed, noise_var)
@@ -1677,58 +1712,6 @@ def _posterior_operands_batch(m, ts, xs, observed, noise_var):
         xl = xs @ Li
         source, term, rows = _hip.ROWS_PLAIN, (m.B.T @ Li @ m.B).to(dt).contiguous(), None
     return source, term, rows, (xl @ m.B).to(dt).contiguous()
-
-
-def _posterior_system_batch(m, ts, xs, observed, noise_var, plan):
-    """(K_Rs, K_Os, v) of the concatenated, block-diagonal posterior system of all series: ``_posterior_system`` with the
-    series-aware assembly (zero coupling across a series boundary, the gap there never evaluated) and the rows' terms
-    added inside it (cgps_leg_posterior_blocks_seg).  CGPS_LEG_BLOCKS_COMPOSED=1 takes the composition it replaces
-    instead -- cgps_peg_precision_seg, then the gather or einsum and the add as torch passes -- for A/B timing.  With
-    ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series."""
-    G = m.G
-    dt = G.dtype
-    source, term, rows, v = _posterior_operands_batch(m, ts, xs, observed, noise_var)
-    tsc, Gc = ts.to(dt).contiguous(), G.contiguous()
-    if os.environ.get("CGPS_LEG_BLOCKS_COMPOSED") == "1":
-        R, d = plan.R, G.shape[0]
-        Rs = torch.empty(R, d, d, dtype=dt, device=G.device)
-        Os = torch.empty(max(R - 1, 0), d, d, dtype=dt, device=G.device)
-        info = torch.zeros(1, dtype=torch.int32, device=G.device)
-        _hip.check(_hip.lib().cgps_peg_precision_seg(_hip.ptr(tsc), _hip.ptr(Gc), _hip.ptr(plan.cut), R, d, _hip.dtype_code(dt),
-                                                     _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
-        if source == _hip.ROWS_WEIGHTED:
-            K_Rs = Rs.add_(torch.einsum("nk,kij->nij", rows, term))
-        elif source == _hip.ROWS_TABLE:
-            K_Rs = Rs.add_(term[rows.long().clamp(max=term.shape[0] - 1)])
-        else:
-            K_Rs = Rs.add_(term.unsqueeze(0))
-    else:
-        K_Rs, Os, info = _posterior_blocks_seg(tsc, Gc, plan.cut, source, term, rows)
-    if cr.CHECK_POSITIVE_DEFINITE:
-        bad = int(info.item())
-        if bad:
-            b, r = _series_of_row(plan, bad - 1)
-            raise cr.NotPSDError("LEG batch: series %d: the time gap next to its row %d gives a singular PEG block "
-                                 "(zero-length gap?)" % (b, r))
-    return K_Rs, Os, v
-
-
-def _insample_posterior_flat(m, ts, xs, lengths, observed, noise_var):
-    """(mean [R, d], cov_diag [R, d, d], cov_off [R-1, d, d], plan) of the concatenated batch (already validated)."""
-    plan = _cached_batch_plan(lengths, m.N.device)
-    K_Rs, K_Os, v = _posterior_system_batch(m, ts, xs, observed, noise_var, plan)
-    try:
-        dec, mean = cr.decompose_solve(K_Rs, K_Os, v)
-    except cr.NotPSDError as e:
-        row = getattr(e, "row", None)
-        if row is None:
-            raise
-        b, r = _series_of_row(plan, row)
-        raise cr.NotPSDError("LEG batch: series %d: a block near its row %d is not positive definite" % (b, r)) from None
-    Sd, So = cr.inverse_blocks(dec)
-    if plan.B > 1:
-        So.index_fill_(0, plan.boundary_rows(), 0)           # (zero up to its sign or a failed series' NaN: exactly zero)
-    return mean, Sd, So, plan
 
 
 def _insample_posterior_per_series(m, ts, xs, lengths, observed, noise_var):
@@ -1754,8 +1737,18 @@ def _insample_posterior_per_series(m, ts, xs, lengths, observed, noise_var):
 def _posterior_flat(m, ts, xs, lengths, observed, noise_var):
     """(mean, cov_diag, cov_off) of the concatenated batch by whichever path the inputs get."""
     if _posterior_batch_supported(ts, m.G):
-        return _insample_posterior_flat(m, ts, xs, lengths, observed, noise_var)[:3]
+        return _posterior_flat_hip(m, ts, xs, lengths, observed, noise_var)[:3]
     return _insample_posterior_per_series(m, ts, xs, lengths, observed, noise_var)
+
+
+def _posterior_flat_hip(m, ts, xs, lengths, observed, noise_var):
+    """(mean [R, d], cov_diag [R, d, d], cov_off [R-1, d, d], plan) of the concatenated batch (already validated): the one
+    chunk of ``_posterior_models_chunks`` without a model axis."""
+    plan = _cached_batch_plan(lengths, m.N.device)
+    G = m.G
+    source, term, rows, v = _posterior_operands_batch(m, ts, xs, observed, noise_var)
+    (_, _, mean, Sd, So), = _posterior_models_chunks(plan, ts.to(G.dtype).contiguous(), G.contiguous(), source, term, rows, v)
+    return mean, Sd, So, plan
 
 
 def insample_posterior_batch(m, ts, xs, lengths=None, observed=None, noise_var=None):
@@ -1788,7 +1781,7 @@ def insample_posterior_batch(m, ts, xs, lengths=None, observed=None, noise_var=N
     CPU tensors, or a rank or dtype outside the kernels', go through ``insample_posterior`` series by series and behave
     as that does (there is no CPU implementation)."""
     with torch.no_grad():
-        ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        ts, xs, lengths, observed, noise_var, dense, bn = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
         d, dt = m.N.shape[0], m.N.dtype
         if not lengths:
             e = lambda *shape: torch.empty(shape, dtype=dt, device=ts.device)      # noqa: E731
@@ -1812,56 +1805,18 @@ def _dense_posterior(mean, Sd, So, B, n):
     return mean.reshape(B, n, d), (Sd.reshape(B, n, d, d), So)
 
 
-# ---- the posterior of many models over one batch -----------------------------------------------------------------
-# The models axis of the posterior: the system "model 0's batch, then model 1's batch, ..." that the backward of
-# ``log_likelihood_models`` already reduces is block-diagonal over models and series, so one factorisation and one
-# selected inverse of it are the posterior of every (model, series).  cgps_leg_posterior_blocks_models assembles it with
-# every model's own row terms, cgps_leg_intercast_models (predict.py) predicts from it.
-MODELS_POSTERIOR_MAX_ROWS = MODELS_BACKWARD_MAX_ROWS
-"""``insample_posterior_models`` and the predictions built on it run in chunks of whole models whose concatenated rows
-stay under this (a chunk always holds at least one model).  Live per row of a chunk: K's two block arrays [rows, d, d],
-the factor's three packed arrays of about the same size together with the reduction's workspace, the two covariance
-arrays [rows, d, d], and v and the mean [rows, d] -- about eight [rows, d, d] arrays, 0.84 GB each for a full chunk at
-d = 5 in fp64; with ``noise_var`` the weights [rows, obs_dim (obs_dim + 1) / 2] of all models as well."""
-
-
-def _posterior_blocks_models(ts, G, cut, source, term, rows=None):
-    """``_posterior_blocks_seg`` for the same rows under G[m, d, d] (cgps_leg_posterior_blocks_models): (K_Rs [m R, d, d],
-    Os [m R - 1, d, d] with zero blocks between two models, info).  source: _hip.ROWS_PLAIN (term [m, d, d]), ROWS_TABLE
-    (term [m, entries, d, d], rows = pattern bytes [R] shared by the models) or ROWS_WEIGHTED (term = basis [m, Kb, d, d],
-    rows = weights [m, R, Kb]).  Contiguous operands of G's dtype.  No autograd graph."""
-    m, d, R = G.shape[0], G.shape[1], ts.shape[0]
-    entries = 0 if source == _hip.ROWS_PLAIN else term.shape[1]
-    K_Rs = torch.empty(m * R, d, d, dtype=G.dtype, device=G.device)
-    Os = torch.empty(max(m * R - 1, 0), d, d, dtype=G.dtype, device=G.device)
-    info = torch.zeros(1, dtype=torch.int32, device=G.device)
-    _hip.check(_hip.lib().cgps_leg_posterior_blocks_models(
-        _hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), R, m, d, _hip.dtype_code(G.dtype), source, _hip.ptr(term), entries,
-        _hip.ptr(rows), _hip.ptr(K_Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
-    return K_Rs, Os, info
-
-
+# ---- the posterior of many models over one batch: its checks and its stacked operands --------------------------------
 def _models_posterior_args(ms, ts, xs, lengths, observed, noise_var):
     """Everything the posterior and prediction calls over many models check before they launch anything, with the
     ValueErrors of ``log_likelihood_models_observed``: (ms, (N, R, B, Lambda) stacked, ts [R], xs [R, obs], lengths,
     observed [R, obs] or None, noise_var [R, obs] / [R] or None, dense, (B, n) of the dense layout or None)."""
-    ms, mats = _models_operands(ms)
-    dense = lengths is None
-    xs_shape = tuple(xs.shape) if isinstance(xs, torch.Tensor) else ()
-    ts, xs, lengths = _batch_layout(ts, xs, lengths)
+    args = _models_args(ms, ts, xs, lengths, observed, noise_var)
+    mats, ts, lengths = args[1], args[2], args[4]
     o = mats[2].shape[1]
-    if observed is not None:
-        observed = _batch_like_xs(observed, _OBSERVED, xs_shape, dense)
-    if noise_var is not None:
-        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
-    if xs.shape[1] != o:
-        raise ValueError("xs must have %d channels, got %s" % (o, tuple(xs.shape)))
-    if observed is not None:
-        observed = _observed_2d(observed, o)
     if (lengths and _posterior_batch_supported(ts, mats[0][0]) and (observed is not None or noise_var is not None)
             and o > MAX_PATTERN_OBS):
         raise ValueError("observation patterns are tabulated for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, o))
-    return ms, mats, ts, xs, lengths, observed, noise_var, dense, (xs_shape[:2] if dense else None)
+    return args
 
 
 def _models_posterior_operands(mats, xs, observed, noise_var):
@@ -1888,73 +1843,6 @@ def _models_posterior_operands(mats, xs, observed, noise_var):
             source, term, rows = _hip.ROWS_TABLE, A_table.to(dt).contiguous(), pattern
         xl = _contract(xz.unsqueeze(0).unsqueeze(2), Li_rows).squeeze(2)        # x~^T Li per model and row
     return G.contiguous(), source, term, rows, _contract(xl, Bm).to(dt).contiguous()
-
-
-def _models_series_ends(plan, m):
-    """Device int64 [m B - 1]: the entries of the off-diagonal array of m models' concatenated batches that lie between two
-    series or two models.  Computed on the device from the plan's offsets (nothing copied from the host) and kept."""
-    kept = plan.__dict__.setdefault("_models_ends", {})
-    idx = kept.get(m)
-    if idx is None:
-        ends = plan.offsets[1:] - 1
-        idx = kept[m] = (torch.arange(m, device=ends.device).unsqueeze(1) * plan.R + ends).reshape(-1)[:-1].contiguous()
-    return idx
-
-
-def _models_row(plan, row):
-    """(model of the chunk, series, local row) of a row of the concatenated system of several models' batches."""
-    b, r = _series_of_row(plan, row % plan.R)
-    return row // plan.R, b, r
-
-
-def _failed_model_series(plan, m, K_Rs, K_Os, row):
-    """(model of the chunk, series, local row) of a factorisation that failed near ``row`` of the concatenated system.
-    The factor's info word is the SMALLEST row whose pivot was not positive, and once a block has failed its NaN climbs the
-    levels of the concatenated reduction through the zero couplings (0 * NaN) and fails pivots of earlier series and
-    models too: the word can name a row in front of the one that broke.  So, on this path only, every (model, series) is
-    reduced on its own (``cr.mahal_and_det_batch``: one workgroup per system, systems never meet) and the first that
-    fails is named; if none does there, ``row`` is mapped through k = row // R and ``_series_of_row``."""
-    try:
-        cr.mahal_and_det_batch(K_Rs, K_Os, None, lengths=list(plan.lengths) * m)
-    except cr.NotPSDError as e:
-        system = getattr(e, "system", None)
-        if system is not None:
-            return system // plan.B, system % plan.B, e.row
-    return _models_row(plan, row)
-
-
-def _posterior_models_chunks(plan, ts, G, source, term, rows, v):
-    """The posterior of every model in chunks of whole models (MODELS_POSTERIOR_MAX_ROWS): yields (k0, k1, mean [m R, d],
-    cov_diag [m R, d, d], cov_off [m R - 1, d, d]) of the models k0 .. k1 - 1, the entries of cov_off between two series
-    or two models exactly zero.  One assembly launch, one ``cr.decompose_solve`` and one ``cr.inverse_blocks`` per chunk."""
-    M, d, R = G.shape[0], G.shape[1], plan.R
-    per = max(1, MODELS_POSTERIOR_MAX_ROWS // R)
-    for k0 in range(0, M, per):
-        k1 = min(M, k0 + per)
-        m = k1 - k0
-        K_Rs, K_Os, info = _posterior_blocks_models(ts, G[k0:k1], plan.cut, source, term[k0:k1],
-                                                    rows if source != _hip.ROWS_WEIGHTED else rows[k0:k1])
-        if cr.CHECK_POSITIVE_DEFINITE:
-            bad = int(info.item())
-            if bad:
-                k, b, r = _models_row(plan, bad - 1)
-                raise cr.NotPSDError("LEG models: model %d, series %d: the time gap next to its row %d gives a singular PEG "
-                                     "block (zero-length gap?)" % (k0 + k, b, r))
-        try:
-            dec, mean = cr.decompose_solve(K_Rs, K_Os, v[k0:k1].reshape(m * R, d))
-        except cr.NotPSDError as e:
-            row = getattr(e, "row", None)
-            if row is None:
-                raise
-            k, b, r = _failed_model_series(plan, m, K_Rs, K_Os, row)
-            raise cr.NotPSDError("LEG models: model %d, series %d: a block near its row %d is not positive definite"
-                                 % (k0 + k, b, r)) from None
-        del K_Rs, K_Os
-        Sd, So = cr.inverse_blocks(dec)
-        del dec
-        if m * R > 1:
-            So.index_fill_(0, _models_series_ends(plan, m), 0)   # (zero up to its sign or a failed model's NaN: exactly zero)
-        yield k0, k1, mean, Sd, So
 
 
 def _posterior_models_per_model(ms, each):
@@ -2107,6 +1995,24 @@ def _loo_empty(lead, obs, leave, dt, device):
     return e(obs), (e(obs, obs) if leave else e(obs)), (e() if leave else e(obs))
 
 
+def _single_series_args(obs, ts, xs, observed, noise_var):
+    """What a call on one series of a model of ``obs`` channels checks before it launches anything; returns ``observed``
+    as bool [n, obs] or None."""
+    if ts.dim() != 1 or xs.dim() != 2 or xs.shape[0] != ts.shape[0] or xs.shape[1] != obs:
+        raise ValueError("one series wants ts[n] and xs[n, %d], got %s and %s" % (obs, tuple(ts.shape), tuple(xs.shape)))
+    n = ts.shape[0]
+    if observed is not None:
+        observed = _observed_2d(observed, obs)
+        if observed.shape[0] != n:
+            raise ValueError("observed has %d rows, xs has %d" % (observed.shape[0], n))
+    if noise_var is not None:
+        if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
+            raise ValueError("noise_var must be a floating-point tensor")
+        if noise_var.dim() not in (1, 2) or noise_var.shape[0] != n or (noise_var.dim() == 2 and noise_var.shape[1] != obs):
+            raise ValueError("noise_var must be [n] or [n, %d], got %s" % (obs, tuple(noise_var.shape)))
+    return observed
+
+
 def loo_predictive(m, ts, xs, observed=None, noise_var=None, leave="entry"):
     """Leave-one-out predictives of one series under a fitted model: ``LooPredictive(mean, var, logpdf, score)``.
 
@@ -2128,18 +2034,8 @@ def loo_predictive(m, ts, xs, observed=None, noise_var=None, leave="entry"):
     with torch.no_grad():
         obs = m.B.shape[0]
         lv = _loo_leave(leave, obs)
-        if ts.dim() != 1 or xs.dim() != 2 or xs.shape[0] != ts.shape[0] or xs.shape[1] != obs:
-            raise ValueError("one series wants ts[n] and xs[n, %d], got %s and %s" % (obs, tuple(ts.shape), tuple(xs.shape)))
+        observed = _single_series_args(obs, ts, xs, observed, noise_var)
         n, dt = ts.shape[0], m.N.dtype
-        if observed is not None:
-            observed = _observed_2d(observed, obs)
-            if observed.shape[0] != n:
-                raise ValueError("observed has %d rows, xs has %d" % (observed.shape[0], n))
-        if noise_var is not None:
-            if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
-                raise ValueError("noise_var must be a floating-point tensor")
-            if noise_var.dim() not in (1, 2) or noise_var.shape[0] != n or (noise_var.dim() == 2 and noise_var.shape[1] != obs):
-                raise ValueError("noise_var must be [n] or [n, %d], got %s" % (obs, tuple(noise_var.shape)))
         if n == 0:
             return LooPredictive(*_loo_empty((0,), obs, lv, dt, ts.device),
                                  torch.zeros((), dtype=torch.float64, device=ts.device))
@@ -2176,7 +2072,7 @@ def loo_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None,
     with torch.no_grad():
         obs = m.B.shape[0]
         lv = _loo_leave(leave, obs)
-        ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        ts, xs, lengths, observed, noise_var, dense, bn = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
         dt = m.N.dtype
         if not lengths:
             lead = (0, bn[1]) if dense else (0,)
@@ -2189,7 +2085,7 @@ def loo_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None,
         if cr.CHECK_POSITIVE_DEFINITE:
             bad = int(info.item())
             if bad:
-                b, r = _series_of_row(plan, bad - 1)
+                _, b, r = _locate_row(plan, bad - 1)
                 raise cr.NotPSDError("LEG leave-one-out: series %d: row %d: %s" % (b, r, _LOO_FAILED))
         om, ov, ol = om[0], ov[0], ol[0]
         if dense:
@@ -2241,7 +2137,7 @@ def loo_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=Non
                 if cr.CHECK_POSITIVE_DEFINITE:
                     bad = int(out[4].item())
                     if bad:
-                        k, b, r = _models_row(plan, bad - 1)
+                        k, b, r = _locate_row(plan, bad - 1)
                         raise cr.NotPSDError("LEG leave-one-out: model %d, series %d: row %d: %s" % (k0 + k, b, r, _LOO_FAILED))
                 parts.append(out[:4])
             om, ov, ol, score = (parts[0][j] if len(parts) == 1 else torch.cat([p[j] for p in parts]) for j in range(4))
@@ -2263,20 +2159,31 @@ _FILTER_FAILED = ("its one-step-ahead predictive does not exist (the covariance 
                   "definite -- a negative noise_var? --, its gap is negative, or a result is not finite)")
 
 
+def _filter_state_kind(init):
+    """``init`` (not None) checked as a ``FilterState``: a triple of tensors; ValueError otherwise."""
+    if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
+        raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
+
+
+def _filter_state(init, want, wants):
+    """``_filter_state_kind``, and the three shapes are ``want`` (an entry None: not looked at); ValueError otherwise,
+    ``wants`` saying what the call takes."""
+    _filter_state_kind(init)
+    got = tuple(tuple(t.shape) for t in init)
+    if any(w is not None and g != w for g, w in zip(got, want)):
+        raise ValueError("%s, got %s, %s and %s" % ((wants,) + got))
+    return init
+
+
 def _filter_init(init, lead, d, ts, starts, dt):
     """``init`` checked against the batch: (t0 [B], m0 lead + [d], P0 lead + [d, d]) of dtype ``dt``, contiguous, or None.
     ``lead`` is (B,) or (M, B); ``starts`` the first row of every series.  ValueError for the wrong kind, shape or device
     and for a state later than the first row of its series."""
     if init is None:
         return None
-    if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
-        raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
-    t0, m0, P0 = init
     B = lead[-1]
     want = ((B,), tuple(lead) + (d,), tuple(lead) + (d, d))
-    got = tuple(tuple(t.shape) for t in (t0, m0, P0))
-    if got != want:
-        raise ValueError("init wants t %s, mean %s and cov %s, got %s, %s and %s" % (want + got))
+    t0, m0, P0 = _filter_state(init, want, "init wants t %s, mean %s and cov %s" % want)
     if any(t.device != ts.device for t in (t0, m0, P0)) or not all(t.dtype.is_floating_point for t in (t0, m0, P0)):
         raise ValueError("init must hold floating-point tensors on the device of ts")
     t0 = t0.to(dt).contiguous()
@@ -2347,7 +2254,7 @@ def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named):
     if cr.CHECK_POSITIVE_DEFINITE:
         bad = int(out[8].item())
         if bad:
-            k, b, r = _models_row(plan, bad - 1)
+            k, b, r = _locate_row(plan, bad - 1)
             where = ("model %d, series %d" % (k, b)) if named else ("series %d" % b)
             raise cr.NotPSDError("LEG filter: %s: row %d: %s" % (where, r, _FILTER_FAILED))
     return out[:8], ts_c[plan.offsets[1:] - 1]
@@ -2381,24 +2288,10 @@ def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None):
     is no CPU implementation)."""
     with torch.no_grad():
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
-        if ts.dim() != 1 or xs.dim() != 2 or xs.shape[0] != ts.shape[0] or xs.shape[1] != obs:
-            raise ValueError("one series wants ts[n] and xs[n, %d], got %s and %s" % (obs, tuple(ts.shape), tuple(xs.shape)))
+        observed = _single_series_args(obs, ts, xs, observed, noise_var)
         n = ts.shape[0]
-        if observed is not None:
-            observed = _observed_2d(observed, obs)
-            if observed.shape[0] != n:
-                raise ValueError("observed has %d rows, xs has %d" % (observed.shape[0], n))
-        if noise_var is not None:
-            if not isinstance(noise_var, torch.Tensor) or not noise_var.dtype.is_floating_point:
-                raise ValueError("noise_var must be a floating-point tensor")
-            if noise_var.dim() not in (1, 2) or noise_var.shape[0] != n or (noise_var.dim() == 2 and noise_var.shape[1] != obs):
-                raise ValueError("noise_var must be [n] or [n, %d], got %s" % (obs, tuple(noise_var.shape)))
         if init is not None:
-            if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
-                raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
-            if tuple(init[0].shape) != () or tuple(init[1].shape) != (d,) or tuple(init[2].shape) != (d, d):
-                raise ValueError("one series wants init with t 0-d, mean [%d] and cov [%d, %d], got %s, %s and %s"
-                                 % ((d, d, d) + tuple(tuple(t.shape) for t in init)))
+            _filter_state(init, ((), (d,), (d, d)), "one series wants init with t 0-d, mean [%d] and cov [%d, %d]" % (d, d, d))
             init = FilterState(init[0].reshape(1), init[1].reshape(1, 1, d), init[2].reshape(1, 1, d, d))
         if n == 0:
             state = FilterState(*(t.reshape(s).to(dt) for t, s in zip(init, ((), (d,), (d, d))))) if init is not None else None
@@ -2428,15 +2321,12 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
     ``state`` are NaN and every other series is untouched.  CPU tensors behave as ``insample_posterior_batch`` does
     (there is no CPU implementation)."""
     with torch.no_grad():
-        ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        ts, xs, lengths, observed, noise_var, dense, bn = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
         if init is not None:
-            if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
-                raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
             B = len(lengths)
-            if tuple(init[1].shape) != (B, d) or tuple(init[2].shape) != (B, d, d):
-                raise ValueError("a batch of %d series wants init with t [%d], mean [%d, %d] and cov [%d, %d, %d], got %s, %s "
-                                 "and %s" % ((B, B, B, d, B, d, d) + tuple(tuple(t.shape) for t in init)))
+            _filter_state(init, (None, (B, d), (B, d, d)), "a batch of %d series wants init with t [%d], mean [%d, %d] and "
+                          "cov [%d, %d, %d]" % (B, B, B, d, B, d, d))
             init = FilterState(init[0], init[1].unsqueeze(0), init[2].unsqueeze(0))
         if not lengths:
             if init is not None and tuple(init[0].shape) != (0,):
@@ -2475,8 +2365,8 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
         ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
                                                                                           noise_var)
         M, obs, d, dt = len(ms), mats[2].shape[1], mats[0].shape[1], mats[0].dtype
-        if init is not None and not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
-            raise ValueError("init must be a FilterState (t, mean, cov) of tensors")
+        if init is not None:
+            _filter_state_kind(init)                               # (``_filter_init`` checks the shapes)
         if not lengths:
             if init is not None and (tuple(init[0].shape), tuple(init[1].shape), tuple(init[2].shape)) != ((0,), (M, 0, d), (M, 0, d, d)):
                 raise ValueError("init wants t [0], mean [%d, 0, %d] and cov [%d, 0, %d, %d] for an empty batch" % (M, d, M, d, d))
@@ -2567,53 +2457,37 @@ def _sample_count(num_samples):
     return S
 
 
-def _perturbation_seg(ts, G, plan, ids, hsource, hterm, rows, v, S, seed, stream):
-    """rhs [R, d, S] of cgps_leg_perturbation_seg; contiguous operands of G's dtype on G's device.  With
-    ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming its series and local row."""
-    R, d, dt = plan.R, G.shape[0], G.dtype
-    out = torch.empty(R, d, S, dtype=dt, device=G.device)
+def _perturbation_models(ts, G, plan, ids, hsource, hterm, pattern, v, S, seed, words, k0=0):
+    """rhs [R, d, S] of cgps_leg_perturbation_seg under the stream word ``words`` (an int) or, with G [m, d, d], rhs
+    [m R, d, S] of cgps_leg_perturbation_models for the models of one chunk (the first of them model k0 of the call):
+    hterm [m, ...] by source, v [m, R, d] or None, ``words`` device int64 [m].  Contiguous operands of G's dtype on G's
+    device.  With ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming (model,) series and row."""
+    R, d, dt, lib = plan.R, G.shape[-1], G.dtype, _hip.lib()
+    fn, count, words = ((lib.cgps_leg_perturbation_models, (R, G.shape[0]), _hip.ptr(words)) if G.dim() == 3 else
+                        (lib.cgps_leg_perturbation_seg, (R,), int(words) & 0xFFFFFFFF))
+    out = torch.empty(math.prod(count), d, S, dtype=dt, device=G.device)
     info = torch.zeros(1, dtype=torch.int32, device=G.device)
-    entries = hterm.shape[0] if hsource == _hip.H_TABLE else 0
+    entries = hterm.shape[-3] if hsource == _hip.H_TABLE else 0
     obs = hterm.shape[-1] if hsource != _hip.H_NONE else 0
-    _hip.check(_hip.lib().cgps_leg_perturbation_seg(
-        _hip.ptr(ts), R, _hip.ptr(G), d, _hip.dtype_code(dt), _hip.ptr(plan.offsets), _hip.ptr(ids), plan.B, hsource,
-        _hip.ptr(hterm), entries, obs, _hip.ptr(rows), _hip.ptr(v), S, int(seed) & 0xFFFFFFFFFFFFFFFF,
-        int(stream) & 0xFFFFFFFF, _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    if cr.CHECK_POSITIVE_DEFINITE:
-        bad = int(info.item())
-        if bad:
-            b, r = _series_of_row(plan, bad - 1)
-            raise cr.NotPSDError("LEG batch: series %d: the time gap next to its row %d is singular (zero-length gap?)" % (b, r))
+    _hip.check(fn(_hip.ptr(ts), *count, _hip.ptr(G), d, _hip.dtype_code(dt), _hip.ptr(plan.offsets), _hip.ptr(ids), plan.B,
+                  hsource, _hip.ptr(hterm), entries, obs, _hip.ptr(pattern), _hip.ptr(v), S, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                  words, _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+    _check_gaps(info, plan, k0 if G.dim() == 3 else None, _GAP_NOISE)
     return out
 
 
-def _posterior_perturbation_flat(m, ts, xs, observed, noise_var, plan, ids, S, seed, stream):
-    """(K_Rs, K_Os, rhs [R, d, S]) of the concatenated batch (already validated, on the GPU)."""
-    K_Rs, K_Os, v = _posterior_system_batch(m, ts, xs, observed, noise_var, plan)
-    dt = K_Rs.dtype
-    if noise_var is not None:
-        hsource, rows = _hip.H_ROWS, None
-    elif observed is not None:
-        bits = 1 << torch.arange(observed.shape[1], device=observed.device)
-        hsource, rows = _hip.H_TABLE, (observed * bits).sum(1).to(torch.uint8)       # observation_tables' pattern byte
-    else:
-        hsource, rows = _hip.H_PLAIN, None
-    hterm = observation_noise_factors(m, observed, noise_var).to(dt).contiguous()
-    rhs = _perturbation_seg(ts.to(dt).contiguous(), m.G.contiguous(), plan, ids, hsource, hterm, rows, v, S, seed, stream)
-    return K_Rs, K_Os, rhs
+_perturbation_seg = _perturbation_models        # the same function: the name of its form without a model axis
 
 
-def _solve_columns(K_Rs, K_Os, rhs, plan):
-    """K^-1 rhs [R, d, S]: one factorisation, the right-hand sides in column chunks (a column never depends on the
-    chunking: the solve treats its columns independently)."""
+def _solve_columns_models(K_Rs, K_Os, rhs, plan, k0):
+    """K^-1 rhs [rows, d, S] on the concatenated system of one model's batch (k0 None) or of a chunk of models (the first
+    of them model k0 of the call): one factorisation, a failure named as ``_posterior_models_chunks`` names it, the
+    right-hand sides in column chunks (a column never depends on the chunking: the solve treats its columns
+    independently)."""
     try:
         dec = cr.decompose(K_Rs, K_Os)
     except cr.NotPSDError as e:
-        row = getattr(e, "row", None)
-        if row is None:
-            raise
-        b, r = _series_of_row(plan, row)
-        raise cr.NotPSDError("LEG batch: series %d: a block near its row %d is not positive definite" % (b, r)) from None
+        raise _factor_error(e, plan, K_Rs, K_Os, k0) from None
     return _solve_factor_columns(dec, rhs)
 
 
@@ -2628,6 +2502,26 @@ def _solve_factor_columns(dec, rhs):
     return x
 
 
+def _noise_source(rows, observed, noise_var):
+    """(hsource, pattern) of the perturbation kernels: where a row's observation-noise factor comes from, and the pattern
+    bytes of the table source (``rows`` of the posterior operands: ``observation_tables``' byte)."""
+    if noise_var is not None:
+        return _hip.H_ROWS, None
+    return (_hip.H_PLAIN, None) if observed is None else (_hip.H_TABLE, rows)
+
+
+def _posterior_perturbation_flat(m, ts, xs, observed, noise_var, plan, ids, S, seed, stream):
+    """(K_Rs, K_Os, rhs [R, d, S]) of the concatenated batch (already validated, on the GPU)."""
+    G = m.G
+    dt = G.dtype
+    source, term, rows, v = _posterior_operands_batch(m, ts, xs, observed, noise_var)
+    tsc, Gc = ts.to(dt).contiguous(), G.contiguous()
+    K_Rs, K_Os = _posterior_system_rows(plan, tsc, Gc, source, term, rows, None)
+    hsource, pattern = _noise_source(rows, observed, noise_var)
+    hterm = observation_noise_factors(m, observed, noise_var).to(dt).contiguous()
+    return K_Rs, K_Os, _perturbation_models(tsc, Gc, plan, ids, hsource, hterm, pattern, v, S, seed, stream)
+
+
 def _on_gpu(m, *tensors):
     """The model and the tensors on the GPU the kernels run on (there is no CPU implementation)."""
     dev = m.N.device if m.N.is_cuda else cr._device()
@@ -2636,7 +2530,7 @@ def _on_gpu(m, *tensors):
 
 def _perturbation_call(m, ts, xs, num_samples, seed, lengths, observed, noise_var, series_ids, stream, solve):
     like = ts
-    ts, xs, lengths, observed, noise_var, dense, bn = _batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+    ts, xs, lengths, observed, noise_var, dense, bn = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
     S = _sample_count(num_samples)
     d, obs, dt = m.N.shape[0], m.B.shape[0], m.N.dtype
     if not 1 <= d <= 8 or dt not in (torch.float32, torch.float64) or obs > MAX_PATTERN_OBS:
@@ -2649,7 +2543,7 @@ def _perturbation_call(m, ts, xs, num_samples, seed, lengths, observed, noise_va
     plan = _cached_batch_plan(lengths, m.N.device)
     K_Rs, K_Os, out = _posterior_perturbation_flat(m, ts, xs, observed, noise_var, plan, ids, S, seed, stream)
     if solve:
-        out = _solve_columns(K_Rs, K_Os, out, plan)
+        out = _solve_columns_models(K_Rs, K_Os, out, plan, None)
     out = cr._back(out, like)
     return out.reshape(bn[0], bn[1], d, S) if dense else out
 
@@ -2688,7 +2582,7 @@ def sample_from_posterior_batch(m, ts, xs, num_samples, seed, lengths=None, obse
     or on num_samples -- bitwise on the right-hand side (``posterior_perturbation_batch``), to the accuracy of the solve
     on the draw itself.  There is no per-series fallback to ``sample_from_posterior``.
 
-    How: ``_posterior_system_batch`` (one assembly launch), one cgps_leg_perturbation_seg launch for the right-hand
+    How: ``_posterior_system_rows`` (one assembly launch), one cgps_leg_perturbation_seg launch for the right-hand
     sides, ONE ``cr.decompose`` and ``cr.solve`` on column chunks of at most ``_sample_column_chunk(rank)`` columns.  A
     repeated call with the same lengths and default ids copies nothing from the host.  With
     ``cr.CHECK_POSITIVE_DEFINITE`` a zero-length gap or a block that is not positive definite raises ``cr.NotPSDError``
@@ -2721,9 +2615,9 @@ def sample_from_prior_batch(m, ts, num_samples, seed, lengths=None, series_ids=N
         ids = _series_ids_arg(series_ids, lengths, d, 1, m.N.device)
         plan = _cached_batch_plan(lengths, m.N.device)
         tsc, G = ts.to(dt).contiguous(), m.G.contiguous()
-        rhs = _perturbation_seg(tsc, G, plan, ids, _hip.H_NONE, None, None, None, S, seed, stream)   # (names a singular gap)
-        Rs, Os = _peg_precision_seg(tsc, G, plan.cut)
-        out = cr._back(_solve_columns(Rs, Os, rhs, plan), like)
+        rhs = _perturbation_models(tsc, G, plan, ids, _hip.H_NONE, None, None, None, S, seed, stream)   # (names a singular gap)
+        Rs, Os = _peg_precision_models(tsc, G, plan.cut)
+        out = cr._back(_solve_columns_models(Rs, Os, rhs, plan, None), like)
         return out.reshape(shape + (d, S)) if dense else out
 
 
@@ -2789,61 +2683,13 @@ def _models_sampling_operands(ms, ts, xs, observed, noise_var):
     term = torch.stack([p[1] for p in parts])
     v = torch.stack([p[3] for p in parts])
     rows = torch.stack([p[2] for p in parts]) if source == _hip.ROWS_WEIGHTED else parts[0][2]
-    if noise_var is not None:
-        hsource, pattern = _hip.H_ROWS, None
-    elif observed is not None:
-        hsource, pattern = _hip.H_TABLE, rows                                 # observation_tables' pattern byte
-    else:
-        hsource, pattern = _hip.H_PLAIN, None
+    hsource, pattern = _noise_source(rows, observed, noise_var)
     return G, source, term, rows, v, hsource, _models_noise_factors(ms, observed, noise_var).to(dt), pattern
-
-
-def _perturbation_models(ts, G, plan, ids, hsource, hterm, pattern, v, S, seed, words, k0=0):
-    """rhs [m R, d, S] of cgps_leg_perturbation_models for the models of one chunk (the first of them model k0 of the
-    call): G [m, d, d], hterm [m, ...] by source, v [m, R, d] or None, words device int64 [m]; contiguous operands of G's
-    dtype.  With ``cr.CHECK_POSITIVE_DEFINITE`` a singular time gap raises NotPSDError naming model, series and row."""
-    m, d, R, dt = G.shape[0], G.shape[1], plan.R, G.dtype
-    out = torch.empty(m * R, d, S, dtype=dt, device=G.device)
-    info = torch.zeros(1, dtype=torch.int32, device=G.device)
-    entries = hterm.shape[1] if hsource == _hip.H_TABLE else 0
-    obs = hterm.shape[-1] if hsource != _hip.H_NONE else 0
-    _hip.check(_hip.lib().cgps_leg_perturbation_models(
-        _hip.ptr(ts), R, m, _hip.ptr(G), d, _hip.dtype_code(dt), _hip.ptr(plan.offsets), _hip.ptr(ids), plan.B, hsource,
-        _hip.ptr(hterm), entries, obs, _hip.ptr(pattern), _hip.ptr(v), S, int(seed) & 0xFFFFFFFFFFFFFFFF, _hip.ptr(words),
-        _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
-    if cr.CHECK_POSITIVE_DEFINITE:
-        bad = int(info.item())
-        if bad:
-            k, b, r = _models_row(plan, bad - 1)
-            raise cr.NotPSDError("LEG models: model %d, series %d: the time gap next to its row %d is singular "
-                                 "(zero-length gap?)" % (k0 + k, b, r))
-    return out
-
-
-def _solve_columns_models(K_Rs, K_Os, rhs, plan, m, k0):
-    """``_solve_columns`` on the concatenated system of m models (the first of them model k0 of the call): a failed
-    factorisation names model, series and local row as ``_posterior_models_chunks`` does."""
-    try:
-        dec = cr.decompose(K_Rs, K_Os)
-    except cr.NotPSDError as e:
-        row = getattr(e, "row", None)
-        if row is None:
-            raise
-        k, b, r = _failed_model_series(plan, m, K_Rs, K_Os, row)
-        raise cr.NotPSDError("LEG models: model %d, series %d: a block near its row %d is not positive definite"
-                             % (k0 + k, b, r)) from None
-    return _solve_factor_columns(dec, rhs)
-
-
-def _model_chunks(M, R):
-    """(k0, k1) of the chunks of whole models of at most MODELS_POSTERIOR_MAX_ROWS concatenated rows (one model at least)."""
-    per = max(1, MODELS_POSTERIOR_MAX_ROWS // R)
-    return [(k0, min(M, k0 + per)) for k0 in range(0, M, per)]
 
 
 def _stack_model_chunks(parts, M, R):
     """[M, R, ...] from the chunks' [m R, ...] results (a view when there is one chunk)."""
-    out = parts[0] if len(parts) == 1 else torch.cat(parts)
+    out = _cat_chunks(parts)
     return out.view((M, R) + tuple(out.shape[1:]))
 
 
@@ -2855,8 +2701,6 @@ def _perturbation_models_call(ms, ts, xs, num_samples, seed, lengths, observed, 
     S = _sample_count(num_samples)
     M, d, obs, dt = len(ms), mats[0].shape[1], mats[2].shape[1], mats[0].dtype
     _sampling_kernels_built(d, obs, dt)
-    if noise_var is not None and noise_var.dim() == 2 and noise_var.shape[1] != obs:
-        raise ValueError("noise_var must have %d channels, got %s" % (obs, tuple(noise_var.shape)))
     words = _model_stream_words(M, stream, model_streams)
     if not lengths:
         _series_ids_arg(series_ids, lengths, d, obs, "cpu")
@@ -2869,14 +2713,13 @@ def _perturbation_models_call(ms, ts, xs, num_samples, seed, lengths, observed, 
     G, source, term, rows, v, hsource, hterm, pattern = _models_sampling_operands(ms, ts, xs, observed, noise_var)
     tsc, wd = ts.to(dt).contiguous(), torch.tensor(words, dtype=torch.int64).to(dev)
     parts = []
-    for k0, k1 in _model_chunks(M, R):
-        m = k1 - k0
-        rhs = _perturbation_models(tsc, G[k0:k1], plan, ids, hsource, hterm[k0:k1], pattern, v[k0:k1], S, seed, wd[k0:k1], k0)
+    for k0, k1, sel in _model_chunks(G, R, MODELS_POSTERIOR_MAX_ROWS):
+        rhs = _perturbation_models(tsc, G[sel], plan, ids, hsource, hterm[sel], pattern, v[sel], S, seed, wd[sel], k0)
         if solve:
-            K_Rs, K_Os, info = _posterior_blocks_models(tsc, G[k0:k1], plan.cut, source, term[k0:k1],
-                                                        rows if source != _hip.ROWS_WEIGHTED else rows[k0:k1])
+            K_Rs, K_Os, info = _posterior_blocks_models(tsc, G[sel], plan.cut, source, term[sel],
+                                                        rows if source != _hip.ROWS_WEIGHTED else rows[sel])
             # (a singular gap was named by the perturbation already: both kernels evaluate the gaps the same way)
-            rhs = _solve_columns_models(K_Rs, K_Os, rhs, plan, m, k0)
+            rhs = _solve_columns_models(K_Rs, K_Os, rhs, plan, k0)
             del K_Rs, K_Os
         parts.append(rhs)
     out = cr._back(_stack_model_chunks(parts, M, R), like)
@@ -2961,15 +2804,14 @@ def sample_from_prior_models(ms, ts, num_samples, seed, lengths=None, series_ids
         tsc, wd = ts.to(dt).contiguous(), torch.tensor(words, dtype=torch.int64).to(dev)
         peg = batch_supported(tsc, G[0])                           # (cgps_peg_precision_models: d <= 7, not fp64 d = 6)
         parts = []
-        for k0, k1 in _model_chunks(M, R):
-            m = k1 - k0
-            rhs = _perturbation_models(tsc, G[k0:k1], plan, ids, _hip.H_NONE, None, None, None, S, seed, wd[k0:k1], k0)
+        for k0, k1, sel in _model_chunks(G, R, MODELS_POSTERIOR_MAX_ROWS):
+            rhs = _perturbation_models(tsc, G[sel], plan, ids, _hip.H_NONE, None, None, None, S, seed, wd[sel], k0)
             if peg:
-                Rs, Os = _peg_precision_models(tsc, G[k0:k1], plan.cut)
+                Rs, Os = _peg_precision_models(tsc, G[sel], plan.cut)
             else:
-                Rs, Os, _ = _posterior_blocks_models(tsc, G[k0:k1], plan.cut, _hip.ROWS_PLAIN,
-                                                     torch.zeros(m, d, d, dtype=dt, device=dev))
-            parts.append(_solve_columns_models(Rs, Os, rhs, plan, m, k0))
+                Rs, Os, _ = _posterior_blocks_models(tsc, G[sel], plan.cut, _hip.ROWS_PLAIN,
+                                                     torch.zeros(k1 - k0, d, d, dtype=dt, device=dev))
+            parts.append(_solve_columns_models(Rs, Os, rhs, plan, k0))
             del Rs, Os
         out = cr._back(_stack_model_chunks(parts, M, R), like)
         return out.reshape((M,) + shape + (d, S)) if dense else out
@@ -3007,13 +2849,8 @@ def _observations_call(ms, z, seed, lengths, observed, noise_var, series_ids, wo
     rows_shape = tuple(z.shape[lead:-2])                           # (B, n) or (R,)
     xs_shape = rows_shape + (obs,)
     # (the layout checks of the other batched calls, on storage-free stand-ins for ts and xs of the right shapes)
-    _, _, lengths = _batch_layout(torch.empty(rows_shape, device="meta"), torch.empty(xs_shape, device="meta"), lengths)
-    if observed is not None:
-        observed = _observed_2d(_batch_like_xs(observed, _OBSERVED, xs_shape, dense), obs)
-    if noise_var is not None:
-        noise_var = _batch_like_xs(noise_var, _NOISE_VAR, xs_shape, dense)
-        if noise_var.dim() == 2 and noise_var.shape[1] != obs:
-            raise ValueError("noise_var must have %d channels, got %s" % (obs, tuple(noise_var.shape)))
+    _, _, lengths, observed, noise_var = _batch_args(obs, torch.empty(rows_shape, device="meta"),
+                                                     torch.empty(xs_shape, device="meta"), lengths, observed, noise_var)[:5]
     out_shape = tuple(z.shape[:-2]) + (obs, S)
     if not lengths:
         _series_ids_arg(series_ids, lengths, d, obs, "cpu")
@@ -3030,7 +2867,7 @@ def _observations_call(ms, z, seed, lengths, observed, noise_var, series_ids, wo
     if cr.CHECK_POSITIVE_DEFINITE:
         bad = int(info.item())
         if bad:
-            k, b, r = _models_row(plan, bad - 1)
+            k, b, r = _locate_row(plan, bad - 1)
             raise cr.NotPSDError("LEG replicated observations: model %d, series %d: the noise covariance of its row %d is "
                                  "not positive definite (a negative noise_var?)" % (k, b, r))
     return cr._back(x, like).reshape(out_shape)

@@ -236,20 +236,28 @@ def _batch_targets(target_ts, target_lengths, lengths, dense):
     return target_ts, target_lengths, None
 
 
-def _intercast_seg_hip(G, ip_mean, Rs, Os, ts, plan, target_ts, tplan):
+def _intercast_models_hip(G, ip_mean, Rs, Os, ts, plan, target_ts, tplan, means=None, covs=None):
     """All targets of all series in one HIP kernel (cgps_leg_intercast_seg, csrc/cgps_leg.h): a lane per target finds
-    its series and does what ``_intercast_hip`` does for that series alone."""
+    its series and does what ``_intercast_hip`` does for that series alone.  With G [m, d, d] the same under every model
+    (cgps_leg_intercast_models): grid (target blocks, m), model k on its slices of the concatenated posterior ip_mean
+    [m R, d], Rs [m R, d, d], Os [m R - 1, d, d], its predictions in means[k] [m, P, d] and covs[k] [m, P, d, d].  ``means``
+    and ``covs``: contiguous tensors to write into (None: new ones)."""
     from . import _hip
     dt, dev = ip_mean.dtype, ip_mean.device
-    d, P = G.shape[0], tplan.P
+    d, P, lead = G.shape[-1], tplan.P, tuple(G.shape[:-2])
     c = lambda t: t.detach().to(device=dev, dtype=dt).contiguous()   # noqa: E731
     ts_, tt_, G_, mu_, Rs_, Os_ = c(ts), c(target_ts), c(G), c(ip_mean), c(Rs), c(Os)
-    means = torch.empty(P, d, dtype=dt, device=dev)
-    covs = torch.empty(P, d, d, dtype=dt, device=dev)
-    _hip.check(_hip.lib().cgps_leg_intercast_seg(
-        _hip.ptr(ts_), _hip.ptr(plan.offsets), _hip.ptr(tt_), _hip.ptr(tplan.offsets), plan.B, P, _hip.ptr(G_), d,
-        _hip.dtype_code(dt), _hip.ptr(mu_), _hip.ptr(Rs_), _hip.ptr(Os_), _hip.ptr(means), _hip.ptr(covs), _hip.stream_ptr()))
+    if means is None:
+        means = torch.empty(lead + (P, d), dtype=dt, device=dev)
+        covs = torch.empty(lead + (P, d, d), dtype=dt, device=dev)
+    fn = _hip.lib().cgps_leg_intercast_models if lead else _hip.lib().cgps_leg_intercast_seg
+    _hip.check(fn(_hip.ptr(ts_), _hip.ptr(plan.offsets), _hip.ptr(tt_), _hip.ptr(tplan.offsets), plan.B, P, *lead, _hip.ptr(G_), d,
+                  _hip.dtype_code(dt), _hip.ptr(mu_), _hip.ptr(Rs_), _hip.ptr(Os_), _hip.ptr(means), _hip.ptr(covs),
+                  _hip.stream_ptr()))
     return means, covs
+
+
+_intercast_seg_hip = _intercast_models_hip        # the same function: the name of its form without a model axis
 
 
 def _intercast_per_series(m, mean, Sd, So, ts, lengths, target_ts, target_lengths):
@@ -284,7 +292,7 @@ def predictive_posterior_batch(m, ts, xs, target_ts, lengths=None, target_length
     call with the same lengths and target lengths copies nothing from the host.  Errors, NaN propagation with
     ``cr.CHECK_POSITIVE_DEFINITE`` off and unsupported inputs: ``leg.insample_posterior_batch``."""
     with torch.no_grad():
-        ts_f, xs_f, lens, observed, noise_var, dense, bn = leg._batch_posterior_args(m, ts, xs, lengths, observed, noise_var)
+        ts_f, xs_f, lens, observed, noise_var, dense, bn = leg._batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
         tt, tlens, bp = _batch_targets(target_ts, target_lengths, lens, dense)
         d, dt = m.N.shape[0], m.N.dtype
         P = sum(tlens)
@@ -298,8 +306,8 @@ def predictive_posterior_batch(m, ts, xs, target_ts, lengths=None, target_length
             tplan = leg._cached_batch_plan(tlens, G.device, make=_TargetPlan)
             if check_sorted and P > 1:
                 assert bool(((tt[1:] - tt[:-1] > 0) | tplan.across).all())     # reference :471, per series
-            mean, Sd, So, plan = leg._insample_posterior_flat(m, ts_f, xs_f, lens, observed, noise_var)
-            pm, pv = _intercast_seg_hip(G, mean, Sd, So, ts_f, plan, tt, tplan)
+            mean, Sd, So, plan = leg._posterior_flat_hip(m, ts_f, xs_f, lens, observed, noise_var)
+            pm, pv = _intercast_models_hip(G, mean, Sd, So, ts_f, plan, tt, tplan)
         else:
             if check_sorted and P > 1:
                 across = _TargetPlan(tlens, tt.device).across
@@ -323,18 +331,6 @@ def make_predictions_batch(m, ts, xs, target_ts, lengths=None, target_lengths=No
 
 
 # ---- many models over one batch --------------------------------------------------------------------------------
-def _intercast_models_hip(G, ip_mean, Rs, Os, ts, plan, target_ts, tplan, means, covs):
-    """All targets of all series under the models G[m, d, d] in one HIP kernel (cgps_leg_intercast_models): grid
-    (target blocks, m), model k on its slices of the concatenated posterior ip_mean [m R, d], Rs [m R, d, d], Os
-    [m R - 1, d, d], its predictions written into means[k] [m, P, d] and covs[k] [m, P, d, d] (contiguous)."""
-    from . import _hip
-    d, P = G.shape[1], tplan.P
-    _hip.check(_hip.lib().cgps_leg_intercast_models(
-        _hip.ptr(ts), _hip.ptr(plan.offsets), _hip.ptr(target_ts), _hip.ptr(tplan.offsets), plan.B, P, G.shape[0], _hip.ptr(G),
-        d, _hip.dtype_code(G.dtype), _hip.ptr(ip_mean), _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(means), _hip.ptr(covs),
-        _hip.stream_ptr()))
-
-
 def _predictive_posterior_models_flat(ms, ts, xs, target_ts, lengths, target_lengths, observed, noise_var, check_sorted):
     """(means [M, P, rank], covs [M, P, rank, rank], B stacked [M, obs, rank], shape of the dense targets (B, p) or None)
     of the validated call: the predictions in the order of the flattened targets."""

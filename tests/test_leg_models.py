@@ -75,6 +75,27 @@ def test_layout_is_checked_as_the_batch_checks_it():
         leg.log_likelihood_models(ms, ts.reshape(2, 5), xs.reshape(2, 5, 1), [5, 5])
 
 
+def test_a_wrong_channel_count_prints_the_shape_each_call_has_always_printed():
+    """Dense xs [2, 5, 2] under models of one channel: the many-model calls name the flattened (10, 2), the batch calls the
+    caller's (2, 5, 2)."""
+    import re
+    from cyclic_gps import predict
+    ms = [_model(2, 1, F64, s, device="cpu") for s in (0, 1)]
+    ts, xs = torch.arange(10, dtype=F64).reshape(2, 5), torch.zeros(2, 5, 2, dtype=F64)
+    many = re.escape("xs must have 1 channels, got (10, 2)")
+    for call in (lambda: leg.log_likelihood_models(ms, ts, xs), lambda: leg.insample_posterior_models(ms, ts, xs),
+                 lambda: predict.predictive_posterior_models(ms, ts, xs, ts), lambda: leg.loo_predictive_models(ms, ts, xs),
+                 lambda: leg.posterior_perturbation_models(ms, ts, xs, 2, 1)):
+        with pytest.raises(ValueError, match=many):
+            call()
+    one = re.escape("xs must have 1 channels, got (2, 5, 2)")
+    seen = torch.ones(2, 5, dtype=torch.bool)
+    for call in (lambda: leg.log_likelihood_batch(ms[0], ts, xs, observed=seen), lambda: leg.insample_posterior_batch(ms[0], ts, xs),
+                 lambda: predict.predictive_posterior_batch(ms[0], ts, xs, ts)):
+        with pytest.raises(ValueError, match=one):
+            call()
+
+
 def test_empty_batch_gives_one_empty_row_per_model():
     ms = [_model(3, 1, F64, s, device="cpu") for s in (0, 1, 2)]
     out = leg.log_likelihood_models(ms, torch.zeros(0, dtype=F64), torch.zeros(0, 1, dtype=F64), [])
@@ -213,6 +234,25 @@ def test_assembly_and_adjoint_are_the_seg_kernels_per_model_bit_for_bit(d, dtype
         assert torch.equal(gtau[k], t1), k
         cuts = plan.cut.bool()
         assert int(torch.count_nonzero(gtau[k][cuts])) == 0                 # a cut gap: gtau = 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d,dtype", [(1, F64), (5, F64), (4, F32)], ids=["d1-f64", "d5-f64", "d4-f32"])
+def test_adjoint_wrapper_without_a_model_axis_is_its_one_model_form(d, dtype):
+    """``leg._peg_precision_adjoint_models`` with G [d, d] (cgps_peg_precision_adjoint_seg) against G [1, d, d]
+    (cgps_peg_precision_adjoint_models), with and without the gradient in ts; the assembly wrapper alongside."""
+    lengths = [1, 2, 5, 64, 65]
+    G, _, ts, _, _, gen = _kernel_operands(d, dtype, 1, lengths, 2500 + d)
+    plan = leg._BatchPlan(lengths, "cuda")
+    for a, b in zip(leg._peg_precision_models(ts, G[0], plan.cut), leg._peg_precision_models(ts, G, plan.cut)):
+        assert torch.equal(a, b)
+    gRs = torch.randn(plan.R, d, d, generator=gen, dtype=F64).to(dtype).cuda()
+    gOs = torch.randn(plan.R - 1, d, d, generator=gen, dtype=F64).to(dtype).cuda()
+    for want_ts in (True, False):
+        gG, gts = leg._peg_precision_adjoint_models(ts, G[0], plan.cut, gRs, gOs, want_ts)
+        gG1, gts1 = leg._peg_precision_adjoint_models(ts, G, plan.cut, gRs, gOs, want_ts)
+        assert gG.shape == (d, d) and gG1.shape == (1, d, d) and torch.equal(gG, gG1[0])
+        assert (gts is None and gts1 is None) if not want_ts else (gts.shape == ts.shape and torch.equal(gts, gts1))
 
 
 @pytest.mark.gpu

@@ -117,6 +117,28 @@ def test_slot_k_across_the_column_chunk_fp64():
     assert torch.equal(rhs[:, :, :, :9], leg.posterior_perturbation_models(ms, ts, xs, 9, seed, series_ids=IDS, **kw))
 
 
+@pytest.mark.parametrize("d,dtype", [(1, F64), (5, F64), (4, F32)], ids=["d1-f64", "d5-f64", "d4-f32"])
+def test_perturbation_wrapper_without_a_model_axis_is_its_one_model_form(d, dtype):
+    """``leg._perturbation_models`` with G [d, d] and an int stream word (cgps_leg_perturbation_seg) against G [1, d, d]
+    and a device word (cgps_leg_perturbation_models), the three noise sources."""
+    lengths, obs, S, seed, word = [1, 2, 5, 64, 65], 2, 3, 11, 6
+    m = sb._model(d, obs, 370 + d, dtype)[0]
+    gen = torch.Generator().manual_seed(d)
+    n = sum(lengths)
+    ts = torch.cat([torch.cumsum(0.5 + torch.rand(k, generator=gen, dtype=F64), 0) for k in lengths]).to(dtype).cuda()
+    xs = torch.randn(n, obs, generator=gen, dtype=F64).to(dtype).cuda()
+    ob = (torch.rand(n, obs, generator=gen) < 0.7).cuda()
+    nv = torch.rand(n, obs, generator=gen, dtype=F64).to(dtype).cuda()
+    plan = leg._cached_batch_plan(lengths, ts.device)
+    ids = torch.arange(len(lengths), dtype=torch.int64, device=ts.device)
+    words = torch.tensor([word], dtype=torch.int64).cuda()
+    for observed, noise_var in ((None, None), (ob, None), (ob, nv)):
+        G, _, _, _, v, hsource, hterm, pattern = leg._models_sampling_operands([m], ts, xs, observed, noise_var)
+        one = leg._perturbation_models(ts, G[0], plan, ids, hsource, hterm[0], pattern, v[0], S, seed, word)
+        assert one.shape == (n, d, S) and not bool(torch.isnan(one).any())
+        assert torch.equal(one, leg._perturbation_models(ts, G, plan, ids, hsource, hterm, pattern, v, S, seed, words, 0))
+
+
 @pytest.mark.parametrize("d", [1, 3, 5, 6, 8])
 def test_prior_slot_k_is_the_batch_call_fp64(d):
     """d = 6 and d = 8 have no cgps_peg_precision_models in fp64: the assembly with a zero term takes its place."""

@@ -9,7 +9,7 @@ rows from leg.co2_like_series with different seeds (standardised as co2_workload
         per B: predict_batch_us / predict_loop_us (make_predictions_batch, check_sorted=False, against the loop, which is
         what a user ran before the batched call existed), posterior_obs_batch_us / posterior_obs_loop_us (70 % of the
         entries kept, another mask per series), and assembly_{plain,obs,noise}_{kernel,composed}_us: the concatenated
-        posterior system alone (leg._posterior_system_batch, operands included) with K's blocks written once by
+        posterior system alone (leg._posterior_operands_batch + leg._posterior_system_rows) with K's blocks written once by
         cgps_leg_posterior_blocks_seg against the composition it replaces (CGPS_LEG_BLOCKS_COMPOSED=1:
         cgps_peg_precision_seg, then the gather or einsum and the add as torch passes), alternated inside every
         repetition; plain, with the mask, and with noise variances uniform in [0, 1].  The batch agrees with the loop
@@ -136,7 +136,8 @@ def main():
                     os.environ["CGPS_LEG_BLOCKS_COMPOSED"] = "1"
                 try:
                     with torch.no_grad():
-                        leg._posterior_system_batch(m, tsf, xsf, observed, noise, plan)
+                        source, term, rows, _ = leg._posterior_operands_batch(m, tsf, xsf, observed, noise)
+                        leg._posterior_system_rows(plan, tsf, m.G.contiguous(), source, term, rows, None)
                 finally:
                     os.environ.pop("CGPS_LEG_BLOCKS_COMPOSED", None)
             return run

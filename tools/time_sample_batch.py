@@ -60,7 +60,8 @@ def main():
 
         def concat():
             with torch.no_grad():
-                K_Rs, K_Os, v = leg._posterior_system_batch(m, tsf, xsf, None, None, plan)
+                source, term, rows, v = leg._posterior_operands_batch(m, tsf, xsf, None, None)
+                K_Rs, K_Os = leg._posterior_system_rows(plan, tsf, m.G.contiguous(), source, term, rows, None)
                 dec, mean = cr.decompose_solve(K_Rs, K_Os, v)
                 return cr.sample(dec, S, seed, mean=mean)
 
@@ -74,7 +75,7 @@ def main():
         dec = cr.decompose(K_Rs, K_Os)
 
         def kernel():
-            return leg._perturbation_seg(tsf, G, plan, ids, _hip.H_PLAIN, H, None, v, S, seed, 0)
+            return leg._perturbation_models(tsf, G, plan, ids, _hip.H_PLAIN, H, None, v, S, seed, 0)
 
         # the batched draws have the posterior's mean and spread before anything is timed (64 draws of one series
         # against leg.insample_posterior: a coarse check, the tests hold the exact ones)

@@ -75,7 +75,7 @@ def row_for(M, B, reps):
             return leg._perturbation_models(tsf, G, plan, ids, hsource, hterm, None, v, S, SEED, words)
 
         def pert_loop():
-            return [leg._perturbation_seg(tsf, G[k], plan, ids, hsource, hterm[k], None, v[k], S, SEED, 4 * k) for k in range(per)]
+            return [leg._perturbation_models(tsf, G[k], plan, ids, hsource, hterm[k], None, v[k], S, SEED, 4 * k) for k in range(per)]
 
         one = pert_models().view(per, plan.R, d, S)
         assert all(torch.equal(one[k], r) for k, r in enumerate(pert_loop()))
