@@ -320,6 +320,47 @@ inline size_t mahal_logdet_ws_bytes(int64_t N, int d, size_t s) {
   return max_bytes(level_ws(N, d, s, true, true).total, tile_ws(N, d, s).total);
 }
 
+// ---- cgps_leg_filter_scan (cgps_leg_filter_scan.h): the time-parallel filter's levels of elements and chunk states ----
+// Level 0 holds one element per (model, chunk), level l + 1 one per group of `fanout` elements of level l, up to the
+// first level of at most `fanout` elements (one group).  An element is filter_scan_elem_scalars(d) scalars (A, b, C,
+// eta, J, the reset flag) and a level is stored value-major, [M][scalars][n[l]], so that the lanes of a wave, which
+// own neighbouring elements, read neighbouring addresses.  Behind the levels: what the final-rows phase reads per chunk
+// (t0 [chunks], m0 [M][chunks][d], P0 [M][chunks][d][d]) and leaves per chunk (loglik [M][chunks] doubles, m_end, P_end).
+constexpr int FILTER_SCAN_MAX_LEVELS = 40;      // fanout >= 2 and at most 2^36 chunks: 37 levels
+constexpr int filter_scan_elem_scalars(int d) { return 3 * d * d + 2 * d + 1; }
+struct FilterScanWs {
+  int levels;
+  int64_t n[FILTER_SCAN_MAX_LEVELS];            // elements per model of every level
+  Region elem[FILTER_SCAN_MAX_LEVELS];
+  Region t0, m0, P0, loglik, m_end, P_end;
+  size_t total;
+};
+inline FilterScanWs filter_scan_ws(int64_t chunks, int64_t M, int d, size_t s, int64_t fanout) {
+  FilterScanWs w{};
+  size_t off = 0;
+  auto cut = [&](size_t bytes) {
+    Region r{off, align_up(bytes)};
+    off = r.end();
+    return r;
+  };
+  int64_t n = chunks;
+  for (;;) {
+    w.n[w.levels] = n;
+    w.elem[w.levels] = cut((size_t)M * filter_scan_elem_scalars(d) * (size_t)n * s);
+    ++w.levels;
+    if (n <= fanout || w.levels == FILTER_SCAN_MAX_LEVELS) break;
+    n = (n + fanout - 1) / fanout;
+  }
+  w.t0 = cut((size_t)chunks * s);
+  w.m0 = cut((size_t)M * chunks * d * s);
+  w.P0 = cut((size_t)M * chunks * d * d * s);
+  w.loglik = cut((size_t)M * chunks * sizeof(double));
+  w.m_end = cut((size_t)M * chunks * d * s);
+  w.P_end = cut((size_t)M * chunks * d * d * s);
+  w.total = off;
+  return w;
+}
+
 // ---- passes of the substitution sweeps -------------------------------------------------------------------------
 // Forward pass p reads the surviving rows of pass p - 1 (the caller's y for p = 0) and, when a pass follows, writes
 // [nsurv][D] surviving rows, one spare row, then [tiles][D] owed vectors into buf[p & 1] of its workspace.  Backward

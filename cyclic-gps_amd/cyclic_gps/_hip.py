@@ -78,6 +78,9 @@ _SIGNATURES = {
     "cgps_leg_loo": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp,
                             _vp, _vp, _vp]),
     "cgps_leg_filter": (_int, [_vp] * 5 + [_i64] * 3 + [_vp] * 3 + [_int] * 3 + [_vp] * 13),
+    "cgps_leg_filter_scan_workspace_bytes": (_int, [_i64, _i64, _int, _int, _i64, ctypes.POINTER(_sz)]),
+    "cgps_leg_filter_scan": (_int, [_vp] * 5 + [_i64] * 3 + [_vp] * 3 + [_int] * 3 + [_vp] * 6 + [_i64] * 3 + [_vp, _sz]
+                             + [_vp] * 10),
     "cgps_record_elems":(_int, [_int, _int, ctypes.POINTER(_i64)]),
     "cgps_shard_reduce": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp, _vp, _vp]),
     "cgps_finish_records": (_int, [_vp, _sz, _vp, _sz, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
@@ -186,6 +189,20 @@ def _sample_workspace_bytes(N, d, dtc, nrhs):
 def sample_workspace(N, d, dt, nrhs, device):
     """The same for cgps_sample (its own carve-up: sample_ws in csrc/cgps_plan.h)."""
     nbytes = _sample_workspace_bytes(int(N), int(d), dtype_code(dt), int(nrhs))
+    return _scratch(_ws_cache, nbytes, device), nbytes
+
+
+@functools.lru_cache(maxsize=512)
+def filter_scan_workspace_bytes(n_chunks, M, d, dtc, fanout):
+    """What cgps_leg_filter_scan asks for (filter_scan_ws in csrc/cgps_plan.h); host arithmetic, no GPU needed."""
+    b = _sz(0)
+    check(lib().cgps_leg_filter_scan_workspace_bytes(n_chunks, M, d, dtc, fanout, ctypes.byref(b)))
+    return b.value
+
+
+def filter_scan_workspace(n_chunks, M, d, dt, fanout, device):
+    """A cached scratch tensor for cgps_leg_filter_scan and its byte count."""
+    nbytes = filter_scan_workspace_bytes(int(n_chunks), int(M), int(d), dtype_code(dt), int(fanout))
     return _scratch(_ws_cache, nbytes, device), nbytes
 
 

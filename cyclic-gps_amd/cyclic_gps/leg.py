@@ -16,6 +16,7 @@ parallel batched device work done with torch ops; everything block-tridiagonal g
 cyclic_gps.cyclic_reduction, i.e. the HIP kernels.  Tensors follow the device of `ts`.
 """
 import collections
+import functools
 import math
 import os
 
@@ -2159,6 +2160,54 @@ _FILTER_FAILED = ("its one-step-ahead predictive does not exist (the covariance 
                   "definite -- a negative noise_var? --, its gap is negative, or a result is not finite)")
 
 
+# The time-parallel form (cgps_leg_filter_scan): what ``chunk_rows="auto"`` stands for -- the fastest pair
+# measured for one series of 2^20 rows (rank 5, fp64) on one MI355X.
+FILTER_CHUNK_ROWS = 128
+FILTER_SCAN_FANOUT = 16
+
+
+def _filter_chunking(chunk_rows):
+    """``chunk_rows`` of the filter calls as None (the serial kernel) or (rows per chunk L >= 1, fan-out F >= 2) of the
+    time-parallel form: an int L, a pair (L, F) or "auto"; ValueError for anything else."""
+    if chunk_rows is None:
+        return None
+    if isinstance(chunk_rows, str) and chunk_rows == "auto":
+        return FILTER_CHUNK_ROWS, FILTER_SCAN_FANOUT
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)      # noqa: E731
+    if is_int(chunk_rows):
+        chunk_rows = (chunk_rows, FILTER_SCAN_FANOUT)
+    if not (isinstance(chunk_rows, (tuple, list)) and len(chunk_rows) == 2 and all(is_int(v) for v in chunk_rows)
+            and chunk_rows[0] >= 1 and chunk_rows[1] >= 2):
+        raise ValueError('chunk_rows must be None, "auto", an int L >= 1 or a pair (L, F) with L >= 1 rows per chunk and '
+                         "fan-out F >= 2, got %r" % (chunk_rows,))
+    return int(chunk_rows[0]), int(chunk_rows[1])
+
+
+class _ChunkPlan:
+    """The chunk layout of a batch for chunks of ``L`` rows (a subclass per L: ``_chunk_plan_kind``): ceil(n_b / L)
+    chunks per series, restarting at every series' first row.  Device int64 tensors ``chunk_offsets`` [chunks + 1] (row
+    offsets), ``chunk_series`` [chunks] and ``series_chunks`` [B + 1] (the first chunk of every series), planned on the
+    host from the lengths and cached like the batch plans (``_cached_batch_plan``)."""
+    L = None
+
+    def __init__(self, lengths, device):
+        lens = torch.as_tensor(list(lengths), dtype=torch.int64)
+        per = (lens + (self.L - 1)) // self.L
+        zero = torch.zeros(1, dtype=torch.int64)
+        first = torch.cat([zero, torch.cumsum(per, 0)])
+        rows = torch.cat([zero, torch.cumsum(lens, 0)])
+        self.chunks = int(first[-1])
+        ser = torch.repeat_interleave(torch.arange(len(lengths), dtype=torch.int64), per, output_size=self.chunks)
+        local = torch.arange(self.chunks, dtype=torch.int64) - first[ser]
+        off = torch.cat([rows[ser] + local * self.L, rows[-1:]])
+        self.chunk_offsets, self.chunk_series, self.series_chunks = (t.to(device) for t in (off, ser, first))
+
+
+@functools.lru_cache(maxsize=None)
+def _chunk_plan_kind(L):
+    return type("_ChunkPlan%d" % L, (_ChunkPlan,), {"L": L, "plans": {}, "captured": {}})
+
+
 def _filter_state_kind(init):
     """``init`` (not None) checked as a ``FilterState``: a triple of tensors; ValueError otherwise."""
     if not (isinstance(init, tuple) and len(init) == 3 and all(isinstance(t, torch.Tensor) for t in init)):
@@ -2192,9 +2241,9 @@ def _filter_init(init, lead, d, ts, starts, dt):
     return t0, m0.to(dt).contiguous(), P0.to(dt).contiguous()
 
 
-def _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init):
-    """cgps_leg_filter: ts [R], xs [R, obs], pattern uint8 [R] or None, noise_var [R, obs] or None, offsets device int64
-    [B + 1] (shared by the models), G [M, d, d], Bm [M, obs, d], LLT [M, obs, obs], init (t0 [B], m0 [M, B, d], P0
+def _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init, scan=None):
+    """cgps_leg_filter, or with ``scan`` = (a ``_ChunkPlan`` of the batch, fan-out) cgps_leg_filter_scan: ts [R], xs
+    [R, obs], pattern uint8 [R] or None, noise_var [R, obs] or None, offsets device int64 [B + 1] (shared by the models), G [M, d, d], Bm [M, obs, d], LLT [M, obs, obs], init (t0 [B], m0 [M, B, d], P0
     [M, B, d, d]) or None, all contiguous and of one dtype.  Returns (mean [M, R, obs], cov [M, R, obs, obs], logpdf
     [M, R], z_mean [M, R, d], z_cov [M, R, d, d], loglik [M, B] fp64, m_end [M, B, d], P_end [M, B, d, d], info int32
     [1]: 0 or 1 + the smallest failing row of the M R).  Nothing is read on the host."""
@@ -2217,11 +2266,18 @@ def _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init):
     info = torch.zeros(1, dtype=torch.int32, device=dev)
     c = lambda t: None if t is None else t.contiguous()      # noqa: E731
     ts, xs, pattern, noise_var, G, Bm, LLT, t0, m0, P0 = (c(t) for t in (ts, xs, pattern, noise_var, G, Bm, LLT, t0, m0, P0))
-    _hip.check(_hip.lib().cgps_leg_filter(
-        _hip.ptr(ts), _hip.ptr(xs), _hip.ptr(pattern), _hip.ptr(noise_var), _hip.ptr(offsets), B, R, M, _hip.ptr(G),
-        _hip.ptr(Bm), _hip.ptr(LLT), d, obs, _hip.dtype_code(dt), _hip.ptr(t0), _hip.ptr(m0), _hip.ptr(P0), _hip.ptr(mean),
-        _hip.ptr(cov), _hip.ptr(lp), _hip.ptr(zm), _hip.ptr(zc), _hip.ptr(loglik), _hip.ptr(m_end), _hip.ptr(P_end),
-        _hip.ptr(info), _hip.stream_ptr()))
+    data = (_hip.ptr(ts), _hip.ptr(xs), _hip.ptr(pattern), _hip.ptr(noise_var), _hip.ptr(offsets), B, R, M, _hip.ptr(G),
+            _hip.ptr(Bm), _hip.ptr(LLT), d, obs, _hip.dtype_code(dt), _hip.ptr(t0), _hip.ptr(m0), _hip.ptr(P0))
+    res = (_hip.ptr(mean), _hip.ptr(cov), _hip.ptr(lp), _hip.ptr(zm), _hip.ptr(zc), _hip.ptr(loglik), _hip.ptr(m_end),
+           _hip.ptr(P_end), _hip.ptr(info), _hip.stream_ptr())
+    if scan is None:
+        _hip.check(_hip.lib().cgps_leg_filter(*data, *res))
+    else:
+        chunks, fanout = scan
+        ws, nbytes = _hip.filter_scan_workspace(chunks.chunks, M, d, dt, fanout, dev)
+        _hip.check(_hip.lib().cgps_leg_filter_scan(
+            *data, _hip.ptr(chunks.chunk_offsets), _hip.ptr(chunks.chunk_series), _hip.ptr(chunks.series_chunks),
+            chunks.chunks, chunks.L, fanout, _hip.ptr(ws), nbytes, *res))
     return mean, cov, lp, zm, zc, loglik, m_end, P_end, info
 
 
@@ -2231,10 +2287,10 @@ def _filter_empty(lead, obs, d, dt, device):
     return e(obs), e(obs, obs), e(), e(d), e(d, d)
 
 
-def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named):
+def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chunking=None):
     """The filter of the stacked models ``mats`` over a validated, non-empty batch: (the eight tensors of
     ``_filter_rows``, the times of the series' last rows [B]).  ``init`` has the models' axis.  ``named``: whether a
-    failure's message names the model."""
+    failure's message names the model.  ``chunking``: None or the (L, F) of ``_filter_chunking``."""
     Nm, Rm, Bm, Lm = mats
     M, obs, d, dt = Nm.shape[0], Bm.shape[1], Nm.shape[1], Nm.dtype
     if obs > MAX_PATTERN_OBS:
@@ -2250,7 +2306,8 @@ def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named):
     LLT = (_contract(Lm, Lm.transpose(1, 2)) + _scaled_eye(obs, 1e-9, dt, Nm.device)).contiguous()
     xs_c, pattern, nv = _loo_data(xs, observed, noise_var, dt)
     ts_c = ts.to(dt).contiguous()
-    out = _filter_rows(ts_c, xs_c, pattern, nv, plan.offsets, G, Bm.contiguous(), LLT, init)
+    scan = None if chunking is None else (_cached_batch_plan(lengths, Nm.device, _chunk_plan_kind(chunking[0])), chunking[1])
+    out = _filter_rows(ts_c, xs_c, pattern, nv, plan.offsets, G, Bm.contiguous(), LLT, init, scan)
     if cr.CHECK_POSITIVE_DEFINITE:
         bad = int(out[8].item())
         if bad:
@@ -2264,7 +2321,7 @@ def _stack1(m):
     return tuple(t.unsqueeze(0) for t in (m.N, m.R, m.B, m.Lambda))
 
 
-def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None):
+def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk_rows=None):
     """One-step-ahead predictives and filtered states of one series: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
     loglik, state)``.
 
@@ -2280,13 +2337,22 @@ def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None):
     that FOLLOW to continue without refiltering; the gap from ``init.t`` to the first row may be zero but not negative
     (ValueError).  ``init=None``: the prior N(0, I) at the first row.
 
-    The work is SERIAL in the series' rows (cgps_leg_filter, DESIGN.md 4.22: one lane per (series, model) walks its
-    rows): one series of 2^20 rows is one lane's chain of 2^20 steps.  The batched calls are what the kernel is for.
+    ``chunk_rows=None``: the work is SERIAL in the series' rows (cgps_leg_filter, DESIGN.md 4.22: one lane per (series,
+    model) walks its rows): one series of 2^20 rows is one lane's chain of 2^20 steps.  ``chunk_rows=`` an int L, a pair
+    (L, F) or "auto" (``FILTER_CHUNK_ROWS``, ``FILTER_SCAN_FANOUT``): TIME-PARALLEL (cgps_leg_filter_scan, DESIGN.md
+    4.23) -- the series is cut into chunks of L rows, a scan with fan-out F over the chunks' compositions gives every
+    chunk the exact state it starts from, and the serial kernel runs over the chunks as if they were series: chains of
+    about 2 L + F log_F(n / L) steps instead of n.  Same results, shapes and failures; rows [0, L) are the serial call's
+    bit for bit, later rows agree with it to rounding (fp64: the bounds of the serial call against the dense truths;
+    fp32: at most 4x the error of the recursion in torch), ``loglik`` is the sum of the chunks' sums.  Pass it for ONE
+    long series or a few -- 2^20 rows, rank 5, fp64 on one MI355X: 2.03 s serially, 2.43 ms with "auto" (DESIGN.md 4.23);
+    2^14 rows: 30.8 ms and 0.84 ms with (16, 16) -- and for batches as well, see ``filter_predictive_batch``.
     Inference only: runs under ``torch.no_grad``.  Ranks 1..8, obs_dim <= 8, both precisions.  With
     ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming it; with the
     check off that row, all later rows and ``loglik`` are NaN.  CPU tensors behave as ``insample_posterior`` does (there
     is no CPU implementation)."""
     with torch.no_grad():
+        chunking = _filter_chunking(chunk_rows)
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
         observed = _single_series_args(obs, ts, xs, observed, noise_var)
         n = ts.shape[0]
@@ -2297,11 +2363,11 @@ def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None):
             state = FilterState(*(t.reshape(s).to(dt) for t, s in zip(init, ((), (d,), (d, d))))) if init is not None else None
             return FilterPredictive(*_filter_empty((0,), obs, d, dt, ts.device),
                                     torch.zeros((), dtype=torch.float64, device=ts.device), state)
-        out, t_end = _filter_models(_stack1(m), ts, xs, [n], observed, noise_var, init, False)
+        out, t_end = _filter_models(_stack1(m), ts, xs, [n], observed, noise_var, init, False, chunking)
         return FilterPredictive(*(t[0] for t in out[:5]), out[5][0, 0], FilterState(t_end[0], out[6][0, 0], out[7][0, 0]))
 
 
-def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None, init=None):
+def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None):
     """``filter_predictive`` of B independent series in one call: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
     loglik, state)`` with ``loglik`` [B] (fp64) and ``state = FilterState(t [B], mean [B, d], cov [B, d, d])``.
 
@@ -2313,14 +2379,25 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
 
     How: ONE cgps_leg_filter, one lane per series, 64-lane workgroups, no workspace, nothing read on the host unless
     ``cr.CHECK_POSITIVE_DEFINITE``.  The work is SERIAL in a series' rows and parallel across series: 1 024 series of 502
-    rows fill 16 CUs for 502 steps; one series of 2^20 rows is one lane's chain of 2^20 steps (a time-parallel scan is
-    not built).  A series' results do not depend on its place in the batch, bit for bit.
+    rows fill 16 CUs for 502 steps; one series of 2^20 rows is one lane's chain of 2^20 steps.  A series' results do
+    not depend on its place in the batch, bit for bit.
+
+    ``chunk_rows=`` (an int L, a pair (L, F), or "auto"): the time-parallel form of ``filter_predictive``, one
+    cgps_leg_filter_scan over all series -- chunks of L rows that never straddle a series (ceil(n_b / L) per series,
+    planned on the host from ``lengths`` and cached like the batch plan), one scan over all chunks in which a series'
+    first chunk is a reset that is SELECTED, so nothing crosses from one series into the next, a failed one's NaN
+    included.  A series' results then depend on its place in the batch through the grouping of the scan alone: within
+    64 eps of any other place, not bit for bit.  When to pass it (one MI355X, fp64, rank 5, series of 502 rows): measured
+    faster than the serial kernel from 64 series (1.62 -> 1.19 ms with "auto", 1.03 ms with (64, 32)) up to 1 024 series
+    (1.68 -> 1.47 ms, 1.39 ms) -- no crossover inside that range; the longer the series the larger the gain.  Leave it
+    None for the bit-for-bit guarantees above and for ``loglik`` as the sum of the rows in row order.
 
     Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming
     the series and its local row; with the check off that row, the later rows of THAT series, its ``loglik`` and its
     ``state`` are NaN and every other series is untouched.  CPU tensors behave as ``insample_posterior_batch`` does
     (there is no CPU implementation)."""
     with torch.no_grad():
+        chunking = _filter_chunking(chunk_rows)
         ts, xs, lengths, observed, noise_var, dense, bn = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
         if init is not None:
@@ -2335,14 +2412,14 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
             state = FilterState(init[0], init[1][0], init[2][0]) if init is not None else None
             return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
                                     torch.empty(0, dtype=torch.float64, device=ts.device), state)
-        out, t_end = _filter_models(_stack1(m), ts, xs, lengths, observed, noise_var, init, False)
+        out, t_end = _filter_models(_stack1(m), ts, xs, lengths, observed, noise_var, init, False, chunking)
         rows = [t[0] for t in out[:5]]
         if dense:
             rows = [t.reshape(bn + tuple(t.shape[1:])) for t in rows]
         return FilterPredictive(*rows, out[5][0], FilterState(t_end, out[6][0], out[7][0]))
 
 
-def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=None, init=None):
+def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None):
     """``filter_predictive_batch`` of M LEG models for the same B series in one call: slot k of every result is
     ``filter_predictive_batch(ms[k], ...)``, bit for bit; ``loglik`` is [M, B] (fp64) and ``state =
     FilterState(t [B], mean [M, B, d], cov [M, B, d, d])``.  ``logpdf`` [M, ...] holds the terms from which the running
@@ -2355,13 +2432,17 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
     leading dimension M.
 
     How: ONE cgps_leg_filter with grid (ceil(B / 64), M): one lane per (series, model).  The work is SERIAL in a
-    series' rows: one series of 2^20 rows is one lane's chain of 2^20 steps under every model.
+    series' rows: one series of 2^20 rows is one lane's chain of 2^20 steps under every model.  ``chunk_rows=`` (an int
+    L, a pair (L, F), or "auto"): the time-parallel form of ``filter_predictive_batch`` with grid rows for the models
+    (cgps_leg_filter_scan); slot k is still the call on ``ms[k]`` with the same ``chunk_rows``, bit for
+    bit.  When to pass it: as for ``filter_predictive_batch`` (timed with one model only).
 
     Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming
     the model, the series and its local row; with the check off that row and the later rows of that series under THAT
     model, its ``loglik`` and its ``state`` are NaN, and every other series and model is untouched.  CPU tensors raise
     as ``filter_predictive_batch`` does (there is no CPU implementation)."""
     with torch.no_grad():
+        chunking = _filter_chunking(chunk_rows)
         ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
                                                                                           noise_var)
         M, obs, d, dt = len(ms), mats[2].shape[1], mats[0].shape[1], mats[0].dtype
@@ -2374,7 +2455,7 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
             return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
                                     torch.empty(M, 0, dtype=torch.float64, device=ts.device),
                                     FilterState(*init) if init is not None else None)
-        out, t_end = _filter_models(mats, ts, xs, lengths, observed, noise_var, init, True)
+        out, t_end = _filter_models(mats, ts, xs, lengths, observed, noise_var, init, True, chunking)
         rows = list(out[:5])
         if dense:
             rows = [t.reshape((M,) + bn + tuple(t.shape[2:])) for t in rows]

@@ -570,6 +570,31 @@ int cgps_leg_filter(const void* ts, const void* xs, const uint8_t* pattern, cons
                     void* pred_mean, void* pred_cov, void* logpdf, void* z_mean, void* z_cov, double* loglik, void* m_end,
                     void* P_end, int* info, void* stream);
 
+/* cgps_leg_filter in time-parallel form: the same arguments, results and failures, for series whose length, not
+ * whose number, is the work.  Every series is cut into chunks of at most chunk_rows rows that never straddle a series:
+ * chunk_offsets[n_chunks+1] are the chunks' row offsets (chunk c holds rows chunk_offsets[c] .. chunk_offsets[c+1]-1,
+ * series after series), chunk_series[n_chunks] the series of every chunk and series_chunks[B+1] the first chunk of
+ * every series; all three are device arrays.  One lane per (chunk, model) composes the rows of its chunk into one
+ * element of the filter's recursion, a scan over the elements with groups of `fanout` (levels of a tree, one launch
+ * per level up and down; an element that starts a series is selected, never multiplied into) gives every chunk the
+ * state it starts from, and the kernels of cgps_leg_filter then run over the chunks as if they were series.  The first
+ * chunk of every series is cgps_leg_filter's own arithmetic, bit for bit; later rows agree with it to rounding.
+ * loglik is the sum of the chunks' sums, added in chunk order.  A failing row fails as in cgps_leg_filter: the rows
+ * before it are finite, it and the later rows of its series under that model are NaN, info holds 1 + the smallest
+ * failing k R + i.  (A row whose S is not positive definite may fail the series from the start of its chunk on.)
+ * ws / ws_bytes: caller-owned device memory of at least cgps_leg_filter_scan_workspace_bytes(n_chunks, M, d, dtype,
+ * fanout) bytes, 256-byte aligned; z_cov is used as scratch before it is written.  The argument errors of
+ * cgps_leg_filter, and CGPS_ERR_ARG for chunk_rows < 1, fanout < 2, a chunk count that does not fit (fewer than B or
+ * than ceil(R / chunk_rows), more than R), a null or too small workspace. */
+int cgps_leg_filter_scan_workspace_bytes(int64_t n_chunks, int64_t M, int d, int dtype, int64_t fanout, size_t* bytes);
+int cgps_leg_filter_scan(const void* ts, const void* xs, const uint8_t* pattern, const void* noise_var,
+                         const int64_t* row_offsets, int64_t B, int64_t R, int64_t M, const void* G, const void* Bmat,
+                         const void* LLT, int d, int obs, int dtype, const void* t0, const void* m0, const void* P0,
+                         const int64_t* chunk_offsets, const int64_t* chunk_series, const int64_t* series_chunks,
+                         int64_t n_chunks, int64_t chunk_rows, int64_t fanout, void* ws, size_t ws_bytes,
+                         void* pred_mean, void* pred_cov, void* logpdf, void* z_mean, void* z_cov, double* loglik,
+                         void* m_end, void* P_end, int* info, void* stream);
+
 /* ---- time-axis sharding (one shard per GPU / rank) -----------------------------------------
  * The reference has no distributed code; this is the multi-GPU form BASELINE.json asks for.
  * A shard is n_loc consecutive block rows: Rs[n_loc], Os[n_loc-1] (couplings INSIDE the shard),
