@@ -51,6 +51,19 @@ int dispatch(int dtype, int d, Fn&& fn) {
 #undef CGPS_CASE
 }
 
+// The channel axis of the per-row LEG kernels: fn(std::integral_constant<int, O>) with O = obs for 1..4 and O = 8 for
+// everything else (5..8: the kernel masks the channels from obs up at run time).
+template <typename Fn>
+void dispatch_obs(int obs, Fn&& fn) {
+  switch (obs) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 3: fn(std::integral_constant<int, 3>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    default: fn(std::integral_constant<int, 8>{}); break;
+  }
+}
+
 // ---- per-device one-time setup -------------------------------------------------------------------
 // Function attributes (dynamic-LDS limits) and occupancy-derived grid sizes belong to a device,
 // not to the process: a process that drives several GPUs, or two host threads racing the first

@@ -27,6 +27,7 @@
 // row: it and every later row of that series under that model are NaN, the series' log-likelihood and end state are
 // NaN, and info gets 1 + (k R + i) of the first such row (report_fail).
 #pragma once
+#include "cgps_host.h"
 #include "cgps_leg.h"
 #include "cgps_leg_loo.h"
 
@@ -291,17 +292,10 @@ void launch_filter(const T* ts, const T* xs, const unsigned char* pattern, const
   if (R > 1)
     hipLaunchKernelGGL((leg_filter_gaps_kernel<T, D>), dim3((unsigned)((R + FILTER_THREADS - 1) / FILTER_THREADS), (unsigned)M),
                        block, 0, st, ts, R, G, z_cov);
-#define CGPS_FILTER_LAUNCH(OV)                                                                                          \
-  hipLaunchKernelGGL((leg_filter_kernel<T, D, OV>), grid, block, 0, st, ts, xs, pattern, noise, roff, B, R, G, Bm, LLT,  \
-                     obs, t0, m0, P0, pred_mean, pred_cov, logpdf, z_mean, z_cov, loglik, m_end, P_end, info)
-  switch (obs) {
-    case 1: CGPS_FILTER_LAUNCH(1); break;
-    case 2: CGPS_FILTER_LAUNCH(2); break;
-    case 3: CGPS_FILTER_LAUNCH(3); break;
-    case 4: CGPS_FILTER_LAUNCH(4); break;
-    default: CGPS_FILTER_LAUNCH(8); break;
-  }
-#undef CGPS_FILTER_LAUNCH
+  cgps_host::dispatch_obs(obs, [&](auto oc) {
+    hipLaunchKernelGGL((leg_filter_kernel<T, D, decltype(oc)::value>), grid, block, 0, st, ts, xs, pattern, noise, roff, B, R,
+                       G, Bm, LLT, obs, t0, m0, P0, pred_mean, pred_cov, logpdf, z_mean, z_cov, loglik, m_end, P_end, info);
+  });
 }
 
 }  // namespace cgps

@@ -36,55 +36,46 @@ namespace cgps {
 
 using cgps_host::filter_scan_elem_scalars;
 
+// An element, and where its scalars live in a level: A, b, C, h (eta), J row-major in that order, then the reset flag.
 template <typename T, int D>
 struct ScanElem {
   T A[D][D], b[D], C[D][D], h[D], J[D][D];
+  static constexpr int OFF_A = 0, OFF_B = OFF_A + D * D, OFF_C = OFF_B + D, OFF_H = OFF_C + D * D, OFF_J = OFF_H + D,
+                       OFF_FLAG = OFF_J + D * D;
+  static_assert(OFF_FLAG + 1 == filter_scan_elem_scalars(D), "the element's scalars and the flag: cgps_plan.h owns the count");
+  // f(offset, scalar) for every scalar of e (a ScanElem or a const one) in the stored order
+  template <typename E, typename Fn>
+  static __device__ __forceinline__ void visit(E& e, Fn&& f) {
+    mat(OFF_A, e.A, f);
+    vec(OFF_B, e.b, f);
+    mat(OFF_C, e.C, f);
+    vec(OFF_H, e.h, f);
+    mat(OFF_J, e.J, f);
+  }
+  template <typename V, typename Fn>
+  static __device__ __forceinline__ void vec(int off, V (&v)[D], Fn&& f) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) f(off + a, v[a]);
+  }
+  template <typename V, typename Fn>
+  static __device__ __forceinline__ void mat(int off, V (&m)[D][D], Fn&& f) {
+#pragma unroll
+    for (int a = 0; a < D; ++a) vec(off + a * D, m[a], f);
+  }
 };
 
 // element c of a level of n elements under one model: scalar v lives at p[v * n], p = level + model offset + c
 template <typename T, int D>
 __device__ __forceinline__ void scan_load(const T* p, int64_t n, ScanElem<T, D>& e, bool& flag) {
-  int v = 0;
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int c = 0; c < D; ++c) e.A[a][c] = p[(v++) * n];
-#pragma unroll
-  for (int a = 0; a < D; ++a) e.b[a] = p[(v++) * n];
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int c = 0; c < D; ++c) e.C[a][c] = p[(v++) * n];
-#pragma unroll
-  for (int a = 0; a < D; ++a) e.h[a] = p[(v++) * n];
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int c = 0; c < D; ++c) e.J[a][c] = p[(v++) * n];
-  flag = p[v * n] != T(0);
+  ScanElem<T, D>::visit(e, [&](int v, T& x) { x = p[v * n]; });
+  flag = p[ScanElem<T, D>::OFF_FLAG * n] != T(0);
 }
 
 template <typename T, int D>
 __device__ __forceinline__ void scan_store(T* p, int64_t n, const ScanElem<T, D>& e, bool flag, bool poison) {
   const T nan = (T)__builtin_nan("");
-  int v = 0;
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int c = 0; c < D; ++c) p[(v++) * n] = poison ? nan : e.A[a][c];
-#pragma unroll
-  for (int a = 0; a < D; ++a) p[(v++) * n] = poison ? nan : e.b[a];
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int c = 0; c < D; ++c) p[(v++) * n] = poison ? nan : e.C[a][c];
-#pragma unroll
-  for (int a = 0; a < D; ++a) p[(v++) * n] = poison ? nan : e.h[a];
-#pragma unroll
-  for (int a = 0; a < D; ++a)
-#pragma unroll
-    for (int c = 0; c < D; ++c) p[(v++) * n] = poison ? nan : e.J[a][c];
-  p[v * n] = flag ? T(1) : T(0);
+  ScanElem<T, D>::visit(e, [&](int v, const T& x) { p[v * n] = poison ? nan : x; });
+  p[ScanElem<T, D>::OFF_FLAG * n] = flag ? T(1) : T(0);
 }
 
 // K = P L U in place (unit lower L below the diagonal, U on and above it, 1 / U_cc in inv), the exchanges of whole rows
@@ -531,17 +522,18 @@ __global__ __launch_bounds__(FILTER_THREADS) void leg_fscan_starts_kernel(
   r0 = r0 < 0 ? 0 : (r0 >= R ? R - 1 : r0);
   const int64_t slot = k * NC + c;
   const bool first = scoff[b] == c;
+  using Elem = ScanElem<T, D>;
   constexpr int NV = filter_scan_elem_scalars(D);
   const T* __restrict__ prev = elems + (size_t)k * NV * NC + (c > 0 ? c - 1 : 0);
   const int64_t s = k * B + b;
   if (k == 0) t0c[c] = first ? (t0 != nullptr ? t0[b] : ts[r0]) : ts[r0 > 0 ? r0 - 1 : 0];
 #pragma unroll
   for (int a = 0; a < D; ++a) {
-    m0c[slot * D + a] = first ? (m0 != nullptr ? m0[s * D + a] : T(0)) : prev[(size_t)(D * D + a) * NC];
+    m0c[slot * D + a] = first ? (m0 != nullptr ? m0[s * D + a] : T(0)) : prev[(size_t)(Elem::OFF_B + a) * NC];
 #pragma unroll
     for (int q = 0; q < D; ++q)
       P0c[(slot * D + a) * D + q] = first ? (P0 != nullptr ? P0[(s * D + a) * D + q] : (a == q ? T(1) : T(0)))
-                                          : prev[(size_t)(D * D + D + a * D + q) * NC];
+                                          : prev[(size_t)(Elem::OFF_C + a * D + q) * NC];
   }
 }
 
@@ -570,28 +562,20 @@ __global__ __launch_bounds__(FILTER_THREADS) void leg_fscan_series_kernel(
 }
 
 template <typename T, int D>
-void launch_filter_scan(const T* ts, const T* xs, const unsigned char* pattern, const T* noise, const int64_t* roff,
-                        int64_t B, int64_t R, int64_t M, const T* G, const T* Bm, const T* LLT, int obs, const T* t0,
-                        const T* m0, const T* P0, const int64_t* coff, const int64_t* cser, const int64_t* scoff,
-                        int64_t NC, int64_t fanout, char* ws, const cgps_host::FilterScanWs& w, T* pred_mean, T* pred_cov,
-                        T* logpdf, T* z_mean, T* z_cov, double* loglik, T* m_end, T* P_end, int* info, hipStream_t st) {
+void launch_filter_scan(const T* ts, const T* xs, const unsigned char* pattern, const T* noise, int64_t B, int64_t R,
+                        int64_t M, const T* G, const T* Bm, const T* LLT, int obs, const T* t0, const T* m0, const T* P0,
+                        const int64_t* coff, const int64_t* cser, const int64_t* scoff, int64_t NC, int64_t fanout,
+                        char* ws, const cgps_host::FilterScanWs& w, T* pred_mean, T* pred_cov, T* logpdf, T* z_mean,
+                        T* z_cov, double* loglik, T* m_end, T* P_end, int* info, hipStream_t st) {
   using cgps_host::at;
-  (void)roff;
   const dim3 block(FILTER_THREADS);
   auto grid = [&](int64_t n) { return dim3((unsigned)((n + FILTER_THREADS - 1) / FILTER_THREADS), (unsigned)M); };
   T* lev0 = at<T>(ws, w.elem[0]);
   if (R > 1) hipLaunchKernelGGL((leg_fscan_gaps_kernel<T, D>), grid(R), block, 0, st, ts, R, G, z_cov);
-#define CGPS_FSCAN_LAUNCH(OV)                                                                                            \
-  hipLaunchKernelGGL((leg_fscan_chunk_kernel<T, D, OV>), grid(NC), block, 0, st, ts, xs, pattern, noise, coff, cser,    \
-                     scoff, NC, B, R, G, Bm, LLT, obs, t0, m0, P0, (const T*)z_cov, lev0)
-  switch (obs) {
-    case 1: CGPS_FSCAN_LAUNCH(1); break;
-    case 2: CGPS_FSCAN_LAUNCH(2); break;
-    case 3: CGPS_FSCAN_LAUNCH(3); break;
-    case 4: CGPS_FSCAN_LAUNCH(4); break;
-    default: CGPS_FSCAN_LAUNCH(8); break;
-  }
-#undef CGPS_FSCAN_LAUNCH
+  cgps_host::dispatch_obs(obs, [&](auto oc) {
+    hipLaunchKernelGGL((leg_fscan_chunk_kernel<T, D, decltype(oc)::value>), grid(NC), block, 0, st, ts, xs, pattern, noise,
+                       coff, cser, scoff, NC, B, R, G, Bm, LLT, obs, t0, m0, P0, (const T*)z_cov, lev0);
+  });
   for (int l = 0; l < w.levels; ++l) {
     if (w.n[l] < 2) break;
     const bool has_up = l + 1 < w.levels;

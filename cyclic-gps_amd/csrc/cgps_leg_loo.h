@@ -27,6 +27,7 @@
 // fixed order that depends on the series' own rows only (lane t takes local rows t, t + LOO_THREADS, ...; then
 // block_sum2), in double, no atomics: a series' score does not depend on its place in the batch.
 #pragma once
+#include "cgps_host.h"
 #include "cgps_math.h"
 
 namespace cgps {
@@ -254,17 +255,10 @@ void launch_loo(const T* xs, const unsigned char* pattern, const T* noise, const
                 int64_t M, const T* Bm, const T* LLT, int obs, const T* mean, const T* Sd, int leave, T* out_mean,
                 T* out_var, T* out_logpdf, double* out_score, int* info, hipStream_t st) {
   const dim3 grid((unsigned)((R + LOO_THREADS - 1) / LOO_THREADS), (unsigned)M), block(LOO_THREADS);
-#define CGPS_LOO_LAUNCH(OV)                                                                                            \
-  hipLaunchKernelGGL((leg_loo_rows_kernel<T, D, OV>), grid, block, 0, st, xs, pattern, noise, R, Bm, LLT, obs, mean, Sd, \
-                     leave, out_mean, out_var, out_logpdf, info)
-  switch (obs) {
-    case 1: CGPS_LOO_LAUNCH(1); break;
-    case 2: CGPS_LOO_LAUNCH(2); break;
-    case 3: CGPS_LOO_LAUNCH(3); break;
-    case 4: CGPS_LOO_LAUNCH(4); break;
-    default: CGPS_LOO_LAUNCH(8); break;
-  }
-#undef CGPS_LOO_LAUNCH
+  cgps_host::dispatch_obs(obs, [&](auto oc) {
+    hipLaunchKernelGGL((leg_loo_rows_kernel<T, D, decltype(oc)::value>), grid, block, 0, st, xs, pattern, noise, R, Bm, LLT,
+                       obs, mean, Sd, leave, out_mean, out_var, out_logpdf, info);
+  });
   hipLaunchKernelGGL((leg_loo_score_kernel<T>), dim3((unsigned)B, (unsigned)M), block, 0, st, out_logpdf, roff, R,
                      leave == LOO_ENTRY ? obs : 1, out_score);
 }

@@ -116,17 +116,10 @@ int run_observations(const T* z, const uint8_t* pattern, const T* noise, const i
   const int64_t chunks = (groups + cgps::REPL_CHUNK_GROUPS - 1) / cgps::REPL_CHUNK_GROUPS;
   const dim3 grid((unsigned)nb, (unsigned)(chunks < 65535 ? chunks : 65535), (unsigned)M), block(cgps::LEG_THREADS);
   (void)hipMemsetAsync(info, 0, sizeof(int), st);
-#define CGPS_REPL_LAUNCH(OV)                                                                                               \
-  hipLaunchKernelGGL((cgps::leg_observations_kernel<T, OV>), grid, block, 0, st, z, R, d, Bmat, LLT, obs, pattern, noise, roff, \
-                     ids, B, nrhs, groups, seed, stream_ids, x, info)
-  switch (obs) {
-    case 1: CGPS_REPL_LAUNCH(1); break;
-    case 2: CGPS_REPL_LAUNCH(2); break;
-    case 3: CGPS_REPL_LAUNCH(3); break;
-    case 4: CGPS_REPL_LAUNCH(4); break;
-    default: CGPS_REPL_LAUNCH(8); break;
-  }
-#undef CGPS_REPL_LAUNCH
+  dispatch_obs(obs, [&](auto oc) {
+    hipLaunchKernelGGL((cgps::leg_observations_kernel<T, decltype(oc)::value>), grid, block, 0, st, z, R, d, Bmat, LLT, obs,
+                       pattern, noise, roff, ids, B, nrhs, groups, seed, stream_ids, x, info);
+  });
   return check_launch("leg_observations");
 }
 }  // namespace
