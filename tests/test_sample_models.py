@@ -227,7 +227,7 @@ def _replicate_case(d, obs):
     return ms, mats, series, z
 
 
-@pytest.mark.parametrize("d,obs", [(1, 2), (3, 1), (5, 3), (8, 3), (3, 8)])
+@pytest.mark.parametrize("d,obs", [(1, 2), (3, 1), (5, 3), (8, 3), (3, 8), (3, 4), (3, 5), (8, 6), (3, 7), (8, 4)])
 def test_replicates_against_the_definition_fp64(d, obs):
     """M = 3 (default words and [7, 7, 2]) and M = 1; the four modes; S in {1, 3, 9} and 33 (the column-chunk edge)."""
     ms, mats, series, z = _replicate_case(d, obs)
@@ -317,7 +317,7 @@ def test_draws_fp32_are_as_accurate_as_the_one_series_sampler(d):
             assert e_models / s_models <= 4 * e_loop / s_loop, (mode, k, e_models / s_models, e_loop / s_loop)
 
 
-@pytest.mark.parametrize("d,obs", [(1, 2), (3, 1), (5, 3), (8, 3), (3, 8)])
+@pytest.mark.parametrize("d,obs", [(1, 2), (3, 1), (5, 3), (8, 3), (3, 8), (3, 4), (3, 5), (8, 6), (3, 7), (8, 4)])
 def test_replicates_fp32_are_as_accurate_as_the_torch_composition(d, obs):
     """fp32, S in {1, 3, 9, 65} (65 crosses the 64-column chunk): the kernel's largest error against the float64
     reference on the same fp32 inputs, relative to max |x|, is at most four times the error of the same formula as fp32
