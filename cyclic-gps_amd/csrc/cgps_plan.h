@@ -361,6 +361,14 @@ inline FilterScanWs filter_scan_ws(int64_t chunks, int64_t M, int d, size_t s, i
   return w;
 }
 
+// ---- cgps_leg_filter_adjoint (cgps_leg_filter_adjoint.h): E of the gap before every row, then E_bar over it -----------
+// One d x d block per (model, row): [M][R][d][d].
+inline size_t filter_adjoint_ws_bytes(int64_t R, int64_t B, int64_t M, int d, int obs, size_t s) {
+  (void)B;
+  (void)obs;
+  return align_up((size_t)M * (size_t)R * d * d * s);
+}
+
 // ---- passes of the substitution sweeps -------------------------------------------------------------------------
 // Forward pass p reads the surviving rows of pass p - 1 (the caller's y for p = 0) and, when a pass follows, writes
 // [nsurv][D] surviving rows, one spare row, then [tiles][D] owed vectors into buf[p & 1] of its workspace.  Backward

@@ -81,6 +81,8 @@ _SIGNATURES = {
     "cgps_leg_filter_scan_workspace_bytes": (_int, [_i64, _i64, _int, _int, _i64, ctypes.POINTER(_sz)]),
     "cgps_leg_filter_scan": (_int, [_vp] * 5 + [_i64] * 3 + [_vp] * 3 + [_int] * 3 + [_vp] * 6 + [_i64] * 3 + [_vp, _sz]
                              + [_vp] * 10),
+    "cgps_leg_filter_adjoint_workspace_bytes": (_int, [_i64, _i64, _i64, _int, _int, _int, ctypes.POINTER(_sz)]),
+    "cgps_leg_filter_adjoint": (_int, [_vp] * 4 + [_i64] * 3 + [_vp] * 3 + [_int] * 3 + [_vp] * 11 + [_sz] + [_vp] * 9),
     "cgps_record_elems":(_int, [_int, _int, ctypes.POINTER(_i64)]),
     "cgps_shard_reduce": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp, _vp, _vp]),
     "cgps_finish_records": (_int, [_vp, _sz, _vp, _sz, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
@@ -203,6 +205,20 @@ def filter_scan_workspace_bytes(n_chunks, M, d, dtc, fanout):
 def filter_scan_workspace(n_chunks, M, d, dt, fanout, device):
     """A cached scratch tensor for cgps_leg_filter_scan and its byte count."""
     nbytes = filter_scan_workspace_bytes(int(n_chunks), int(M), int(d), dtype_code(dt), int(fanout))
+    return _scratch(_ws_cache, nbytes, device), nbytes
+
+
+@functools.lru_cache(maxsize=512)
+def filter_adjoint_workspace_bytes(R, B, M, d, obs, dtc):
+    """What cgps_leg_filter_adjoint asks for (filter_adjoint_ws_bytes in csrc/cgps_plan.h); host arithmetic."""
+    b = _sz(0)
+    check(lib().cgps_leg_filter_adjoint_workspace_bytes(R, B, M, d, obs, dtc, ctypes.byref(b)))
+    return b.value
+
+
+def filter_adjoint_workspace(R, B, M, d, obs, dt, device):
+    """A cached scratch tensor for cgps_leg_filter_adjoint and its byte count."""
+    nbytes = filter_adjoint_workspace_bytes(int(R), int(B), int(M), int(d), int(obs), dtype_code(dt))
     return _scratch(_ws_cache, nbytes, device), nbytes
 
 

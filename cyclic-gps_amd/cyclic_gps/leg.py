@@ -16,6 +16,7 @@ parallel batched device work done with torch ops; everything block-tridiagonal g
 cyclic_gps.cyclic_reduction, i.e. the HIP kernels.  Tensors follow the device of `ts`.
 """
 import collections
+import contextlib
 import functools
 import math
 import os
@@ -2281,16 +2282,105 @@ def _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init, scan=Non
     return mean, cov, lp, zm, zc, loglik, m_end, P_end, info
 
 
+def _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, zc, m0, P0, cots):
+    """cgps_leg_filter_adjoint: the data and operands of ``_filter_rows``, gap [R] (the time before every row; 0 at a first
+    row without a start state), the saved z_mean / z_cov, the start states or None, and ``cots`` = the cotangents of
+    (mean, cov, logpdf, z_mean, z_cov), each [M, R, ...] or None.  Returns (x_bar [M, R, obs], s_bar [M, R, obs], B_bar
+    [M, B, obs, d], LLT_bar [M, B, obs, obs], m0_bar [M, B, d], P0_bar [M, B, d, d], G_bar partial sums [M, blocks, d, d],
+    gap_bar [M, R]).  Nothing is read on the host."""
+    M, obs, d = Bm.shape
+    R, B, dt, dev = xs.shape[0], offsets.shape[0] - 1, G.dtype, G.device
+    c = lambda t: None if t is None else t.to(dt).contiguous()      # noqa: E731
+    cots = [c(t) for t in cots]
+    for t, tail in zip(cots, ((obs,), (obs, obs), (), (d,), (d, d))):
+        assert t is None or tuple(t.shape) == (M, R) + tail
+    e = lambda *shape: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+    blocks = (R + 63) // 64
+    gx, gs, gB, gL, gm0, gP0, gG, gg = (e(M, R, obs), e(M, R, obs), e(M, B, obs, d), e(M, B, obs, obs), e(M, B, d),
+                                        e(M, B, d, d), e(M, blocks, d, d), e(M, R))
+    ws, nbytes = _hip.filter_adjoint_workspace(R, B, M, d, obs, dt, dev)
+    xs, noise_var, G, Bm, LLT, gap, zm, zc, m0, P0 = (c(t) for t in (xs, noise_var, G, Bm, LLT, gap, zm, zc, m0, P0))
+    _hip.check(_hip.lib().cgps_leg_filter_adjoint(
+        _hip.ptr(xs), _hip.ptr(pattern), _hip.ptr(noise_var), _hip.ptr(offsets), B, R, M, _hip.ptr(G), _hip.ptr(Bm),
+        _hip.ptr(LLT), d, obs, _hip.dtype_code(dt), _hip.ptr(gap), _hip.ptr(zm), _hip.ptr(zc), _hip.ptr(m0), _hip.ptr(P0),
+        *(_hip.ptr(t) for t in cots), _hip.ptr(ws), nbytes, _hip.ptr(gx), _hip.ptr(gs), _hip.ptr(gB), _hip.ptr(gL),
+        _hip.ptr(gm0), _hip.ptr(gP0), _hip.ptr(gG), _hip.ptr(gg), _hip.stream_ptr()))
+    return gx, gs, gB, gL, gm0, gP0, gG, gg
+
+
+class _FilterFn(torch.autograd.Function):
+    """``_filter_rows`` with a backward: the forward is the same launch (serial or time-parallel) and
+    keeps z_mean and z_cov; the backward is ONE cgps_leg_filter_adjoint -- gaps, the serial reverse walk, the Frechet pass
+    -- and a few torch sums.  Inputs: G [M, d, d], Bm [M, obs, d], LLT [M, obs, obs], ts [R], xs [R, obs], noise_var
+    [R, obs] or None, t0 [B], m0 [M, B, d], P0 [M, B, d, d] or three None; ``pattern``, ``offsets`` and ``scan`` carry no
+    gradient.  Outputs: the nine of ``_filter_rows``; info is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, G, Bm, LLT, ts, xs, noise_var, t0, m0, P0, pattern, offsets, scan):
+        ctx.set_materialize_grads(False)
+        init = None if t0 is None else (t0, m0, P0)
+        out = _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init, scan)
+        ctx.save_for_backward(G, Bm, LLT, ts, xs, noise_var, t0, m0, P0, out[3], out[4])
+        ctx.data = (pattern, offsets)
+        ctx.mark_non_differentiable(out[8])
+        return out
+
+    @staticmethod
+    def backward(ctx, g_mean, g_cov, g_lp, g_zm, g_zc, g_ll, g_mend, g_Pend, _g_info):
+        G, Bm, LLT, ts, xs, noise_var, t0, m0, P0, zm, zc = ctx.saved_tensors
+        pattern, offsets = ctx.data
+        M, obs, d = Bm.shape
+        R, B, dt, dev = xs.shape[0], offsets.shape[0] - 1, G.dtype, G.device
+        lens = offsets[1:] - offsets[:-1]
+        sid = torch.repeat_interleave(torch.arange(B, device=dev), lens, output_size=R)      # the series of every row
+        is_first = torch.arange(R, device=dev) == offsets[:-1][sid]
+        has_rows = lens > 0
+        last = (offsets[1:] - 1).clamp_min(0)
+        # loglik is the sum of the series' logpdf; the end state is the last row's filtered state (a series without rows:
+        # the state it started from)
+        if g_ll is not None:
+            add = g_ll.to(dt)[:, sid]
+            g_lp = add if g_lp is None else g_lp + add
+        direct = [None, None]
+        cots = [g_zm, g_zc]
+        for j, (g_end, tail) in enumerate(((g_mend, (d,)), (g_Pend, (d, d)))):
+            if g_end is not None:
+                keep = has_rows.reshape((1, B) + (1,) * len(tail))
+                acc = torch.zeros((M, R) + tail, dtype=dt, device=dev) if cots[j] is None else cots[j].to(dt).clone()
+                cots[j] = acc.index_add_(1, last, g_end.to(dt) * keep)
+                direct[j] = g_end.to(dt) * ~keep
+        gap = ts - torch.roll(ts, 1)
+        gap = torch.where(is_first, (ts - t0[sid]) if t0 is not None else torch.zeros_like(ts), gap)
+        gx, gs, gB, gL, gm0, gP0, gG, gg = _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, zc, m0,
+                                                              P0, [g_mean, g_cov, g_lp] + cots)
+        gg = gg.sum(0)
+        inner = torch.where(is_first, torch.zeros_like(gg), gg)      # gap i = ts[i] - ts[i - 1]
+        g_ts = inner - torch.cat([inner[1:], inner.new_zeros(1)])
+        g_t0 = None
+        if t0 is not None:                                           # gap = ts[first row] - t0
+            head = torch.where(is_first, gg, torch.zeros_like(gg))
+            g_ts = g_ts + head
+            g_t0 = -torch.zeros(B, dtype=dt, device=dev).index_add_(0, sid, head)
+            gm0 = gm0 if direct[0] is None else gm0 + direct[0]
+            gP0 = gP0 if direct[1] is None else gP0 + direct[1]
+        else:
+            gm0 = gP0 = None
+        return (gG.sum(1), gB.sum(1), gL.sum(1), g_ts, gx.sum(0), gs.sum(0) if noise_var is not None else None, g_t0, gm0,
+                gP0, None, None, None)
+
+
 def _filter_empty(lead, obs, d, dt, device):
     """Empty per-row results with the leading dimensions ``lead`` (one of them the empty one) in front of the row axes."""
     e = lambda *shape: torch.empty(tuple(lead) + shape, dtype=dt, device=device)      # noqa: E731
     return e(obs), e(obs, obs), e(), e(d), e(d, d)
 
 
-def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chunking=None):
+def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chunking=None, differentiable=False):
     """The filter of the stacked models ``mats`` over a validated, non-empty batch: (the eight tensors of
     ``_filter_rows``, the times of the series' last rows [B]).  ``init`` has the models' axis.  ``named``: whether a
-    failure's message names the model.  ``chunking``: None or the (L, F) of ``_filter_chunking``."""
+    failure's message names the model.  ``chunking``: None or the (L, F) of ``_filter_chunking``.  ``differentiable``:
+    under grad mode and with an input that requires grad, the launch goes through ``_FilterFn`` and the results carry
+    a graph (the caller must not be under ``torch.no_grad``)."""
     Nm, Rm, Bm, Lm = mats
     M, obs, d, dt = Nm.shape[0], Bm.shape[1], Nm.shape[1], Nm.dtype
     if obs > MAX_PATTERN_OBS:
@@ -2307,7 +2397,13 @@ def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chun
     xs_c, pattern, nv = _loo_data(xs, observed, noise_var, dt)
     ts_c = ts.to(dt).contiguous()
     scan = None if chunking is None else (_cached_batch_plan(lengths, Nm.device, _chunk_plan_kind(chunking[0])), chunking[1])
-    out = _filter_rows(ts_c, xs_c, pattern, nv, plan.offsets, G, Bm.contiguous(), LLT, init, scan)
+    t0, m0, P0 = init if init is not None else (None, None, None)
+    inputs = (G, Bm.contiguous(), LLT, ts_c, xs_c, nv, t0, m0, P0)
+    if differentiable and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in inputs):
+        out = _FilterFn.apply(*inputs, pattern, plan.offsets, scan)
+    else:
+        with torch.no_grad():
+            out = _filter_rows(ts_c, xs_c, pattern, nv, plan.offsets, G, Bm.contiguous(), LLT, init, scan)
     if cr.CHECK_POSITIVE_DEFINITE:
         bad = int(out[8].item())
         if bad:
@@ -2317,11 +2413,16 @@ def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chun
     return out[:8], ts_c[plan.offsets[1:] - 1]
 
 
+def _filter_grad_mode(differentiable):
+    """The context the filter calls run under: ``torch.no_grad`` unless ``differentiable``."""
+    return contextlib.nullcontext() if differentiable else torch.no_grad()
+
+
 def _stack1(m):
     return tuple(t.unsqueeze(0) for t in (m.N, m.R, m.B, m.Lambda))
 
 
-def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk_rows=None):
+def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk_rows=None, differentiable=False):
     """One-step-ahead predictives and filtered states of one series: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
     loglik, state)``.
 
@@ -2347,11 +2448,19 @@ def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk
     fp32: at most 4x the error of the recursion in torch), ``loglik`` is the sum of the chunks' sums.  Pass it for ONE
     long series or a few -- 2^20 rows, rank 5, fp64 on one MI355X: 2.03 s serially, 2.43 ms with "auto" (DESIGN.md 4.23);
     2^14 rows: 30.8 ms and 0.84 ms with (16, 16) -- and for batches as well, see ``filter_predictive_batch``.
-    Inference only: runs under ``torch.no_grad``.  Ranks 1..8, obs_dim <= 8, both precisions.  With
+    ``differentiable=False`` (the default): inference only, the call runs under ``torch.no_grad``.
+    ``differentiable=True``: under grad mode and with an input that requires grad, ``mean``, ``cov``, ``logpdf``,
+    ``z_mean``, ``z_cov``, ``loglik``, ``state.mean`` and ``state.cov`` carry a graph -- same forward launch, same bits --
+    with gradients in the model's N, R, B, Lambda and in ``ts``, ``xs``, ``noise_var``, ``init.t``, ``init.mean``,
+    ``init.cov`` (a mask has none; the gradient in xs and noise_var is exactly 0 at unobserved entries).  The backward
+    is one cgps_leg_filter_adjoint: a reverse walk of the rows, one lane per series, from the saved
+    ``z_mean`` / ``z_cov``.  With ``chunk_rows=`` the forward is the scan and the backward is still that SERIAL walk:
+    the backward of one long series is one lane's chain (a time-parallel backward is not built).  No second derivatives.
+    Ranks 1..8, obs_dim <= 8, both precisions.  With
     ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming it; with the
     check off that row, all later rows and ``loglik`` are NaN.  CPU tensors behave as ``insample_posterior`` does (there
     is no CPU implementation)."""
-    with torch.no_grad():
+    with _filter_grad_mode(differentiable):
         chunking = _filter_chunking(chunk_rows)
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
         observed = _single_series_args(obs, ts, xs, observed, noise_var)
@@ -2363,11 +2472,12 @@ def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk
             state = FilterState(*(t.reshape(s).to(dt) for t, s in zip(init, ((), (d,), (d, d))))) if init is not None else None
             return FilterPredictive(*_filter_empty((0,), obs, d, dt, ts.device),
                                     torch.zeros((), dtype=torch.float64, device=ts.device), state)
-        out, t_end = _filter_models(_stack1(m), ts, xs, [n], observed, noise_var, init, False, chunking)
+        out, t_end = _filter_models(_stack1(m), ts, xs, [n], observed, noise_var, init, False, chunking, differentiable)
         return FilterPredictive(*(t[0] for t in out[:5]), out[5][0, 0], FilterState(t_end[0], out[6][0, 0], out[7][0, 0]))
 
 
-def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None):
+def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None,
+                            differentiable=False):
     """``filter_predictive`` of B independent series in one call: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
     loglik, state)`` with ``loglik`` [B] (fp64) and ``state = FilterState(t [B], mean [B, d], cov [B, d, d])``.
 
@@ -2392,11 +2502,18 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
     (1.68 -> 1.47 ms, 1.39 ms) -- no crossover inside that range; the longer the series the larger the gain.  Leave it
     None for the bit-for-bit guarantees above and for ``loglik`` as the sum of the rows in row order.
 
+    ``differentiable=``: as in ``filter_predictive`` -- False (the default) is inference only under ``torch.no_grad``;
+    True builds the graph for every result but ``state.t``, and the backward is one serial reverse walk per series
+    (cgps_leg_filter_adjoint, one lane per series; with ``chunk_rows=`` too).  ``loglik.sum().backward()`` gives the
+    gradients of ``log_likelihood_batch`` without the smoother's factorisation; per-row weights on ``logpdf``, losses on
+    ``mean`` or ``z_mean`` and the gradient into ``init`` come from nowhere else.
+
     Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming
     the series and its local row; with the check off that row, the later rows of THAT series, its ``loglik`` and its
-    ``state`` are NaN and every other series is untouched.  CPU tensors behave as ``insample_posterior_batch`` does
+    ``state`` are NaN and every other series is untouched (with ``differentiable=True`` the gradient in that series' rows
+    of xs and noise_var, in its ``init`` and in the model's matrices is NaN; the other series' rows are untouched).  CPU tensors behave as ``insample_posterior_batch`` does
     (there is no CPU implementation)."""
-    with torch.no_grad():
+    with _filter_grad_mode(differentiable):
         chunking = _filter_chunking(chunk_rows)
         ts, xs, lengths, observed, noise_var, dense, bn = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
@@ -2412,14 +2529,15 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
             state = FilterState(init[0], init[1][0], init[2][0]) if init is not None else None
             return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
                                     torch.empty(0, dtype=torch.float64, device=ts.device), state)
-        out, t_end = _filter_models(_stack1(m), ts, xs, lengths, observed, noise_var, init, False, chunking)
+        out, t_end = _filter_models(_stack1(m), ts, xs, lengths, observed, noise_var, init, False, chunking, differentiable)
         rows = [t[0] for t in out[:5]]
         if dense:
             rows = [t.reshape(bn + tuple(t.shape[1:])) for t in rows]
         return FilterPredictive(*rows, out[5][0], FilterState(t_end, out[6][0], out[7][0]))
 
 
-def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None):
+def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None,
+                             differentiable=False):
     """``filter_predictive_batch`` of M LEG models for the same B series in one call: slot k of every result is
     ``filter_predictive_batch(ms[k], ...)``, bit for bit; ``loglik`` is [M, B] (fp64) and ``state =
     FilterState(t [B], mean [M, B, d], cov [M, B, d, d])``.  ``logpdf`` [M, ...] holds the terms from which the running
@@ -2435,13 +2553,15 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
     series' rows: one series of 2^20 rows is one lane's chain of 2^20 steps under every model.  ``chunk_rows=`` (an int
     L, a pair (L, F), or "auto"): the time-parallel form of ``filter_predictive_batch`` with grid rows for the models
     (cgps_leg_filter_scan); slot k is still the call on ``ms[k]`` with the same ``chunk_rows``, bit for
-    bit.  When to pass it: as for ``filter_predictive_batch`` (timed with one model only).
+    bit.  When to pass it: as for ``filter_predictive_batch`` (timed with one model only).  ``differentiable=``: as in
+    ``filter_predictive_batch``, with gradients in every model's four matrices; the gradients in ``ts``, ``xs``,
+    ``noise_var`` and ``init.t``, which the models share, are summed over the models.
 
     Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming
     the model, the series and its local row; with the check off that row and the later rows of that series under THAT
     model, its ``loglik`` and its ``state`` are NaN, and every other series and model is untouched.  CPU tensors raise
     as ``filter_predictive_batch`` does (there is no CPU implementation)."""
-    with torch.no_grad():
+    with _filter_grad_mode(differentiable):
         chunking = _filter_chunking(chunk_rows)
         ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
                                                                                           noise_var)
@@ -2455,7 +2575,7 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
             return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
                                     torch.empty(M, 0, dtype=torch.float64, device=ts.device),
                                     FilterState(*init) if init is not None else None)
-        out, t_end = _filter_models(mats, ts, xs, lengths, observed, noise_var, init, True, chunking)
+        out, t_end = _filter_models(mats, ts, xs, lengths, observed, noise_var, init, True, chunking, differentiable)
         rows = list(out[:5])
         if dense:
             rows = [t.reshape((M,) + bn + tuple(t.shape[2:])) for t in rows]

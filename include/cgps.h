@@ -595,6 +595,38 @@ int cgps_leg_filter_scan(const void* ts, const void* xs, const uint8_t* pattern,
                          void* pred_mean, void* pred_cov, void* logpdf, void* z_mean, void* z_cov, double* loglik,
                          void* m_end, void* P_end, int* info, void* stream);
 
+/* Gradients through cgps_leg_filter: the reverse walk of its recursion.  The data arguments, G, Bmat, LLT, d, obs and
+ * dtype are the forward's.  gap[R] replaces ts and t0: the time from the previous row of the series to row i, from the
+ * start state to a series' first row, and 0 at a first row without a start state.  z_mean[M][R][d], z_cov[M][R][d][d]:
+ * what the forward (serial or time-parallel) stored; m0[M][B][d], P0[M][B][d][d]: the start states, or both NULL.
+ * The cotangents of the forward's per-row results, each may be NULL (zero): g_mean[M][R][obs], g_cov[M][R][obs][obs]
+ * (its symmetric part is used), g_logpdf[M][R], g_z_mean[M][R][d], g_z_cov[M][R][d][d] (symmetric part).  The caller
+ * adds the cotangent of loglik to g_logpdf of the series' rows and those of m_end, P_end to g_z_mean, g_z_cov of its
+ * last row.  Three launches: one lane per (row, model) evaluates exp(-1/2 gap G) into the workspace; one lane per
+ * (series, model), grid (ceil(B / 64), M), walks the series' rows from last to first, recomputes every row from the
+ * state saved before it and stores the adjoint of the exponential over it; one lane per (row, model) takes that
+ * through the Frechet derivative of the exponential.  Results:
+ *   g_xs[M][R][obs], g_noise_var[M][R][obs]   per model (the caller sums over the models); exactly 0 at unobserved
+ *                                             entries, whatever xs and noise_var hold there,
+ *   g_Bmat[M][B][obs][d], g_LLT[M][B][obs][obs], g_m0[M][B][d], g_P0[M][B][d][d]   per (model, series); g_LLT and g_P0
+ *                                             are symmetric; the caller sums g_Bmat and g_LLT over the series,
+ *   g_G_partial[M][ceil(R / 64)][d][d]        sums over the rows of one workgroup in a fixed order (the caller adds them),
+ *   g_gap[M][R]                               the gradient in gap, which the caller scatters to ts and t0.
+ * A (model, series) whose forward failed (NaN in its last z_mean, z_cov) gets NaN in its rows of g_xs, g_noise_var
+ * and g_gap, in its g_Bmat, g_LLT, g_m0, g_P0 and so in its model's g_G_partial; other series are untouched.
+ * ws / ws_bytes: caller-owned device memory of at least cgps_leg_filter_adjoint_workspace_bytes(R, B, M, d, obs, dtype)
+ * bytes.  CGPS_ERR_ARG, before anything is launched: a null required pointer, one of m0, P0 without the other, B < 0,
+ * R < 0, M outside 1..65535, d or obs outside 1..8, a workspace that is too small; an unknown dtype:
+ * CGPS_ERR_UNSUPPORTED; B = 0 or R = 0: CGPS_OK, nothing launched. */
+int cgps_leg_filter_adjoint_workspace_bytes(int64_t R, int64_t B, int64_t M, int d, int obs, int dtype, size_t* bytes);
+int cgps_leg_filter_adjoint(const void* xs, const uint8_t* pattern, const void* noise_var, const int64_t* row_offsets,
+                            int64_t B, int64_t R, int64_t M, const void* G, const void* Bmat, const void* LLT, int d,
+                            int obs, int dtype, const void* gap, const void* z_mean, const void* z_cov, const void* m0,
+                            const void* P0, const void* g_mean, const void* g_cov, const void* g_logpdf,
+                            const void* g_z_mean, const void* g_z_cov, void* ws, size_t ws_bytes, void* g_xs,
+                            void* g_noise_var, void* g_Bmat, void* g_LLT, void* g_m0, void* g_P0, void* g_G_partial,
+                            void* g_gap, void* stream);
+
 /* ---- time-axis sharding (one shard per GPU / rank) -----------------------------------------
  * The reference has no distributed code; this is the multi-GPU form BASELINE.json asks for.
  * A shard is n_loc consecutive block rows: Rs[n_loc], Os[n_loc-1] (couplings INSIDE the shard),
