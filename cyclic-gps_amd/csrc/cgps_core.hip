@@ -63,6 +63,9 @@ int cgps_mahal_logdet_levelwise(const void* Rs, const void* Os, const void* x, i
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_mahal_logdet_levelwise", {{"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"x", x, ALIGN_VEC},
+                                                                 {"ws", ws, ALIGN_WS}, {"out2", out2, 8}, {"info", info, 4}}))
+      return rc;
     return run_levelwise<T, D>((const T*)Rs, (const T*)Os, (const T*)x, N, nullptr, nullptr, nullptr, nullptr,
                                (char*)ws, ws_bytes, out2, info, (hipStream_t)stream);
   });
@@ -75,6 +78,10 @@ int cgps_decompose_step(const void* Rs, const void* Os, int64_t n, int d, int dt
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_decompose_step", {{"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"Dk", Dk, ALIGN_VEC},
+                                                         {"Fk", Fk, ALIGN_VEC}, {"Gk", Gk, ALIGN_VEC}, {"Rn", Rn, ALIGN_VEC},
+                                                         {"On", On, ALIGN_VEC}, {"info", info, 4}}))
+      return rc;
     hipStream_t st = (hipStream_t)stream;
     hipMemsetAsync(info, 0, sizeof(int), st);
     const int64_t nb = level_blocks(n);
@@ -93,6 +100,7 @@ int cgps_logdet_factor(const void* Dp, int64_t N, int d, int dtype, void* ws, si
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_logdet_factor", {{"Dp", Dp, ALIGN_VEC}, {"ws", ws, ALIGN_WS}, {"out", out, 8}})) return rc;
     hipStream_t st = (hipStream_t)stream;
     double* partial = at<double>((char*)ws, w.partial);
     int64_t nb = (N * D + 255) / 256;

@@ -116,6 +116,11 @@ int cgps_decompose_solve(const void* Rs, const void* Os, const void* y, int64_t 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_decompose_solve", {{"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"y", y, ALIGN_VEC},
+                                                          {"Dp", Dp, ALIGN_VEC}, {"Fp", Fp, ALIGN_VEC}, {"Gp", Gp, ALIGN_VEC},
+                                                          {"xcrr", xcrr, ALIGN_VEC}, {"x", x, ALIGN_VEC}, {"ws", ws, ALIGN_WS},
+                                                          {"info", info, 4}}))
+      return rc;
     const DecomposeSolveWs w = decompose_solve_ws(N, D, sizeof(T));
     if (ws_bytes < w.total) return fail(CGPS_ERR_ARG, "workspace too small: %zu < %zu", ws_bytes, w.total);
     const size_t main_bytes = w.main.bytes;      // what decompose and the sweeps use, one after the other
@@ -135,7 +140,7 @@ int cgps_decompose_solve(const void* Rs, const void* Os, const void* y, int64_t 
       Layout L;
       make_layout(N, L);
       const int l = rhs_levels;
-      rc = cgps_halfsolve((const T*)Dp + L.offD[l] * D * D, (const T*)Fp + L.offF[l] * D * D, (const T*)Gp + L.offG[l] * D * D,
+      rc = halfsolve_unchecked((const T*)Dp + L.offD[l] * D * D, (const T*)Fp + L.offF[l] * D * D, (const T*)Gp + L.offG[l] * D * D,
                           L.ms[l], d, dtype, 1, ynext, (T*)xcrr + L.offD[l] * D, ws, main_bytes, nullptr, stream);
     } else {
       rc = cgps_halfsolve(Dp, Fp, Gp, N, d, dtype, 1, y, xcrr, ws, main_bytes, nullptr, stream);
@@ -152,6 +157,10 @@ int cgps_decompose(const void* Rs, const void* Os, int64_t N, int d, int dtype, 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_decompose", {{"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"Dp", Dp, ALIGN_VEC},
+                                                    {"Fp", Fp, ALIGN_VEC}, {"Gp", Gp, ALIGN_VEC}, {"ws", ws, ALIGN_WS},
+                                                    {"info", info, 4}}))
+      return rc;
     if (!levelwise_solve_requested())
       return run_decompose_passes<T, D>((const T*)Rs, (const T*)Os, N, (T*)Dp, (T*)Fp, (T*)Gp, (char*)ws, ws_bytes, info,
                                         (hipStream_t)stream);

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 
@@ -107,6 +108,29 @@ LevelBuf<T> carve(char* ws, const LevelWs& w, int i, int d, bool with_mats, bool
 }
 
 inline bool bad_common(int64_t N, int d) { return N < 1 || d < 1; }
+
+// ---- alignment of the caller's pointers (include/cgps.h, Conventions; the table of who reads what: DESIGN 3.2) ------
+// Arrays of blocks and of vectors are read and written 16 bytes at a time (Vec16 in cgps_math.h), workspaces are cut
+// into 256-byte regions, everything else is accessed by element.  A null pointer is not this check's business.
+constexpr size_t ALIGN_VEC = 16, ALIGN_WS = 256;
+inline size_t elem_bytes(int dtype) { return dtype == CGPS_F32 ? 4 : 8; }
+struct PtrArg {
+  const char* name;
+  const void* p;
+  size_t align;
+};
+inline bool misaligned(const void* p, size_t align) { return p && (reinterpret_cast<uintptr_t>(p) % align) != 0; }
+// CGPS_OK, or CGPS_ERR_ARG with a message that names the first argument off its boundary; before anything is launched
+inline int check_alignment(const char* entry, std::initializer_list<PtrArg> args) {
+  for (const PtrArg& a : args)
+    if (misaligned(a.p, a.align))
+      return fail(CGPS_ERR_ARG, "%s: %s = %p is not aligned to %zu bytes", entry, a.name, a.p, a.align);
+  return CGPS_OK;
+}
+// cgps_halfsolve without the alignment check, for cgps_decompose_solve: the sub-system of the levels its first pass
+// leaves starts at a level offset inside the packed factor (cgps_solve.hip)
+int halfsolve_unchecked(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype, int nrhs, const void* y,
+                        void* xcrr, void* ws, size_t ws_bytes, double* mahal_out, void* stream);
 
 inline bool levelwise_solve_requested() {
   static const int v = [] {

@@ -113,6 +113,9 @@ int cgps_inverse_blocks(const void* Dp, const void* Fp, const void* Gp, int64_t 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_inverse_blocks", {{"Dp", Dp, ALIGN_VEC}, {"Fp", Fp, ALIGN_VEC}, {"Gp", Gp, ALIGN_VEC},
+                                                         {"Sd", Sd, ALIGN_VEC}, {"So", So, ALIGN_VEC}, {"ws", ws, ALIGN_WS}}))
+      return rc;
     return run_inverse<T, D>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, (T*)Sd, (T*)So, (char*)ws, ws_bytes,
                              (hipStream_t)stream);
   });
@@ -125,6 +128,9 @@ int cgps_mahal_logdet_adjoint(void* Sd, void* So, const void* w, int64_t N, int 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_mahal_logdet_adjoint", {{"Sd", Sd, ALIGN_VEC}, {"So", So, ALIGN_VEC}, {"w", w, ALIGN_VEC},
+                                                               {"gm", gm, elem_bytes(dtype)}, {"gl", gl, elem_bytes(dtype)}}))
+      return rc;
     const int64_t total = (2 * N - 1) * D * D;
     int64_t nb = (total + cgps::ADJ_THREADS - 1) / cgps::ADJ_THREADS;
     if (nb > 16384) nb = 16384;
@@ -141,6 +147,10 @@ int cgps_mahal_logdet_adjoint_seg(void* Sd, void* So, const void* w, const int* 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_mahal_logdet_adjoint_seg", {{"Sd", Sd, ALIGN_VEC}, {"So", So, ALIGN_VEC}, {"w", w, ALIGN_VEC},
+                                                                   {"seg", seg, 4}, {"gm", gm, elem_bytes(dtype)},
+                                                                   {"gl", gl, elem_bytes(dtype)}}))
+      return rc;
     const int64_t total = (2 * N - 1) * D * D;
     int64_t nb = (total + cgps::ADJ_THREADS - 1) / cgps::ADJ_THREADS;
     if (nb > 16384) nb = 16384;

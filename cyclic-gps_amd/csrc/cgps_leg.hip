@@ -15,6 +15,7 @@ int cgps_peg_precision(const void* ts, const void* G, int64_t N, int d, int dtyp
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_peg_precision", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"info", info, 4}})) return rc;
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(info, 0, sizeof(int), st);
     const int64_t nb = (N + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
@@ -31,6 +32,7 @@ int cgps_peg_precision_adjoint(const void* ts, const void* G, int64_t N, int d, 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_peg_precision_adjoint", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"gRs", gRs, ALIGN_VEC}, {"gOs", gOs, ALIGN_VEC}, {"gG_partial", gG_partial, elem_bytes(dtype)}, {"gtau", gtau, elem_bytes(dtype)}})) return rc;
     const int64_t nb = (N - 1 + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
     hipLaunchKernelGGL((cgps::peg_precision_adjoint_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEG_THREADS), 0,
                        (hipStream_t)stream, (const T*)ts, (const T*)G, N, (const T*)gRs, (const T*)gOs, (T*)gG_partial,
@@ -46,6 +48,7 @@ int cgps_peg_precision_seg(const void* ts, const void* G, const unsigned char* c
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_peg_precision_seg", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"info", info, 4}})) return rc;
     hipStream_t st = (hipStream_t)stream;
     (void)hipMemsetAsync(info, 0, sizeof(int), st);
     const int64_t nb = (N + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
@@ -62,6 +65,7 @@ int cgps_peg_precision_adjoint_seg(const void* ts, const void* G, const unsigned
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_peg_precision_adjoint_seg", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"gRs", gRs, ALIGN_VEC}, {"gOs", gOs, ALIGN_VEC}, {"gG_partial", gG_partial, elem_bytes(dtype)}, {"gtau", gtau, elem_bytes(dtype)}})) return rc;
     const int64_t nb = (N - 1 + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
     hipLaunchKernelGGL((cgps::peg_precision_adjoint_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEG_THREADS), 0,
                        (hipStream_t)stream, (const T*)ts, (const T*)G, N, (const T*)gRs, (const T*)gOs, (T*)gG_partial,
@@ -78,6 +82,7 @@ int cgps_peg_precision_models(const void* ts, const void* G, const unsigned char
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_peg_precision_models", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"info", info, 4}})) return rc;
     if constexpr (!cgps::peg_models_supported<T, D>()) {
       return fail(CGPS_ERR_UNSUPPORTED, "cgps_peg_precision_models: not built for this block size (d = 8, fp64 d = 6)");
     } else {
@@ -102,6 +107,7 @@ int cgps_peg_precision_adjoint_models(const void* ts, const void* G, const unsig
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_peg_precision_adjoint_models", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"gRs", gRs, ALIGN_VEC}, {"gOs", gOs, ALIGN_VEC}, {"gG_partial", gG_partial, elem_bytes(dtype)}, {"gtau", gtau, elem_bytes(dtype)}})) return rc;
     if constexpr (!cgps::peg_models_supported<T, D>()) {
       return fail(CGPS_ERR_UNSUPPORTED, "cgps_peg_precision_adjoint_models: not built for this block size (d = 8, fp64 d = 6)");
     } else {
@@ -126,6 +132,7 @@ int cgps_leg_intercast(const void* ts, int64_t n, const void* target_ts, int64_t
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_intercast", {{"ts", ts, elem_bytes(dtype)}, {"target_ts", target_ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"ip_mean", ip_mean, elem_bytes(dtype)}, {"ip_cov_diag", ip_cov_diag, ALIGN_VEC}, {"ip_cov_offdiag", ip_cov_offdiag, ALIGN_VEC}, {"out_mean", out_mean, elem_bytes(dtype)}, {"out_cov", out_cov, ALIGN_VEC}})) return rc;
     const int64_t nb = (p + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
     hipLaunchKernelGGL((cgps::leg_intercast_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEG_THREADS), 0,
                        (hipStream_t)stream, (const T*)ts, n, (const T*)target_ts, p, (const T*)G, (const T*)ip_mean,
@@ -147,6 +154,7 @@ int cgps_leg_intercast_seg(const void* ts, const int64_t* row_offsets, const voi
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_intercast_seg", {{"ts", ts, elem_bytes(dtype)}, {"row_offsets", row_offsets, 8}, {"target_ts", target_ts, elem_bytes(dtype)}, {"target_offsets", target_offsets, 8}, {"G", G, elem_bytes(dtype)}, {"ip_mean", ip_mean, elem_bytes(dtype)}, {"ip_cov_diag", ip_cov_diag, ALIGN_VEC}, {"ip_cov_offdiag", ip_cov_offdiag, ALIGN_VEC}, {"out_mean", out_mean, elem_bytes(dtype)}, {"out_cov", out_cov, ALIGN_VEC}})) return rc;
     const int64_t nb = (P + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
     if (nb > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_intercast_seg: P = %lld targets, too many for one launch", (long long)P);
     hipLaunchKernelGGL((cgps::leg_intercast_seg_kernel<T, D>), dim3((unsigned)nb), dim3(cgps::LEG_THREADS), 0,
@@ -172,6 +180,7 @@ int cgps_leg_posterior_blocks_seg(const void* ts, const void* G, const unsigned 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_posterior_blocks_seg", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"term", term, ALIGN_VEC}, {"K_Rs", K_Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"info", info, 4}})) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nb = (N + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
     if (nb > 0x7fffffffLL) return fail(CGPS_ERR_ARG, "cgps_leg_posterior_blocks_seg: N = %lld rows, too many for one launch", (long long)N);
@@ -207,6 +216,7 @@ int cgps_leg_posterior_blocks_models(const void* ts, const void* G, const unsign
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_posterior_blocks_models", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"term", term, ALIGN_VEC}, {"K_Rs", K_Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"info", info, 4}})) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nb = (R + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
     if (nb > 0x7fffffffLL)
@@ -241,6 +251,7 @@ int cgps_leg_intercast_models(const void* ts, const int64_t* row_offsets, const 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_intercast_models", {{"ts", ts, elem_bytes(dtype)}, {"row_offsets", row_offsets, 8}, {"target_ts", target_ts, elem_bytes(dtype)}, {"target_offsets", target_offsets, 8}, {"G", G, elem_bytes(dtype)}, {"ip_mean", ip_mean, elem_bytes(dtype)}, {"ip_cov_diag", ip_cov_diag, ALIGN_VEC}, {"ip_cov_offdiag", ip_cov_offdiag, ALIGN_VEC}, {"out_mean", out_mean, elem_bytes(dtype)}, {"out_cov", out_cov, ALIGN_VEC}})) return rc;
     const int64_t nb = (P + cgps::LEG_THREADS - 1) / cgps::LEG_THREADS;
     if (nb > 0x7fffffffLL)
       return fail(CGPS_ERR_ARG, "cgps_leg_intercast_models: P = %lld targets, too many for one launch", (long long)P);

@@ -90,6 +90,7 @@ int cgps_leg_filter_scan(const void* ts, const void* xs, const uint8_t* pattern,
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_filter_scan", {{"ws", ws, ALIGN_WS}})) return rc;
     (void)hipMemsetAsync(info, 0, sizeof(int), (hipStream_t)stream);
     cgps::launch_filter_scan<T, D>((const T*)ts, (const T*)xs, pattern, (const T*)noise_var, B, R, M, (const T*)G,
                                    (const T*)Bmat, (const T*)LLT, obs, (const T*)t0, (const T*)m0, (const T*)P0,

@@ -45,6 +45,7 @@ int cgps_leg_filter_adjoint(const void* xs, const uint8_t* pattern, const void* 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_filter_adjoint", {{"ws", ws, ALIGN_WS}})) return rc;
     cgps::launch_filter_adjoint<T, D>((const T*)xs, pattern, (const T*)noise_var, row_offsets, B, R, M, (const T*)G,
                                       (const T*)Bmat, (const T*)LLT, obs, (const T*)gap, (const T*)z_mean,
                                       (const T*)z_cov, (const T*)m0, (const T*)P0, (const T*)g_mean, (const T*)g_cov,

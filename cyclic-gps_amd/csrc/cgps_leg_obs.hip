@@ -29,6 +29,12 @@ int cgps_leg_mahal_logdet_pair_obs(const void* ts, const void* G, const void* A_
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_mahal_logdet_pair_obs", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"A_table", A_table, elem_bytes(dtype)},
+                                                                  {"v", v, elem_bytes(dtype)}, {"ws", ws, ALIGN_WS}, {"out4", out4, 8}, {"info2", info2, 4}})) return rc;
+    if constexpr (cgps::leg_source_supported<T, D>())
+      if (ws_bytes < leg_pair_ws_bytes(N, D, sizeof(T)))
+        return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_obs (that of cgps_leg_mahal_logdet_pair): %zu < %zu", ws_bytes,
+                    leg_pair_ws_bytes(N, D, sizeof(T)));
     const int rc = cgps::run_tile_leg<T, D, 2>((const T*)ts, (const T*)G, (const T*)A_table, (const T*)v, N, (char*)ws, ws_bytes,
                                                out4, info2, (hipStream_t)stream, true, pattern, P);
     if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_obs (that of cgps_leg_mahal_logdet_pair)");
@@ -45,6 +51,12 @@ int cgps_leg_mahal_logdet_pair_w(const void* ts, const void* G, const void* basi
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_mahal_logdet_pair_w", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)}, {"basis", basis, elem_bytes(dtype)},
+                                                                {"weights", weights, elem_bytes(dtype)}, {"v", v, elem_bytes(dtype)}, {"ws", ws, ALIGN_WS}, {"out4", out4, 8}, {"info2", info2, 4}})) return rc;
+    if constexpr (cgps::leg_source_supported<T, D>())
+      if (ws_bytes < leg_pair_ws_bytes(N, D, sizeof(T)))
+        return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_w (that of cgps_leg_mahal_logdet_pair): %zu < %zu", ws_bytes,
+                    leg_pair_ws_bytes(N, D, sizeof(T)));
     const int rc = cgps::run_tile_leg<T, D, 3>((const T*)ts, (const T*)G, (const T*)basis, (const T*)v, N, (char*)ws, ws_bytes,
                                                out4, info2, (hipStream_t)stream, true, (const unsigned char*)weights, Kb);
     if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair_w (that of cgps_leg_mahal_logdet_pair)");

@@ -18,10 +18,15 @@ int cgps_mahal_logdet(const void* Rs, const void* Os, const void* x, int64_t N, 
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_mahal_logdet", {{"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"x", x, ALIGN_VEC},
+                                                       {"ws", ws, ALIGN_WS}, {"out2", out2, 8}, {"info", info, 4}}))
+      return rc;
     if constexpr (!cgps::tile_supported<T, D>()) {
       return run_levelwise<T, D>((const T*)Rs, (const T*)Os, (const T*)x, N, nullptr, nullptr, nullptr, nullptr,
                                  (char*)ws, ws_bytes, out2, info, (hipStream_t)stream);
     } else {
+      if (ws_bytes < mahal_logdet_ws_bytes(N, D, sizeof(T)))
+        return fail(CGPS_ERR_ARG, "workspace too small for cgps_mahal_logdet: %zu < %zu", ws_bytes, mahal_logdet_ws_bytes(N, D, sizeof(T)));
       int rc = cgps::run_tile_mahal_logdet<T, D>((const T*)Rs, (const T*)Os, (const T*)x, N, (char*)ws, ws_bytes,
                                                  out2, info, (hipStream_t)stream, g_prof_start, g_prof_stop);
       g_prof_start = g_prof_stop = nullptr;
@@ -45,9 +50,15 @@ int cgps_shard_reduce(const void* Rs, const void* Os, const void* x, const void*
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_shard_reduce", {{"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"x", x, ALIGN_VEC},
+                                                       {"O_left", O_left, ALIGN_VEC}, {"ws", ws, ALIGN_WS},
+                                                       {"record_out", record_out, ALIGN_VEC}, {"partial_out", partial_out, 8}}))
+      return rc;
     if constexpr (!cgps::tile_supported<T, D>()) {
       return fail(CGPS_ERR_UNSUPPORTED, "sharded reduction is built for fp64 d<=5 and fp32 d<=8");
     } else {
+      if (ws_bytes < mahal_logdet_ws_bytes(n_loc, D, sizeof(T)))
+        return fail(CGPS_ERR_ARG, "workspace too small for cgps_shard_reduce: %zu < %zu", ws_bytes, mahal_logdet_ws_bytes(n_loc, D, sizeof(T)));
       int rc = cgps::run_tile_mahal_logdet<T, D>((const T*)Rs, (const T*)Os, (const T*)x, n_loc, (char*)ws, ws_bytes,
                                                  nullptr, nullptr, (hipStream_t)stream, g_prof_start, g_prof_stop,
                                                  (const T*)O_left, (T*)record_out, partial_out);
@@ -66,6 +77,9 @@ int cgps_finish_records(const void* records, size_t record_stride_bytes, const d
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_finish_records", {{"records", records, ALIGN_VEC}, {"partials", partials, 8},
+                                                         {"out2", out2, 8}, {"info", info, 4}}))
+      return rc;
     if constexpr (!cgps::tile_supported<T, D>()) {
       return fail(CGPS_ERR_UNSUPPORTED, "sharded reduction is built for fp64 d<=5 and fp32 d<=8");
     } else {
@@ -88,6 +102,13 @@ int cgps_leg_mahal_logdet(const void* ts, const void* G, const void* A, const vo
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_mahal_logdet", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)},
+                                                           {"A", A, elem_bytes(dtype)}, {"v", v, elem_bytes(dtype)},
+                                                           {"ws", ws, ALIGN_WS}, {"out2", out2, 8}, {"info", info, 4}}))
+      return rc;
+    if constexpr (cgps::leg_source_supported<T, D>())             // (elsewhere: CGPS_ERR_UNSUPPORTED, below)
+      if (ws_bytes < mahal_logdet_ws_bytes(N, D, sizeof(T)))
+        return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet: %zu < %zu", ws_bytes, mahal_logdet_ws_bytes(N, D, sizeof(T)));
     const int rc = cgps::run_tile_leg<T, D>((const T*)ts, (const T*)G, (const T*)A, (const T*)v, N, (char*)ws, ws_bytes, out2,
                                             info, (hipStream_t)stream);
     if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet");
@@ -103,6 +124,14 @@ int cgps_leg_mahal_logdet_pair(const void* ts, const void* G, const void* A, con
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_leg_mahal_logdet_pair", {{"ts", ts, elem_bytes(dtype)}, {"G", G, elem_bytes(dtype)},
+                                                                {"A", A, elem_bytes(dtype)}, {"v", v, elem_bytes(dtype)},
+                                                                {"ws", ws, ALIGN_WS}, {"out4", out4, 8}, {"info2", info2, 4}}))
+      return rc;
+    if constexpr (cgps::leg_source_supported<T, D>())
+      if (ws_bytes < leg_pair_ws_bytes(N, D, sizeof(T)))
+        return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair (twice cgps_mahal_logdet's, each rounded up to 256 bytes): %zu < %zu",
+                    ws_bytes, leg_pair_ws_bytes(N, D, sizeof(T)));
     const int rc = cgps::run_tile_leg<T, D>((const T*)ts, (const T*)G, (const T*)A, (const T*)v, N, (char*)ws, ws_bytes, out4,
                                             info2, (hipStream_t)stream, true);
     if (rc == -1) return fail(CGPS_ERR_ARG, "workspace too small for cgps_leg_mahal_logdet_pair (twice cgps_mahal_logdet's, each rounded up to 256 bytes)");
@@ -132,6 +161,9 @@ int cgps_mahal_logdet_batch(const void* Rs, const void* Os, const void* x, const
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_mahal_logdet_batch", {{"Rs", Rs, ALIGN_VEC}, {"Os", Os, ALIGN_VEC}, {"x", x, ALIGN_VEC},
+                                                             {"offsets", offsets, 8}, {"out2", out2, 8}, {"info", info, 4}}))
+      return rc;
     if constexpr (!cgps::mahal_batch_supported<T, D>()) {
       return fail(CGPS_ERR_UNSUPPORTED, "cgps_mahal_logdet_batch: not built for this block size (d = 8, fp64 d = 6): reduce each system with cgps_mahal_logdet");
     } else {

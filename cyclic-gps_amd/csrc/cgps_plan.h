@@ -320,6 +320,10 @@ inline size_t mahal_logdet_ws_bytes(int64_t N, int d, size_t s) {
   return max_bytes(level_ws(N, d, s, true, true).total, tile_ws(N, d, s).total);
 }
 
+// what include/cgps.h states for the pair forms: twice cgps_mahal_logdet's, each half rounded up to 256 bytes
+inline size_t leg_pair_ws_bytes(int64_t N, int d, size_t s) { return 2 * align_up(mahal_logdet_ws_bytes(N, d, s)); }
+// (The entry points hold the caller to these stated sizes, not to the sometimes smaller part that the path taken cuts up.)
+
 // ---- cgps_leg_filter_scan (cgps_leg_filter_scan.h): the time-parallel filter's levels of elements and chunk states ----
 // Level 0 holds one element per (model, chunk), level l + 1 one per group of `fanout` elements of level l, up to the
 // first level of at most `fanout` elements (one group).  An element is filter_scan_elem_scalars(d) scalars (A, b, C,

@@ -148,6 +148,9 @@ int cgps_sample(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_sample", {{"Dp", Dp, ALIGN_VEC}, {"Fp", Fp, ALIGN_VEC}, {"Gp", Gp, ALIGN_VEC},
+                                                 {"mean", mean, ALIGN_VEC}, {"x", x, ALIGN_VEC}, {"ws", ws, ALIGN_WS}}))
+      return rc;
     switch (cgps::panel_width(nrhs > 8 ? 8 : (int)nrhs)) {
       case 2: return run_sample<T, D, 2>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)mean, seed, stream_id, (T*)x,
                                          (char*)ws, ws_bytes, (hipStream_t)stream);

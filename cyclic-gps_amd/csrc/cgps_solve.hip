@@ -365,6 +365,28 @@ int run_panels_any(PanelOp op, const T* Dp, const T* Fp, const T* Gp, int64_t N,
     default: return run_panels<T, D, 8>(op, Dp, Fp, Gp, N, nrhs, y, out, ws, ws_bytes, mahal_out, st);
   }
 }
+
+// cgps_halfsolve (aligned = true: the caller's pointers are checked) and the call cgps_decompose_solve makes on the
+// sub-system of the levels its first pass leaves, whose factor starts at a level offset (halfsolve_unchecked)
+int halfsolve_any(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype, int nrhs, const void* y,
+                  void* xcrr, void* ws, size_t ws_bytes, double* mahal_out, void* stream, bool aligned) {
+  if (bad_common(N, d) || nrhs < 1 || !Dp || !Fp || !Gp || !y || !xcrr || !ws)
+    return fail(CGPS_ERR_ARG, "cgps_halfsolve: null pointer, N < 1 or nrhs < 1");
+  return dispatch(dtype, d, [&](auto t, auto dc) {
+    using T = decltype(t);
+    constexpr int D = decltype(dc)::value;
+    if (aligned)
+      if (int rc = check_alignment("cgps_halfsolve", {{"Dp", Dp, ALIGN_VEC}, {"Fp", Fp, ALIGN_VEC}, {"Gp", Gp, ALIGN_VEC},
+                                                      {"y", y, ALIGN_VEC}, {"xcrr", xcrr, ALIGN_VEC}, {"ws", ws, ALIGN_WS},
+                                                      {"mahal_out", mahal_out, 8}}))
+        return rc;
+    if (nrhs > 1)
+      return run_panels_any<T, D>(PanelOp::Half, (const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)y, (T*)xcrr,
+                                  (char*)ws, ws_bytes, mahal_out, (hipStream_t)stream);
+    return run_halfsolve<T, D>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, (const T*)y, (T*)xcrr, (char*)ws, ws_bytes,
+                               mahal_out, (hipStream_t)stream);
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -383,18 +405,17 @@ int cgps_solve_workspace_bytes(int64_t N, int d, int dtype, int op, int nrhs, si
 
 int cgps_halfsolve(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype, int nrhs, const void* y,
                    void* xcrr, void* ws, size_t ws_bytes, double* mahal_out, void* stream) {
-  if (bad_common(N, d) || nrhs < 1 || !Dp || !Fp || !Gp || !y || !xcrr || !ws)
-    return fail(CGPS_ERR_ARG, "cgps_halfsolve: null pointer, N < 1 or nrhs < 1");
-  return dispatch(dtype, d, [&](auto t, auto dc) {
-    using T = decltype(t);
-    constexpr int D = decltype(dc)::value;
-    if (nrhs > 1)
-      return run_panels_any<T, D>(PanelOp::Half, (const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)y, (T*)xcrr,
-                                  (char*)ws, ws_bytes, mahal_out, (hipStream_t)stream);
-    return run_halfsolve<T, D>((const T*)Dp, (const T*)Fp, (const T*)Gp, N, (const T*)y, (T*)xcrr, (char*)ws, ws_bytes,
-                               mahal_out, (hipStream_t)stream);
-  });
+  return halfsolve_any(Dp, Fp, Gp, N, d, dtype, nrhs, y, xcrr, ws, ws_bytes, mahal_out, stream, true);
 }
+
+}  // extern "C"
+
+int cgps_host::halfsolve_unchecked(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype, int nrhs,
+                                   const void* y, void* xcrr, void* ws, size_t ws_bytes, double* mahal_out, void* stream) {
+  return halfsolve_any(Dp, Fp, Gp, N, d, dtype, nrhs, y, xcrr, ws, ws_bytes, mahal_out, stream, false);
+}
+
+extern "C" {
 
 int cgps_backsolve(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d, int dtype, int nrhs,
                    const void* ycrr, void* x, void* ws, size_t ws_bytes, void* stream) {
@@ -403,6 +424,9 @@ int cgps_backsolve(const void* Dp, const void* Fp, const void* Gp, int64_t N, in
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_backsolve", {{"Dp", Dp, ALIGN_VEC}, {"Fp", Fp, ALIGN_VEC}, {"Gp", Gp, ALIGN_VEC},
+                                                    {"ycrr", ycrr, ALIGN_VEC}, {"x", x, ALIGN_VEC}, {"ws", ws, ALIGN_WS}}))
+      return rc;
     if (nrhs > 1)
       return run_panels_any<T, D>(PanelOp::Back, (const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)ycrr, (T*)x,
                                   (char*)ws, ws_bytes, nullptr, (hipStream_t)stream);
@@ -418,6 +442,9 @@ int cgps_solve(const void* Dp, const void* Fp, const void* Gp, int64_t N, int d,
   return dispatch(dtype, d, [&](auto t, auto dc) {
     using T = decltype(t);
     constexpr int D = decltype(dc)::value;
+    if (int rc = check_alignment("cgps_solve", {{"Dp", Dp, ALIGN_VEC}, {"Fp", Fp, ALIGN_VEC}, {"Gp", Gp, ALIGN_VEC},
+                                                {"y", y, ALIGN_VEC}, {"x", x, ALIGN_VEC}, {"ws", ws, ALIGN_WS}}))
+      return rc;
     if (nrhs > 1)
       return run_panels_any<T, D>(PanelOp::Solve, (const T*)Dp, (const T*)Fp, (const T*)Gp, N, nrhs, (const T*)y, (T*)x,
                                   (char*)ws, ws_bytes, nullptr, (hipStream_t)stream);

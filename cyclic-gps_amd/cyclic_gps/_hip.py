@@ -222,8 +222,12 @@ def filter_adjoint_workspace(R, B, M, d, obs, dt, device):
     return _scratch(_ws_cache, nbytes, device), nbytes
 
 
-def pair_workspace(N, d, dt, device):
-    """The same for cgps_leg_mahal_logdet_pair: two fused pipelines, each rounded up to 256 bytes (tile_pair_ws in
+def pair_workspace_bytes(N, d, dt):
+    """What cgps_leg_mahal_logdet_pair asks for: two fused pipelines, each rounded up to 256 bytes (tile_pair_ws in
     csrc/cgps_plan.h is the layout run_tile_leg cuts up; include/cgps.h states the size)."""
-    nbytes = 2 * ((_workspace_bytes(int(N), int(d), dtype_code(dt), OP_MAHAL_LOGDET) + 255) // 256 * 256)
-    return _scratch(_pair_ws_cache, nbytes, device)
+    return 2 * ((_workspace_bytes(int(N), int(d), dtype_code(dt), OP_MAHAL_LOGDET) + 255) // 256 * 256)
+
+
+def pair_workspace(N, d, dt, device):
+    """A cached scratch tensor of at least pair_workspace_bytes(N, d, dt) bytes."""
+    return _scratch(_pair_ws_cache, pair_workspace_bytes(N, d, dt), device)

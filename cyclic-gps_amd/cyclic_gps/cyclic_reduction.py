@@ -57,12 +57,20 @@ def _device():
 
 
 def _stage(t, dtype=None):
-    """Contiguous GPU tensor for t (copying from the CPU when needed)."""
+    """Contiguous GPU tensor for t on a 16-byte boundary, which is what include/cgps.h asks of every array of blocks or
+    vectors (copying from the CPU when needed; a contiguous view that starts off the boundary, such as Rs[1:] of odd-sized
+    blocks, is copied to fresh memory, so that the Python surface keeps taking any view)."""
     if t.device.type != "cuda":
         t = t.to(_device())
     if dtype is not None and t.dtype != dtype:
         t = t.to(dtype)
-    return t.contiguous()
+    return _aligned16(t.contiguous())
+
+
+def _aligned16(t):
+    """t, or a copy of it when its first byte is not on a 16-byte boundary (a slice of odd-sized blocks at an odd row:
+    the kernels read blocks and vectors 16 bytes at a time, and the library refuses such a pointer)."""
+    return t.clone() if t.numel() and t.data_ptr() % 16 else t
 
 
 def _back(t, like):
@@ -462,12 +470,6 @@ def _batch_layout(Rs, Os, x, lengths):
     if not 1 <= d <= 8:
         raise ValueError("block size d=%d outside 1..8" % d)
     return _BatchLayout(dense, lens, int(d), Rs.dtype, (tuple(Rs.shape), tuple(Os.shape), None if x is None else tuple(x.shape)))
-
-
-def _aligned16(t):
-    """t, or a copy of it when its first byte is not on a 16-byte boundary (a slice of odd-sized blocks at an odd row:
-    the one-system kernels read such rows two at a time with 16-byte loads)."""
-    return t.clone() if t.numel() and t.data_ptr() % 16 else t
 
 
 def _capturing():

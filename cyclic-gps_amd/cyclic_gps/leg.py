@@ -123,8 +123,8 @@ class _PegPrecisionFn(torch.autograd.Function):
         if n < 2:
             return None, torch.zeros_like(G)
         tsd = ts.detach().to(G.dtype).contiguous()
-        gRs = torch.zeros(n, d, d, dtype=G.dtype, device=G.device) if gRs is None else gRs.to(G.dtype).contiguous()
-        gOs = torch.zeros(n - 1, d, d, dtype=G.dtype, device=G.device) if gOs is None else gOs.to(G.dtype).contiguous()
+        gRs = torch.zeros(n, d, d, dtype=G.dtype, device=G.device) if gRs is None else cr._aligned16(gRs.to(G.dtype).contiguous())
+        gOs = torch.zeros(n - 1, d, d, dtype=G.dtype, device=G.device) if gOs is None else cr._aligned16(gOs.to(G.dtype).contiguous())
         nb = (n - 1 + 63) // 64
         part = torch.empty(nb, d, d, dtype=G.dtype, device=G.device)
         want_ts = ctx.needs_input_grad[0]
@@ -332,14 +332,14 @@ def _leg_pair_raw(ts, G, source, term, rows, v):
     cgps_leg_mahal_logdet_pair), ROWS_TABLE (term [P, d, d], rows = pattern bytes [n]: cgps_leg_mahal_logdet_pair_obs) or
     ROWS_WEIGHTED (term = basis [Kb, d, d], rows = weights [n, Kb]: cgps_leg_mahal_logdet_pair_w)."""
     n, d, dt = ts.shape[0], G.shape[0], G.dtype
-    ws = _hip.pair_workspace(n, d, dt, G.device)
+    ws, ws_bytes = _hip.pair_workspace(n, d, dt, G.device), _hip.pair_workspace_bytes(n, d, dt)
     out = torch.empty(4, dtype=torch.float64, device=G.device)
     info = torch.zeros(2, dtype=torch.int32, device=G.device)
     lib = _hip.lib()
     fn = (lib.cgps_leg_mahal_logdet_pair, lib.cgps_leg_mahal_logdet_pair_obs, lib.cgps_leg_mahal_logdet_pair_w)[source]
     per_row = () if source == _hip.ROWS_PLAIN else (term.shape[0], _hip.ptr(rows))
     _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(term), *per_row, _hip.ptr(v), n, d, _hip.dtype_code(dt), _hip.ptr(ws),
-                  ws.numel(), _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
+                  ws_bytes, _hip.ptr(out), _hip.ptr(info), _hip.stream_ptr()))
     return out, info
 
 
@@ -580,8 +580,8 @@ def _peg_precision_adjoint_models(ts, G, cut, gRs, gOs, want_ts):
     gtau = torch.empty(lead + (R - 1,), dtype=G.dtype, device=G.device) if want_ts else None
     lib = _hip.lib()
     fn, count = (lib.cgps_peg_precision_adjoint_models, (R,) + lead) if lead else (lib.cgps_peg_precision_adjoint_seg, (R,))
-    _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), *count, d, _hip.dtype_code(G.dtype), _hip.ptr(gRs.contiguous()),
-                  _hip.ptr(gOs.contiguous()), _hip.ptr(part), _hip.ptr(gtau), _hip.stream_ptr()))
+    _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), *count, d, _hip.dtype_code(G.dtype), _hip.ptr(cr._aligned16(gRs.contiguous())),
+                  _hip.ptr(cr._aligned16(gOs.contiguous())), _hip.ptr(part), _hip.ptr(gtau), _hip.stream_ptr()))
     gts = None
     if want_ts:
         z = gtau.new_zeros(lead + (1,))
@@ -1613,6 +1613,7 @@ def _posterior_blocks_models(ts, G, cut, source, term, rows=None):
     K_Rs = torch.empty(n, d, d, dtype=G.dtype, device=G.device)
     Os = torch.empty(max(n - 1, 0), d, d, dtype=G.dtype, device=G.device)
     info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    term = cr._aligned16(term)                      # (an array of blocks: include/cgps.h wants it on a 16-byte boundary)
     _hip.check(fn(_hip.ptr(ts), _hip.ptr(G), _hip.ptr(cut), *count, d, _hip.dtype_code(G.dtype), source, _hip.ptr(term),
                   entries, _hip.ptr(rows), _hip.ptr(K_Rs), _hip.ptr(Os), _hip.ptr(info), _hip.stream_ptr()))
     return K_Rs, Os, info

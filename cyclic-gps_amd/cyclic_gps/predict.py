@@ -95,7 +95,7 @@ def _intercast_hip(G, ip_mean, Rs, Os, ts, target_ts):
     from . import _hip
     dt, dev = ip_mean.dtype, ip_mean.device
     n, d, p = ip_mean.shape[0], G.shape[0], target_ts.shape[0]
-    c = lambda t: t.detach().to(device=dev, dtype=dt).contiguous()   # noqa: E731
+    c = lambda t: leg.cr._aligned16(t.detach().to(device=dev, dtype=dt).contiguous())   # noqa: E731
     ts_, tt_, G_, mu_, Rs_, Os_ = c(ts), c(target_ts), c(G), c(ip_mean), c(Rs), c(Os)
     means = torch.empty(p, d, dtype=dt, device=dev)
     covs = torch.empty(p, d, d, dtype=dt, device=dev)
@@ -245,7 +245,7 @@ def _intercast_models_hip(G, ip_mean, Rs, Os, ts, plan, target_ts, tplan, means=
     from . import _hip
     dt, dev = ip_mean.dtype, ip_mean.device
     d, P, lead = G.shape[-1], tplan.P, tuple(G.shape[:-2])
-    c = lambda t: t.detach().to(device=dev, dtype=dt).contiguous()   # noqa: E731
+    c = lambda t: leg.cr._aligned16(t.detach().to(device=dev, dtype=dt).contiguous())   # noqa: E731
     ts_, tt_, G_, mu_, Rs_, Os_ = c(ts), c(target_ts), c(G), c(ip_mean), c(Rs), c(Os)
     if means is None:
         means = torch.empty(lead + (P, d), dtype=dt, device=dev)

@@ -54,6 +54,11 @@ class HipShardOps:
         self.info = torch.zeros(1, dtype=torch.int32, device=device)
 
     def shard_reduce(self, Rs, Os, x, O_left, send, rec_bytes):
+        # a sub-shard is a view Rs[lo:hi] of the rank's rows: off the 16-byte boundary the library asks for when lo and
+        # d are odd, and copied to fresh memory then (include/cgps.h, Conventions)
+        from . import cyclic_reduction as cr
+        Rs, Os, x = cr._aligned16(Rs), cr._aligned16(Os), cr._aligned16(x)
+        O_left = None if O_left is None else cr._aligned16(O_left)
         base = send.data_ptr()
         _hip.check(_hip.lib().cgps_shard_reduce(
             _hip.ptr(Rs), _hip.ptr(Os), _hip.ptr(x), _hip.ptr(O_left), self.n_loc, self.d,

@@ -10,6 +10,24 @@
  *   - All data pointers are DEVICE pointers (hipMalloc / torch CUDA tensors),
  *     C-contiguous, batch-major: Rs[N][d][d], Os[N-1][d][d], vectors [N][d].
  *     O_i is the LOWER off-diagonal block J[i+1][i].
+ *   - Alignment.  The kernels read and write blocks and vectors 16 bytes at a
+ *     time, so every ARRAY OF BLOCKS OR VECTORS of the factorisation, solve,
+ *     sampling, inverse, batch and sharding entry points (Rs, Os, x, y, xcrr,
+ *     Dp, Fp, Gp, Dk .. On, Sd, So, w, mean, O_left, records, record_out) and
+ *     every array of d x d blocks of the LEG assembly and prediction entry
+ *     points (Rs, Os, K_Rs, gRs, gOs, term, ip_cov_diag, ip_cov_offdiag,
+ *     out_cov) starts on a 16-byte boundary.  Every workspace starts on a
+ *     256-byte boundary (hipMalloc and torch give that).  An array or a
+ *     workspace off its boundary is CGPS_ERR_ARG, with the argument's name in
+ *     cgps_last_error(), before anything is launched.  Every other pointer
+ *     (time stamps, G, scalars, offsets, out2, info, patterns, weights ...)
+ *     must be aligned to its element size, as C asks of any pointer; the entry
+ *     points named above check that too, the element-wise LEG entry points
+ *     (log-likelihood forms, perturbation, observations, leave-one-out, the
+ *     filter and its adjoint, cgps_normal_fill) take it on trust.
+ *     Packed arrays of odd-sized blocks keep rows off the boundary inside the
+ *     array (row 1 of 3 x 3 doubles starts at byte 72): that is the kernels'
+ *     business; the rule is about the pointer handed in.
  *   - The library never allocates, frees or synchronises: the caller passes a
  *     scratch buffer of cgps_workspace_bytes() bytes, a HIP stream (hipStream_t
  *     as void*; NULL = default stream), and every call is asynchronous.
@@ -646,7 +664,8 @@ int cgps_leg_filter_adjoint(const void* xs, const uint8_t* pattern, const void* 
  * be 8-byte aligned).  P <= 1024 (256 for fp32 d = 8 and fp64 d = 7; 64 for fp64 d = 6 and d = 8).  Built for every block size
  * 1 <= d <= 8 in both precisions.  A rank may send several records (its rows cut into consecutive sub-shards,
  * each reduced by its own cgps_shard_reduce with O_left = the coupling to the previous sub-shard's last row):
- * cgps_finish_records simply takes all of them in row order. */
+ * cgps_finish_records simply takes all of them in row order.
+ * Workspace of cgps_shard_reduce: cgps_workspace_bytes(n_loc, d, dtype, CGPS_OP_MAHAL_LOGDET). */
 int cgps_record_elems(int d, int dtype, int64_t* elems);
 int cgps_shard_reduce(const void* Rs, const void* Os, const void* x, const void* O_left, int64_t n_loc, int d,
                       int dtype, void* ws, size_t ws_bytes, void* record_out, double* partial_out, void* stream);
