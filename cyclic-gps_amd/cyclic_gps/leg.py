@@ -2185,16 +2185,41 @@ def _filter_chunking(chunk_rows):
     return int(chunk_rows[0]), int(chunk_rows[1])
 
 
+# The time-parallel backward: what ``backward_chunk_rows="auto"`` stands for, and how the chunks'
+# transfer maps are measured -- d sequential probe calls of cgps_leg_filter_adjoint (False), or ONE call over d + 1 copies
+# of the models (True: copy 0 carries the real cotangents, copies 1..d the probes) at d + 1 times the memory of the saved
+# states and the cotangents.  Both MEASURED (tools/time_filter_grad_scan.py, one MI355X, fp64, rank 5): 128 rows is the
+# fastest L or within 7 % of it at 2^14, 2^17 and 2^20 rows (256 wins at 2^20), and the replicated call is the faster
+# at 2^20 rows (14.3 against 15.4 ms at obs_dim 1, 15.7 against 18.3 ms at obs_dim 3) and at every shorter length.
+FILTER_BACKWARD_CHUNK_ROWS = 128
+FILTER_LINK_REPLICATE = True
+
+
+def _filter_backward_chunking(backward_chunk_rows):
+    """``backward_chunk_rows`` of the filter calls as None (the serial reverse walk) or the rows per chunk L >= 1 of the
+    time-parallel backward: an int L or "auto"; ValueError for anything else."""
+    if backward_chunk_rows is None:
+        return None
+    if isinstance(backward_chunk_rows, str) and backward_chunk_rows == "auto":
+        return FILTER_BACKWARD_CHUNK_ROWS
+    if not (isinstance(backward_chunk_rows, int) and not isinstance(backward_chunk_rows, bool) and backward_chunk_rows >= 1):
+        raise ValueError('backward_chunk_rows must be None, "auto" or an int L >= 1 rows per chunk, got %r'
+                         % (backward_chunk_rows,))
+    return int(backward_chunk_rows)
+
+
 class _ChunkPlan:
     """The chunk layout of a batch for chunks of ``L`` rows (a subclass per L: ``_chunk_plan_kind``): ceil(n_b / L)
     chunks per series, restarting at every series' first row.  Device int64 tensors ``chunk_offsets`` [chunks + 1] (row
     offsets), ``chunk_series`` [chunks] and ``series_chunks`` [B + 1] (the first chunk of every series), planned on the
-    host from the lengths and cached like the batch plans (``_cached_batch_plan``)."""
+    host from the lengths and cached like the batch plans (``_cached_batch_plan``).  ``rounds``: ceil(log2(the most
+    chunks of one series - 1)), the doubling rounds of ``_filter_link_scan``."""
     L = None
 
     def __init__(self, lengths, device):
         lens = torch.as_tensor(list(lengths), dtype=torch.int64)
         per = (lens + (self.L - 1)) // self.L
+        self.rounds = max(int(per.max()) - 2, 0).bit_length() if len(lengths) else 0
         zero = torch.zeros(1, dtype=torch.int64)
         first = torch.cat([zero, torch.cumsum(per, 0)])
         rows = torch.cat([zero, torch.cumsum(lens, 0)])
@@ -2283,12 +2308,14 @@ def _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init, scan=Non
     return mean, cov, lp, zm, zc, loglik, m_end, P_end, info
 
 
-def _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, zc, m0, P0, cots):
+def _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, zc, m0, P0, cots, out=None):
     """cgps_leg_filter_adjoint: the data and operands of ``_filter_rows``, gap [R] (the time before every row; 0 at a first
     row without a start state), the saved z_mean / z_cov, the start states or None, and ``cots`` = the cotangents of
     (mean, cov, logpdf, z_mean, z_cov), each [M, R, ...] or None.  Returns (x_bar [M, R, obs], s_bar [M, R, obs], B_bar
     [M, B, obs, d], LLT_bar [M, B, obs, obs], m0_bar [M, B, d], P0_bar [M, B, d, d], G_bar partial sums [M, blocks, d, d],
-    gap_bar [M, R]).  Nothing is read on the host."""
+    gap_bar [M, R]).  ``out``: the eight of an earlier call with the same shapes, written again instead of fresh ones.
+    ``offsets`` may be a chunk plan's ``chunk_offsets`` with the chunks' start states: the entry then walks every chunk
+    as if it were a series.  Nothing is read on the host."""
     M, obs, d = Bm.shape
     R, B, dt, dev = xs.shape[0], offsets.shape[0] - 1, G.dtype, G.device
     c = lambda t: None if t is None else t.to(dt).contiguous()      # noqa: E731
@@ -2297,8 +2324,11 @@ def _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, z
         assert t is None or tuple(t.shape) == (M, R) + tail
     e = lambda *shape: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
     blocks = (R + 63) // 64
-    gx, gs, gB, gL, gm0, gP0, gG, gg = (e(M, R, obs), e(M, R, obs), e(M, B, obs, d), e(M, B, obs, obs), e(M, B, d),
-                                        e(M, B, d, d), e(M, blocks, d, d), e(M, R))
+    shapes = ((M, R, obs), (M, R, obs), (M, B, obs, d), (M, B, obs, obs), (M, B, d), (M, B, d, d), (M, blocks, d, d), (M, R))
+    if out is None:
+        out = tuple(e(*s) for s in shapes)
+    assert all(tuple(t.shape) == s and t.dtype == dt and t.is_contiguous() for t, s in zip(out, shapes))
+    gx, gs, gB, gL, gm0, gP0, gG, gg = out
     ws, nbytes = _hip.filter_adjoint_workspace(R, B, M, d, obs, dt, dev)
     xs, noise_var, G, Bm, LLT, gap, zm, zc, m0, P0 = (c(t) for t in (xs, noise_var, G, Bm, LLT, gap, zm, zc, m0, P0))
     _hip.check(_hip.lib().cgps_leg_filter_adjoint(
@@ -2309,27 +2339,174 @@ def _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, z
     return gx, gs, gB, gL, gm0, gP0, gG, gg
 
 
+# ---- the time-parallel backward --------------------------------------------------------------------------
+# The reverse recursion is affine in the cotangent it receives.  Chunk c maps what its last row receives, (mb, Db), to
+# what it hands the chunk before it:
+#     mb_in = PhiT_c mb + cm_c ;    Db_in = PhiT_c Db PhiT_c^T + sum_j mb_j T_c[j] + cD_c          (T_c[j] symmetric)
+# Db never feeds mb, Db -> Db is the congruence with the matrix that carries mb, and mb -> Db is linear.  Two chunks, 1
+# the earlier rows, 2 the later ones (2 is applied first), compose to
+#     PhiT_12 = PhiT_1 PhiT_2 ;    T_12[j] = PhiT_1 T_2[j] PhiT_1^T + sum_i (PhiT_2)_ij T_1[i]
+#     cm_12 = PhiT_1 cm_2 + cm_1 ;    cD_12 = PhiT_1 cD_2 PhiT_1^T + sum_i (cm_2)_i T_1[i] + cD_1
+def _filter_link_scan(PhiT, T, cm, cD, series_chunks, rounds=None):
+    """What every chunk's last row receives from the later chunks of its series: (mb [M, C, d], Db [M, C, d, d]), the affine
+    part of the composite of chunks c + 1 .. the series' last (zero for a series' last chunk).  ``PhiT`` [M, C, d, d],
+    ``T`` [M, C, d, d, d] (T[m, c, j] symmetric), ``cm`` [M, C, d], ``cD`` [M, C, d, d]: the chunks' maps in the notation
+    above; ``series_chunks`` int64 [B + 1]: the first chunk of every series.  A segmented suffix scan over the chunk axis
+    by doubling: ``rounds`` rounds (None: ceil(log2(C - 1)), enough for any layout; a chunk receives at most the composite
+    of the n - 1 chunks after it, n the most chunks of a series, and the caller that knows n passes ceil(log2(n - 1))).
+    A composition across a series' boundary is never SELECTED, so nothing -- a failed series' NaN included -- passes from
+    one series into another.  Pure torch on any device; nothing is read on the host."""
+    M, C, d = cm.shape
+    dev = cm.device
+    if C == 0:
+        return cm.clone(), cD.clone()
+    B = series_chunks.shape[0] - 1
+    per = series_chunks[1:] - series_chunks[:-1]
+    ser = torch.repeat_interleave(torch.arange(B, device=dev), per, output_size=C)
+    end = series_chunks[1:][ser]                                   # one past the last chunk of the chunk's series
+    idx = torch.arange(C, device=dev)
+    if rounds is None:
+        rounds = max(C - 2, 0).bit_length()
+
+    def later(step):
+        nxt = idx + step
+        return nxt < end, nxt.clamp_max(C - 1)
+
+    def select(ok, new, old):
+        return torch.where(ok.reshape((1, C) + (1,) * (old.dim() - 2)), new, old)
+
+    step = 1
+    for r in range(rounds):                                        # element c: the composite of c .. c + step - 1
+        ok, j = later(step)
+        Phi = PhiT.transpose(-1, -2)
+        m2, D2 = cm[:, j], cD[:, j]
+        new_m = (PhiT @ m2.unsqueeze(-1)).squeeze(-1) + cm
+        new_D = PhiT @ D2 @ Phi + torch.einsum("mci,mciab->mcab", m2, T) + cD
+        if r + 1 < rounds:                                         # (the last round's maps are used by nobody)
+            P2, T2 = PhiT[:, j], T[:, j]
+            new_T = PhiT.unsqueeze(2) @ T2 @ Phi.unsqueeze(2) + torch.einsum("mcij,mciab->mcjab", P2, T)
+            PhiT, T = select(ok, PhiT @ P2, PhiT), select(ok, new_T, T)
+        cm, cD = select(ok, new_m, cm), select(ok, new_D, cD)
+        step *= 2
+    ok, j = later(1)
+    return select(ok, cm[:, j], torch.zeros_like(cm)), select(ok, cD[:, j], torch.zeros_like(cD))
+
+
+def _filter_chunk_maps(run, M, R, d, dt, dev, last, cots, replicate):
+    """The maps of ``_filter_link_scan`` for every (model, chunk), measured by cgps_leg_filter_adjoint itself: (PhiT, T,
+    cm, cD, the eight output buffers to use again or None).  ``run(cots, out, copies)`` is the entry over the chunk view
+    (``copies`` > 1: over that many copies of the models along the model axis), ``last`` the chunks' last rows.  (cm, cD)
+    are the start-state adjoints under the real cotangents with nothing received; column j of PhiT and T[j] those under
+    no cotangent but e_j on z_mean of every chunk's last row.  ``replicate``: one call over d + 1 copies of the models
+    instead of d + 1 calls."""
+    if not replicate:
+        bufs = run(cots, None, 1)
+        C = bufs[4].shape[1]
+        cm, cD = bufs[4].clone(), bufs[5].clone()
+        PhiT = torch.empty(M, C, d, d, dtype=dt, device=dev)
+        T = torch.empty(M, C, d, d, d, dtype=dt, device=dev)
+        probe = torch.zeros(M, R, d, dtype=dt, device=dev)
+        for j in range(d):
+            if j:
+                probe[:, last, j - 1] = 0
+            probe[:, last, j] = 1
+            run([None, None, None, probe, None], bufs, 1)
+            PhiT[..., j] = bufs[4]
+            T[:, :, j] = bufs[5]
+        return PhiT, T, cm, cD, bufs
+    K = d + 1
+    big = []
+    for j, t in enumerate(cots):
+        if t is None and j != 3:
+            big.append(None)
+            continue
+        tail = (d,) if j == 3 else tuple(t.shape[2:])
+        full = torch.zeros((K, M, R) + tail, dtype=dt, device=dev)
+        if t is not None:
+            full[0] = t
+        big.append(full)
+    for j in range(d):
+        big[3][j + 1, :, last, j] = 1
+    out = run([None if t is None else t.reshape((K * M,) + tuple(t.shape[2:])) for t in big], None, K)
+    C = out[4].shape[1]
+    gm0, gP0 = out[4].reshape(K, M, C, d), out[5].reshape(K, M, C, d, d)
+    return gm0[1:].permute(1, 2, 3, 0), gP0[1:].permute(1, 2, 0, 3, 4), gm0[0], gP0[0], None
+
+
+def _filter_chunk_states(chunks, zm, zc, m0, P0):
+    """The chunk view of a batch: (the start state of every chunk -- mean [M, C, d] and cov [M, C, d, d]: the saved
+    filtered state of the row before it, for a series' first chunk its (m0, P0), or (0, I) when there is none --, the
+    chunks' last rows [C])."""
+    M, R, d = zm.shape
+    dt, dev, C = zm.dtype, zm.device, chunks.chunks
+    coff, cser, first = chunks.chunk_offsets, chunks.chunk_series, chunks.series_chunks
+    head = (torch.arange(C, device=dev) == first[:-1][cser]).reshape(1, C, 1)      # a series' first chunk
+    prev = (coff[:-1] - 1).clamp_min(0)
+    if m0 is not None:
+        sm, sP = m0.to(dt)[:, cser], P0.to(dt)[:, cser]
+    else:
+        sm, sP = torch.zeros(1, 1, d, dtype=dt, device=dev), torch.eye(d, dtype=dt, device=dev).reshape(1, 1, d, d)
+    return (torch.where(head, sm, zm[:, prev]).contiguous(), torch.where(head.unsqueeze(-1), sP, zc[:, prev]).contiguous(),
+            coff[1:] - 1)
+
+
+def _filter_adjoint_linked(xs, pattern, noise_var, G, Bm, LLT, gap, zm, zc, m0, P0, cots, chunks, replicate=None):
+    """``_filter_adjoint_rows`` of the batch, parallel in time: the entry runs over the chunks of
+    ``chunks`` (a ``_ChunkPlan`` of the batch) as if they were series -- ``_filter_chunk_states`` --, d + 1 times to
+    measure every chunk's map, a scan over arrays with one element per chunk links them, and a last call with what every
+    chunk receives on its last row gives the result.  Returns the eight of ``_filter_adjoint_rows`` with B_bar and LLT_bar
+    per (model, CHUNK) and m0_bar, P0_bar per (model, series): those of the series' first chunk."""
+    M, obs, d = Bm.shape
+    R, dt, dev, C = xs.shape[0], G.dtype, G.device, chunks.chunks
+    replicate = FILTER_LINK_REPLICATE if replicate is None else replicate
+    coff, first = chunks.chunk_offsets, chunks.series_chunks
+    B = first.shape[0] - 1
+    cm0, cP0, last = _filter_chunk_states(chunks, zm, zc, m0, P0)
+    cots = [None if t is None else t.to(dt) for t in cots]
+
+    def run(cots_, out, copies):
+        rep = lambda t: t if copies == 1 else t.repeat((copies,) + (1,) * (t.dim() - 1))      # noqa: E731
+        return _filter_adjoint_rows(xs, pattern, noise_var, coff, rep(G), rep(Bm), rep(LLT), gap, rep(zm), rep(zc), rep(cm0),
+                                    rep(cP0), cots_, out)
+
+    PhiT, T, cm, cD, bufs = _filter_chunk_maps(run, M, R, d, dt, dev, last, cots, replicate)
+    wide = lambda t: t.to(torch.float64)      # noqa: E731
+    rm, rD = _filter_link_scan(wide(PhiT), wide(T), wide(cm), wide(cD), first, chunks.rounds)
+    g_zm = torch.zeros(M, R, d, dtype=dt, device=dev) if cots[3] is None else cots[3].clone()
+    g_zc = torch.zeros(M, R, d, d, dtype=dt, device=dev) if cots[4] is None else cots[4].clone()
+    g_zm.index_add_(1, last, rm.to(dt))
+    g_zc.index_add_(1, last, rD.to(dt))
+    gx, gs, gB, gL, gm0, gP0, gG, gg = run(cots[:3] + [g_zm, g_zc], bufs, 1)
+    has_rows = (first[1:] > first[:-1]).reshape(1, B, 1)
+    at = first[:-1].clamp_max(C - 1)
+    gm0 = torch.where(has_rows, gm0[:, at], torch.zeros((), dtype=dt, device=dev))
+    gP0 = torch.where(has_rows.unsqueeze(-1), gP0[:, at], torch.zeros((), dtype=dt, device=dev))
+    return gx, gs, gB, gL, gm0, gP0, gG, gg
+
+
 class _FilterFn(torch.autograd.Function):
     """``_filter_rows`` with a backward: the forward is the same launch (serial or time-parallel) and
     keeps z_mean and z_cov; the backward is ONE cgps_leg_filter_adjoint -- gaps, the serial reverse walk, the Frechet pass
-    -- and a few torch sums.  Inputs: G [M, d, d], Bm [M, obs, d], LLT [M, obs, obs], ts [R], xs [R, obs], noise_var
-    [R, obs] or None, t0 [B], m0 [M, B, d], P0 [M, B, d, d] or three None; ``pattern``, ``offsets`` and ``scan`` carry no
-    gradient.  Outputs: the nine of ``_filter_rows``; info is not differentiable."""
+    -- and a few torch sums, or with ``bchunks`` (a ``_ChunkPlan`` of the batch in which a series has more than one chunk)
+    ``_filter_adjoint_linked``, the same entry over chunks.  Inputs: G [M, d, d], Bm [M, obs, d], LLT
+    [M, obs, obs], ts [R], xs [R, obs], noise_var [R, obs] or None, t0 [B], m0 [M, B, d], P0 [M, B, d, d] or three None;
+    ``pattern``, ``offsets``, ``scan`` and ``bchunks`` carry no gradient.  Outputs: the nine of ``_filter_rows``; info is
+    not differentiable."""
 
     @staticmethod
-    def forward(ctx, G, Bm, LLT, ts, xs, noise_var, t0, m0, P0, pattern, offsets, scan):
+    def forward(ctx, G, Bm, LLT, ts, xs, noise_var, t0, m0, P0, pattern, offsets, scan, bchunks=None):
         ctx.set_materialize_grads(False)
         init = None if t0 is None else (t0, m0, P0)
         out = _filter_rows(ts, xs, pattern, noise_var, offsets, G, Bm, LLT, init, scan)
         ctx.save_for_backward(G, Bm, LLT, ts, xs, noise_var, t0, m0, P0, out[3], out[4])
-        ctx.data = (pattern, offsets)
+        ctx.data = (pattern, offsets, bchunks)
         ctx.mark_non_differentiable(out[8])
         return out
 
     @staticmethod
     def backward(ctx, g_mean, g_cov, g_lp, g_zm, g_zc, g_ll, g_mend, g_Pend, _g_info):
         G, Bm, LLT, ts, xs, noise_var, t0, m0, P0, zm, zc = ctx.saved_tensors
-        pattern, offsets = ctx.data
+        pattern, offsets, bchunks = ctx.data
         M, obs, d = Bm.shape
         R, B, dt, dev = xs.shape[0], offsets.shape[0] - 1, G.dtype, G.device
         lens = offsets[1:] - offsets[:-1]
@@ -2352,8 +2529,17 @@ class _FilterFn(torch.autograd.Function):
                 direct[j] = g_end.to(dt) * ~keep
         gap = ts - torch.roll(ts, 1)
         gap = torch.where(is_first, (ts - t0[sid]) if t0 is not None else torch.zeros_like(ts), gap)
-        gx, gs, gB, gL, gm0, gP0, gG, gg = _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, zc, m0,
-                                                              P0, [g_mean, g_cov, g_lp] + cots)
+        if bchunks is None:
+            gx, gs, gB, gL, gm0, gP0, gG, gg = _filter_adjoint_rows(xs, pattern, noise_var, offsets, G, Bm, LLT, gap, zm, zc,
+                                                                  m0, P0, [g_mean, g_cov, g_lp] + cots)
+        else:
+            gx, gs, gB, gL, gm0, gP0, gG, gg = _filter_adjoint_linked(xs, pattern, noise_var, G, Bm, LLT, gap, zm, zc, m0, P0,
+                                                                    [g_mean, g_cov, g_lp] + cots, bchunks)
+            # a failed (model, series): NaN in ALL its entries of x_bar and s_bar, as the serial walk stores them (the
+            # linked one leaves the exact zeros of its unobserved entries)
+            failed = ~torch.isfinite(zm[:, last].sum(-1) + zc[:, last].sum((-1, -2))) & has_rows
+            nan = torch.full((), float("nan"), dtype=dt, device=dev)
+            gx, gs = (torch.where(failed[:, sid].unsqueeze(-1), nan, t) for t in (gx, gs))
         gg = gg.sum(0)
         inner = torch.where(is_first, torch.zeros_like(gg), gg)      # gap i = ts[i] - ts[i - 1]
         g_ts = inner - torch.cat([inner[1:], inner.new_zeros(1)])
@@ -2367,7 +2553,7 @@ class _FilterFn(torch.autograd.Function):
         else:
             gm0 = gP0 = None
         return (gG.sum(1), gB.sum(1), gL.sum(1), g_ts, gx.sum(0), gs.sum(0) if noise_var is not None else None, g_t0, gm0,
-                gP0, None, None, None)
+                gP0, None, None, None, None)
 
 
 def _filter_empty(lead, obs, d, dt, device):
@@ -2376,12 +2562,15 @@ def _filter_empty(lead, obs, d, dt, device):
     return e(obs), e(obs, obs), e(), e(d), e(d, d)
 
 
-def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chunking=None, differentiable=False):
+def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chunking=None, differentiable=False,
+                   backward_rows=None):
     """The filter of the stacked models ``mats`` over a validated, non-empty batch: (the eight tensors of
     ``_filter_rows``, the times of the series' last rows [B]).  ``init`` has the models' axis.  ``named``: whether a
     failure's message names the model.  ``chunking``: None or the (L, F) of ``_filter_chunking``.  ``differentiable``:
     under grad mode and with an input that requires grad, the launch goes through ``_FilterFn`` and the results carry
-    a graph (the caller must not be under ``torch.no_grad``)."""
+    a graph (the caller must not be under ``torch.no_grad``).  ``backward_rows``: None or the L of
+    ``_filter_backward_chunking``; the backward of that graph is then parallel in time wherever a series has more than one
+    chunk of L rows."""
     Nm, Rm, Bm, Lm = mats
     M, obs, d, dt = Nm.shape[0], Bm.shape[1], Nm.shape[1], Nm.dtype
     if obs > MAX_PATTERN_OBS:
@@ -2401,7 +2590,10 @@ def _filter_models(mats, ts, xs, lengths, observed, noise_var, init, named, chun
     t0, m0, P0 = init if init is not None else (None, None, None)
     inputs = (G, Bm.contiguous(), LLT, ts_c, xs_c, nv, t0, m0, P0)
     if differentiable and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in inputs):
-        out = _FilterFn.apply(*inputs, pattern, plan.offsets, scan)
+        bchunks = None
+        if backward_rows is not None and max(lengths) > backward_rows:
+            bchunks = _cached_batch_plan(lengths, Nm.device, _chunk_plan_kind(backward_rows))
+        out = _FilterFn.apply(*inputs, pattern, plan.offsets, scan, bchunks)
     else:
         with torch.no_grad():
             out = _filter_rows(ts_c, xs_c, pattern, nv, plan.offsets, G, Bm.contiguous(), LLT, init, scan)
@@ -2423,7 +2615,8 @@ def _stack1(m):
     return tuple(t.unsqueeze(0) for t in (m.N, m.R, m.B, m.Lambda))
 
 
-def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk_rows=None, differentiable=False):
+def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk_rows=None, differentiable=False,
+                      backward_chunk_rows=None):
     """One-step-ahead predictives and filtered states of one series: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
     loglik, state)``.
 
@@ -2455,14 +2648,26 @@ def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk
     with gradients in the model's N, R, B, Lambda and in ``ts``, ``xs``, ``noise_var``, ``init.t``, ``init.mean``,
     ``init.cov`` (a mask has none; the gradient in xs and noise_var is exactly 0 at unobserved entries).  The backward
     is one cgps_leg_filter_adjoint: a reverse walk of the rows, one lane per series, from the saved
-    ``z_mean`` / ``z_cov``.  With ``chunk_rows=`` the forward is the scan and the backward is still that SERIAL walk:
-    the backward of one long series is one lane's chain (a time-parallel backward is not built).  No second derivatives.
+    ``z_mean`` / ``z_cov``.  ``backward_chunk_rows=None`` (the default): that walk is SERIAL whatever ``chunk_rows`` is --
+    the backward of one long series is one lane's chain.  ``backward_chunk_rows=`` an int L >= 1 or "auto"
+    (``FILTER_BACKWARD_CHUNK_ROWS`` = 128, chosen from the measurement below): the backward is TIME-PARALLEL (DESIGN.md
+    4.25), independent of ``chunk_rows`` since it needs only the saved states -- the same entry walks chunks of L rows as if they were series,
+    once over d + 1 copies of the model to measure every chunk's affine map of the cotangent it receives (d + 1 times the
+    memory of the saved states; ``FILTER_LINK_REPLICATE = False``: d + 1 calls instead), a scan over arrays with one
+    element per chunk links the chunks of a series, and one more call gives the gradients: chains of about 2 L steps
+    ((d + 2) L with the sequential calls) and ceil(log2(n / L)) scan rounds instead of n.  Same gradients to rounding
+    (fp64: rtol 1e-7 / atol 1e-10 against autograd of the recursion; fp32: at most 4x the error of the serial backward);
+    a series that fits one chunk: the serial call, bit for bit.  Forward + backward of ``loglik.sum()``, one series, rank 5, fp64, obs_dim 1 on one MI355X with
+    ``chunk_rows="auto"``: 2^20 rows 2.85 s with the serial backward (timed once), 14.3 ms with "auto" (13.5 ms with 256);
+    2^17 rows 398 ms and 5.0 ms; 2^14 rows 45.3 ms and 4.3 ms.  Anything else is a ValueError; without
+    ``differentiable=True`` or with nothing that requires grad it is checked and ignored.  No second derivatives.
     Ranks 1..8, obs_dim <= 8, both precisions.  With
     ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming it; with the
     check off that row, all later rows and ``loglik`` are NaN.  CPU tensors behave as ``insample_posterior`` does (there
     is no CPU implementation)."""
     with _filter_grad_mode(differentiable):
         chunking = _filter_chunking(chunk_rows)
+        backward_rows = _filter_backward_chunking(backward_chunk_rows)
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
         observed = _single_series_args(obs, ts, xs, observed, noise_var)
         n = ts.shape[0]
@@ -2473,12 +2678,13 @@ def filter_predictive(m, ts, xs, observed=None, noise_var=None, init=None, chunk
             state = FilterState(*(t.reshape(s).to(dt) for t, s in zip(init, ((), (d,), (d, d))))) if init is not None else None
             return FilterPredictive(*_filter_empty((0,), obs, d, dt, ts.device),
                                     torch.zeros((), dtype=torch.float64, device=ts.device), state)
-        out, t_end = _filter_models(_stack1(m), ts, xs, [n], observed, noise_var, init, False, chunking, differentiable)
+        out, t_end = _filter_models(_stack1(m), ts, xs, [n], observed, noise_var, init, False, chunking, differentiable,
+                                     backward_rows)
         return FilterPredictive(*(t[0] for t in out[:5]), out[5][0, 0], FilterState(t_end[0], out[6][0, 0], out[7][0, 0]))
 
 
 def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None,
-                            differentiable=False):
+                            differentiable=False, backward_chunk_rows=None):
     """``filter_predictive`` of B independent series in one call: ``FilterPredictive(mean, cov, logpdf, z_mean, z_cov,
     loglik, state)`` with ``loglik`` [B] (fp64) and ``state = FilterState(t [B], mean [B, d], cov [B, d, d])``.
 
@@ -2505,7 +2711,13 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
 
     ``differentiable=``: as in ``filter_predictive`` -- False (the default) is inference only under ``torch.no_grad``;
     True builds the graph for every result but ``state.t``, and the backward is one serial reverse walk per series
-    (cgps_leg_filter_adjoint, one lane per series; with ``chunk_rows=`` too).  ``loglik.sum().backward()`` gives the
+    (cgps_leg_filter_adjoint, one lane per series; with ``chunk_rows=`` too) unless ``backward_chunk_rows=`` (an int L
+    or "auto") makes it parallel in time as in ``filter_predictive``: chunks of L rows that never straddle a series, a
+    series' first chunk starting from its ``init``, nothing passing from one series into the next, a failed one's NaN
+    included.  When to pass it (one MI355X, fp64, rank 5, series of 502 rows, forward + backward of
+    ``loglik.sum()``): at 64 series 64 rows per chunk measured 3.24 ms against 3.42 ms serial at obs_dim 1 -- level in
+    a second run -- (3.81 against 5.06 ms at obs_dim 3) and "auto" 3.46 ms (4.55 ms); at 1 024 series the serial walk
+    WINS, 4.17 ms against 6.40 ms (6.11 against 7.60 ms) -- leave it None for wide batches of short series.  ``loglik.sum().backward()`` gives the
     gradients of ``log_likelihood_batch`` without the smoother's factorisation; per-row weights on ``logpdf``, losses on
     ``mean`` or ``z_mean`` and the gradient into ``init`` come from nowhere else.
 
@@ -2516,6 +2728,7 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
     (there is no CPU implementation)."""
     with _filter_grad_mode(differentiable):
         chunking = _filter_chunking(chunk_rows)
+        backward_rows = _filter_backward_chunking(backward_chunk_rows)
         ts, xs, lengths, observed, noise_var, dense, bn = _batch_args(m.B.shape[0], ts, xs, lengths, observed, noise_var)
         obs, d, dt = m.B.shape[0], m.N.shape[0], m.N.dtype
         if init is not None:
@@ -2530,7 +2743,8 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
             state = FilterState(init[0], init[1][0], init[2][0]) if init is not None else None
             return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
                                     torch.empty(0, dtype=torch.float64, device=ts.device), state)
-        out, t_end = _filter_models(_stack1(m), ts, xs, lengths, observed, noise_var, init, False, chunking, differentiable)
+        out, t_end = _filter_models(_stack1(m), ts, xs, lengths, observed, noise_var, init, False, chunking, differentiable,
+                                     backward_rows)
         rows = [t[0] for t in out[:5]]
         if dense:
             rows = [t.reshape(bn + tuple(t.shape[1:])) for t in rows]
@@ -2538,7 +2752,7 @@ def filter_predictive_batch(m, ts, xs, lengths=None, observed=None, noise_var=No
 
 
 def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=None, init=None, chunk_rows=None,
-                             differentiable=False):
+                             differentiable=False, backward_chunk_rows=None):
     """``filter_predictive_batch`` of M LEG models for the same B series in one call: slot k of every result is
     ``filter_predictive_batch(ms[k], ...)``, bit for bit; ``loglik`` is [M, B] (fp64) and ``state =
     FilterState(t [B], mean [M, B, d], cov [M, B, d, d])``.  ``logpdf`` [M, ...] holds the terms from which the running
@@ -2556,7 +2770,9 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
     (cgps_leg_filter_scan); slot k is still the call on ``ms[k]`` with the same ``chunk_rows``, bit for
     bit.  When to pass it: as for ``filter_predictive_batch`` (timed with one model only).  ``differentiable=``: as in
     ``filter_predictive_batch``, with gradients in every model's four matrices; the gradients in ``ts``, ``xs``,
-    ``noise_var`` and ``init.t``, which the models share, are summed over the models.
+    ``noise_var`` and ``init.t``, which the models share, are summed over the models.  ``backward_chunk_rows=``: the
+    time-parallel backward of ``filter_predictive_batch`` with one chunk map per (model, chunk); None (the default) is the
+    serial walk.
 
     Failures: with ``cr.CHECK_POSITIVE_DEFINITE`` a row whose predictive does not exist raises ``cr.NotPSDError`` naming
     the model, the series and its local row; with the check off that row and the later rows of that series under THAT
@@ -2564,6 +2780,7 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
     as ``filter_predictive_batch`` does (there is no CPU implementation)."""
     with _filter_grad_mode(differentiable):
         chunking = _filter_chunking(chunk_rows)
+        backward_rows = _filter_backward_chunking(backward_chunk_rows)
         ms, mats, ts, xs, lengths, observed, noise_var, dense, bn = _models_posterior_args(ms, ts, xs, lengths, observed,
                                                                                           noise_var)
         M, obs, d, dt = len(ms), mats[2].shape[1], mats[0].shape[1], mats[0].dtype
@@ -2576,7 +2793,8 @@ def filter_predictive_models(ms, ts, xs, lengths=None, observed=None, noise_var=
             return FilterPredictive(*_filter_empty(lead, obs, d, dt, ts.device),
                                     torch.empty(M, 0, dtype=torch.float64, device=ts.device),
                                     FilterState(*init) if init is not None else None)
-        out, t_end = _filter_models(mats, ts, xs, lengths, observed, noise_var, init, True, chunking, differentiable)
+        out, t_end = _filter_models(mats, ts, xs, lengths, observed, noise_var, init, True, chunking, differentiable,
+                                     backward_rows)
         rows = list(out[:5])
         if dense:
             rows = [t.reshape((M,) + bn + tuple(t.shape[2:])) for t in rows]

@@ -632,6 +632,9 @@ int cgps_leg_filter_scan(const void* ts, const void* xs, const uint8_t* pattern,
  *   g_gap[M][R]                               the gradient in gap, which the caller scatters to ts and t0.
  * A (model, series) whose forward failed (NaN in its last z_mean, z_cov) gets NaN in its rows of g_xs, g_noise_var
  * and g_gap, in its g_Bmat, g_LLT, g_m0, g_P0 and so in its model's g_G_partial; other series are untouched.
+ * The entry is also called over CHUNKS of the series as if they were series (the time-parallel backward):
+ * row_offsets = the chunks' offsets, B = their number, m0 / P0 = the saved state of the row before every chunk, gap
+ * unchanged; g_m0, g_P0 are then the adjoints of those saved states and the caller links the chunks of a series.
  * ws / ws_bytes: caller-owned device memory of at least cgps_leg_filter_adjoint_workspace_bytes(R, B, M, d, obs, dtype)
  * bytes.  CGPS_ERR_ARG, before anything is launched: a null required pointer, one of m0, P0 without the other, B < 0,
  * R < 0, M outside 1..65535, d or obs outside 1..8, a workspace that is too small; an unknown dtype:
