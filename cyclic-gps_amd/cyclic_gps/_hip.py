@@ -1,4 +1,4 @@
-"""ctypes binding of libcgps.so (C ABI: include/cgps.h).
+"""ctypes binding of libcgps.so (C ABI: include/cgps.h, and include/cgps_glm.h for the extension entry points).
 
 The library is the product: if it is missing this module raises, it never falls
 back to a CPU or torch implementation.
@@ -88,6 +88,14 @@ _SIGNATURES = {
     "cgps_finish_records": (_int, [_vp, _sz, _vp, _sz, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
 }
 
+# Entry points declared in include/cgps_glm.h: the same library, a table of their own
+_EXTENSION_SIGNATURES = {
+    "cgps_leg_glm_step": (_int, [_vp] * 10 + [_i64] * 2 + [_int] * 4 + [ctypes.c_double] + [_vp] * 6),
+}
+GLM_POISSON, GLM_BERNOULLI, GLM_GAUSSIAN = range(3)
+GLM_CONVERGED, GLM_STALLED = 1, 2
+GLM_STATE = 4
+
 
 class CgpsError(RuntimeError):
     pass
@@ -95,6 +103,11 @@ class CgpsError(RuntimeError):
 
 def exported_symbols():
     return sorted(_SIGNATURES)
+
+
+def extension_symbols():
+    """the entry points of include/cgps_glm.h"""
+    return sorted(_EXTENSION_SIGNATURES)
 
 
 def lib():
@@ -112,7 +125,7 @@ def lib():
         if os.path.exists(rt):
             ctypes.CDLL(rt, mode=ctypes.RTLD_GLOBAL)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_EXTENSION_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

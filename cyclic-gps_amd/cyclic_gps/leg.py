@@ -3325,6 +3325,290 @@ def sample_observations_models(ms, z, seed, lengths=None, observed=None, noise_v
                                   _model_stream_words(len(ms), stream, model_streams), True)
 
 
+# ---- observations that are not Gaussian: the Laplace approximation ----------------------------------
+LaplacePosterior = collections.namedtuple("LaplacePosterior", ["mean", "cov", "log_evidence", "iterations", "converged"])
+
+_FAMILIES = {"poisson": _hip.GLM_POISSON, "bernoulli": _hip.GLM_BERNOULLI, "gaussian": _hip.GLM_GAUSSIAN}
+GLM_CANDIDATES = 12
+"""Step lengths 1, 1/2, .., 2^-11 of the damped Newton step (cgps_leg_glm_step tries the same)."""
+LAPLACE_TOL = {torch.float64: 1e-16, torch.float32: 1e-9}
+"""``tol=None``: a series has converged once a step's gain is <= tol (1 + |psi|).  The gain of a Newton step is about
+half its squared length in the metric of J, and the point it lands on is within about that squared length of the
+mode: these leave the mode at rounding level in either precision.  They are also well above what rounding does to
+the gain itself, about eps^2 |z|^2 |J| cond(J) (the step is then noise, and so is its gain): a smaller tolerance
+would be met by chance or not at all."""
+_LOG_EXPOSURE = ("log_exposure", "a floating-point tensor", lambda dtype: dtype.is_floating_point)
+
+
+class _GlmOperands:
+    """What every step of one call reads, contiguous and of the model's dtype: the prior blocks (written once), the
+    data, the pattern bytes (None: everything observed), offset and extra (None: zeros), B, the plan."""
+
+    def __init__(self, plan, Rs, Os, ys, observed, offset, extra, Bm, family, tol):
+        self.plan, self.Rs, self.Os, self.ys, self.observed = plan, Rs, Os, ys, observed
+        self.offset, self.extra, self.Bm, self.family, self.tol = offset, extra, Bm, family, float(tol)
+        obs = ys.shape[1]
+        self.pattern = None
+        if observed is not None:
+            self.pattern = (observed * (1 << torch.arange(obs, device=observed.device))).sum(1).to(torch.uint8).contiguous()
+
+
+def _glm_step_hip(op, z, prop, state):
+    """One launch of cgps_leg_glm_step: (z_out, J_Rs, rhs, state_out)."""
+    R, d = z.shape
+    dt, dev = z.dtype, z.device
+    z_out = torch.empty(R, d, dtype=dt, device=dev)
+    J_Rs = torch.empty(R, d, d, dtype=dt, device=dev)
+    rhs = torch.empty(R, d, dtype=dt, device=dev)
+    state_out = torch.empty(op.plan.B, _hip.GLM_STATE, dtype=torch.float64, device=dev)
+    P = _hip.ptr
+    _hip.check(_hip.lib().cgps_leg_glm_step(
+        P(z), P(prop), P(op.Rs), P(op.Os), P(op.ys), P(op.pattern), P(op.offset), P(op.extra), P(op.Bm), P(op.plan.offsets),
+        op.plan.B, R, d, op.ys.shape[1], _hip.dtype_code(dt), op.family, op.tol, P(state), P(z_out), P(J_Rs), P(rhs),
+        P(state_out), _hip.stream_ptr()))
+    return z_out, J_Rs, rhs, state_out
+
+
+def _glm_point(family, y, eta, s):
+    """(log density, its derivative g, the weight w = -l'', the factor of ``_glm_diff``) at the linear predictor eta"""
+    if family == _hip.GLM_POISSON:
+        e = torch.exp(eta)
+        return y * eta - e, y - e, e, e
+    if family == _hip.GLM_BERNOULLI:
+        e = torch.exp(-eta.abs())
+        r = 1.0 / (1.0 + e)
+        sig = torch.where(eta >= 0, r, e * r)
+        return y * eta - (eta.clamp(min=0) + torch.log1p(e)), y - sig, e * r * r, sig
+    inv, res = 1.0 / s, y - eta
+    return -0.5 * res * res * inv - 0.5 * torch.log(2 * math.pi * s), res * inv, inv, inv
+
+
+def _glm_diff(family, y, g, base, t):
+    """l(eta + t) - l(eta) with nothing of the size of l cancelling"""
+    if family == _hip.GLM_POISSON:
+        return y * t - base * torch.expm1(t)
+    if family == _hip.GLM_BERNOULLI:
+        return y * t - torch.log1p(base * torch.expm1(t))
+    return t * (g - 0.5 * t * base)
+
+
+def _glm_step_composed(op, z, prop, state):
+    """The step of cgps_leg_glm_step as torch passes over [R, obs] and [R, d, d] arrays (CGPS_LEG_GLM_COMPOSED=1): the same
+    arithmetic in the arrays' dtype, the sums per series in fp64 (``index_add_``: not in a fixed order).  For A/B timing,
+    and the yardstick of the kernel's fp32 error."""
+    plan, fam, dt = op.plan, op.family, z.dtype
+    F64 = torch.float64
+    B, R = plan.B, z.shape[0]
+    seg = plan.per_row(torch.arange(B, device=z.device))
+    mask = op.observed if op.observed is not None else torch.ones_like(op.ys, dtype=torch.bool)
+    zero = z.new_zeros(())
+
+    def ssum(x):
+        return torch.zeros(B, dtype=F64, device=z.device).index_add_(0, seg, x.to(F64))
+
+    def quad(u, v):
+        q = (u * (op.Rs @ v.unsqueeze(-1)).squeeze(-1)).sum(-1).to(F64)
+        if R > 1:
+            Ov, Ou = (op.Os @ v[:-1].unsqueeze(-1)).squeeze(-1), (op.Os @ u[:-1].unsqueeze(-1)).squeeze(-1)
+            c = torch.where(plan.cut == 0, ((u[1:] * Ov).sum(-1) + (v[1:] * Ou).sum(-1)).to(F64), zero.to(F64))
+            q = q + torch.cat([c, c.new_zeros(1)])
+        return ssum(q)
+
+    def predictor(zz):
+        bz = zz @ op.Bm.T
+        eta = bz if op.offset is None else bz + op.offset
+        if fam != _hip.GLM_GAUSSIAN and op.extra is not None:
+            eta = eta + op.extra
+        return bz, eta
+
+    s = op.extra if fam == _hip.GLM_GAUSSIAN else None
+    if prop is None:
+        active = torch.zeros(B, dtype=torch.bool, device=z.device)
+        delta = torch.zeros_like(z)
+        iters = torch.zeros(B, dtype=F64, device=z.device)
+    else:
+        active = state[:, 2] == 0
+        delta = torch.where(active[seg].unsqueeze(-1), prop - z, zero)
+        iters = state[:, 1]
+    qa, qb, qc = quad(z, z), quad(z, delta), quad(delta, delta)
+    _, eta0 = predictor(z)
+    de = delta @ op.Bm.T
+    _, g0, _, base0 = _glm_point(fam, op.ys, eta0, s)
+    gd = ssum(torch.where(mask, g0 * de, zero).sum(-1))
+    alpha = torch.zeros(B, dtype=F64, device=z.device)
+    gain, found = torch.zeros_like(alpha), torch.zeros_like(active)
+    for k in range(GLM_CANDIDATES):
+        ak = 0.5 ** k
+        gk = ssum(torch.where(mask, _glm_diff(fam, op.ys, g0, base0, ak * de), zero).sum(-1)) - ak * qb - 0.5 * ak * ak * qc
+        ok = active & ~found & (gk >= 0) & torch.isfinite(gk)
+        alpha, gain, found = torch.where(ok, ak, alpha), torch.where(ok, gk, gain), found | ok
+    a_row = alpha[seg].to(dt).unsqueeze(-1)
+    z_out = z if prop is None else torch.where(a_row == 1, prop, torch.where(a_row == 0, z, z + a_row * (prop - z)))
+    bz, eta = predictor(z_out)
+    l, g, w, _ = _glm_point(fam, op.ys, eta, s)
+    wm, u = torch.where(mask, w, zero), torch.where(mask, w * bz + g, zero)
+    J_Rs = op.Rs + torch.einsum("rc,ca,cb->rab", wm, op.Bm, op.Bm)
+    rhs = u @ op.Bm
+    psi = ssum(torch.where(mask, l, zero).sum(-1)) - 0.5 * (qa + 2 * alpha * qb + alpha * alpha * qc)
+    bound = op.tol * (1 + psi.abs())
+    conv = torch.where(found, gain <= bound, (gd - qb).abs() <= bound)
+    flags = torch.where(conv, float(_hip.GLM_CONVERGED), torch.where(found, 0.0, float(_hip.GLM_STALLED)))
+    out = torch.stack([psi, iters + 1, flags.to(F64), alpha], 1)
+    if prop is None:
+        out[:, 1:] = 0
+    else:
+        out = torch.where(active.unsqueeze(-1), out, state)
+    return z_out.contiguous(), J_Rs.contiguous(), rhs.contiguous(), out
+
+
+def _glm_step(op, z, prop, state):
+    if os.environ.get("CGPS_LEG_GLM_COMPOSED") == "1":
+        return _glm_step_composed(op, z, prop, state)
+    return _glm_step_hip(op, z, prop, state)
+
+
+def _laplace_args(m, ts, ys, lengths, family, observed, offset, log_exposure, noise_var, init, max_iter, tol):
+    """Everything the Laplace calls check, before anything is launched: (family code, ts [R], ys [R, obs], lengths,
+    observed [R, obs] or None, offset [obs] or None, extra [R, obs] or None, init [R, d] or None, dense, (B, n), tol)."""
+    if family not in _FAMILIES:
+        raise ValueError("family must be one of %s, got %r" % (sorted(_FAMILIES), family))
+    fam = _FAMILIES[family]
+    d, obs, dt = m.N.shape[0], m.B.shape[0], m.N.dtype
+    if obs > MAX_PATTERN_OBS:
+        raise ValueError("the Laplace posterior is built for obs_dim <= %d, got %d" % (MAX_PATTERN_OBS, obs))
+    if not 1 <= d <= 8 or dt not in (torch.float32, torch.float64):
+        raise ValueError("the Laplace posterior is built for rank 1..8, float32 / float64")
+    if not isinstance(ts, torch.Tensor) or not isinstance(ys, torch.Tensor):
+        raise ValueError("ts and ys must be tensors")
+    dense, ys_shape = lengths is None, tuple(ys.shape)
+    if fam == _hip.GLM_GAUSSIAN and noise_var is None:
+        raise ValueError("family 'gaussian' needs noise_var, the variance of every observed entry")
+    if fam != _hip.GLM_GAUSSIAN and noise_var is not None:
+        raise ValueError("noise_var belongs to family 'gaussian', got family %r" % family)
+    if fam == _hip.GLM_GAUSSIAN and log_exposure is not None:
+        raise ValueError("log_exposure belongs to the families 'poisson' and 'bernoulli'")
+    ts, ys, lengths, observed, noise_var, dense, bn = _batch_args(obs, ts, ys, lengths, observed, noise_var)
+    if log_exposure is not None:
+        log_exposure = _batch_like_xs(log_exposure, _LOG_EXPOSURE, ys_shape, dense)
+    extra = noise_var if fam == _hip.GLM_GAUSSIAN else log_exposure
+    if extra is not None and extra.dim() == 1:
+        extra = extra.unsqueeze(-1).expand(-1, obs)
+    if offset is not None and (not isinstance(offset, torch.Tensor) or not offset.dtype.is_floating_point or
+                               tuple(offset.shape) != (obs,)):
+        raise ValueError("offset must be a floating-point tensor [%d]" % obs)
+    if init is not None:
+        want = (bn[0], bn[1], d) if dense else (ts.shape[0], d)
+        if not isinstance(init, torch.Tensor) or not init.dtype.is_floating_point or tuple(init.shape) != want:
+            raise ValueError("init must be a floating-point tensor %s, the shape of the mean" % (want,))
+        init = init.reshape(-1, d)
+    if int(max_iter) != max_iter or max_iter < 0:
+        raise ValueError("max_iter must be a non-negative integer, got %r" % (max_iter,))
+    if tol is None:
+        tol = LAPLACE_TOL[dt]
+    elif not tol >= 0:
+        raise ValueError("tol must be >= 0, got %r" % (tol,))
+    tensors = [t for t in (m.N, ts, ys, observed, offset, extra, init) if t is not None]
+    if lengths and not all(t.is_cuda for t in tensors):
+        raise _hip.CgpsError("the Laplace posterior runs on GPU tensors only (there is no CPU implementation)")
+    return fam, ts, ys, lengths, observed, offset, extra, init, dense, bn, float(tol)
+
+
+def _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_iter, tol):
+    """The Newton loop on the concatenated batch: (mean [R, d], cov_diag, cov_off, log_evidence [B], iterations [B],
+    converged [B])."""
+    d, dt, dev = m.N.shape[0], m.N.dtype, m.N.device
+    plan = _cached_batch_plan(lengths, dev)
+    c = lambda t: None if t is None else t.to(dt).contiguous()       # noqa: E731
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    Rs, Os = _peg_precision_seg(ts.to(dt).contiguous(), m.G.contiguous(), plan.cut, info)     # once per call
+    _check_gaps(info, plan, None, _GAP_BLOCK)
+    ys = c(ys)
+    op = _GlmOperands(plan, Rs, Os, ys, None if observed is None else observed.contiguous(), c(offset), c(extra), c(m.B), fam, tol)
+    z = torch.zeros(plan.R, d, dtype=dt, device=dev) if init is None else cr._aligned16(c(init))
+    z, J_Rs, rhs, state = _glm_step(op, z, None, None)
+    for _ in range(int(max_iter)):
+        _, prop = cr.decompose_solve(J_Rs, Os, rhs)
+        z, J_Rs, rhs, state = _glm_step(op, z, prop, state)
+        if bool((state[:, 2] != 0).all()):                           # one flag read on the host per iteration
+            break
+    Sd, So = cr.inverse_blocks(cr.decompose(J_Rs, Os))              # J at the mode: the step wrote it at z_out
+    if plan.B > 1:
+        So.index_fill_(0, plan.boundary_rows(1), 0)
+    _, logdet_J = cr.mahal_and_det_batch(J_Rs, Os, None, lengths=lengths)
+    _, logdet_K = cr.mahal_and_det_batch(Rs, Os, None, lengths=lengths)
+    ev = state[:, 0] + 0.5 * (logdet_K.to(torch.float64) - logdet_J.to(torch.float64))
+    if fam == _hip.GLM_POISSON:                                      # the term of log p that does not depend on eta
+        lg = torch.lgamma(ys.to(torch.float64) + 1)
+        if observed is not None:
+            lg = torch.where(observed, lg, lg.new_zeros(()))
+        ev = ev - torch.zeros_like(ev).index_add_(0, plan.per_row(torch.arange(plan.B, device=dev)), lg.sum(-1))
+    return z, Sd, So, ev, state[:, 1].to(torch.int64), (state[:, 2].to(torch.int64) & _hip.GLM_CONVERGED) != 0
+
+
+def laplace_posterior_batch(m, ts, ys, lengths=None, family=None, observed=None, offset=None, log_exposure=None,
+                            noise_var=None, init=None, max_iter=50, tol=None):
+    """The Laplace approximation of the posterior of B independent series whose observations are counts, binary outcomes
+    or Gaussian values: ``LaplacePosterior(mean, cov, log_evidence, iterations, converged)``.
+
+    Model: z ~ the LEG prior of ``m`` (``m.Lambda`` is not used), and every observed entry (i, c) has the linear
+    predictor eta_ic = B[c, :] z_i + offset[c] + log_exposure[i, c] (both optional, default 0) with
+    ``family="poisson"``: log p = y eta - e^eta - lgamma(y + 1); ``"bernoulli"``: log p = y eta - softplus(eta);
+    ``"gaussian"``: y ~ N(eta, noise_var[i, c]), for which the approximation is exact.
+
+    Layouts, ``lengths`` and ``observed``: those of ``insample_posterior_batch`` (dense ts[B, n], ys[B, n, obs_dim], or
+    ragged with host ``lengths``); ``log_exposure`` and ``noise_var`` in the layout of ys (or one value per row);
+    ``offset`` [obs_dim]; ``init`` a starting point in the shape of the mean (default zeros).  ``mean`` is the posterior
+    mode and ``cov`` = (diag, off) the blocks of the inverse of J = K + blockdiag(B^T W B) at the mode, in the shapes of
+    ``insample_posterior_batch``; ``log_evidence`` [B] (fp64) = sum log p(y | eta) - z^T K z / 2 + log|K| / 2 - log|J| / 2
+    at the mode; ``iterations`` [B] (int64) the Newton steps a series took part in; ``converged`` [B] (bool).  Rows that
+    observe nothing take part, so target times go in through ``merge_targets``; a padded dense batch is the mask whose
+    tail rows are False.  What ys, log_exposure and noise_var hold at unobserved entries is ignored, NaN included.
+    Values of ys are not checked (as those of ``noise_var`` are not elsewhere).  B = 0 returns empty tensors.  Every
+    ValueError is raised before anything is launched.  Inference only: runs under ``torch.no_grad``.
+
+    How: Newton's method on the concatenated block-tridiagonal system.  cgps_peg_precision_seg writes
+    the prior blocks once; every iteration is one ``cr.decompose_solve`` (the proposal J^-1 r) and one launch of
+    cgps_leg_glm_step, one workgroup per series, which picks the largest of the step lengths 1, 1/2, .., 2^-11 whose
+    objective is finite and not below the current one, applies it, and writes J and r at the new point.  A series has
+    converged once a step's gain is <= tol (1 + |psi|) (``tol=None``: ``LAPLACE_TOL``), and is then frozen: its result does
+    not depend on how long its neighbours take.  The loop reads ONE flag on the host per iteration (have all series
+    finished?) and stops early when they have; a series that has not converged within ``max_iter`` steps does not raise,
+    ``converged`` reports it.  Then one factorisation at the mode, ``cr.inverse_blocks``, and two
+    ``cr.mahal_and_det_batch`` calls for log|J| and log|K| per series.  CGPS_LEG_GLM_COMPOSED=1 composes the step from
+    torch passes instead (A/B timing).
+
+    One workgroup per series makes this a call for batches: one series of 2^20 rows runs on one workgroup.  Every rank
+    1..8, obs_dim <= 8, both precisions.  CPU tensors raise ``CgpsError``: there is no CPU implementation."""
+    with torch.no_grad():
+        like = ts
+        fam, ts, ys, lengths, observed, offset, extra, init, dense, bn, tol = _laplace_args(
+            m, ts, ys, lengths, family, observed, offset, log_exposure, noise_var, init, max_iter, tol)
+        d, dt = m.N.shape[0], m.N.dtype
+        if not lengths:
+            e = lambda *shape, dtype=dt: torch.empty(shape, dtype=dtype, device=like.device)      # noqa: E731
+            n = bn[1] if dense else None
+            mean, cov = ((e(0, n, d), (e(0, n, d, d), e(0, max(n - 1, 0), d, d))) if dense else
+                         (e(0, d), (e(0, d, d), e(0, d, d))))
+            return LaplacePosterior(mean, cov, e(0, dtype=torch.float64), e(0, dtype=torch.int64), e(0, dtype=torch.bool))
+        mean, Sd, So, ev, iters, conv = _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_iter, tol)
+        if dense:
+            mean, (Sd, So) = _dense_posterior(mean, Sd, So, bn[0], bn[1])
+        return LaplacePosterior(mean, (Sd, So), ev, iters, conv)
+
+
+def laplace_posterior(m, ts, ys, family, observed=None, offset=None, log_exposure=None, noise_var=None, init=None,
+                      max_iter=50, tol=None):
+    """``laplace_posterior_batch`` of one series ts[n], ys[n, obs_dim]: ``LaplacePosterior`` with mean [n, d], cov
+    ([n, d, d], [n-1, d, d]) and 0-d ``log_evidence``, ``iterations`` and ``converged``.  The series runs on one
+    workgroup: the call is meant for series of moderate length, many of them through the batch form."""
+    if not isinstance(ts, torch.Tensor) or not isinstance(ys, torch.Tensor) or ts.dim() != 1 or ys.dim() != 2:
+        raise ValueError("one series wants ts[n] and ys[n, obs_dim]")
+    if ts.shape[0] < 1:
+        raise ValueError("series of length 0")
+    r = laplace_posterior_batch(m, ts, ys, [ts.shape[0]], family, observed, offset, log_exposure, noise_var, init, max_iter, tol)
+    return LaplacePosterior(r.mean, r.cov, r.log_evidence[0], r.iterations[0], r.converged[0])
+
+
 # ---- the config-5 workload -----------------------------------------------------------------
 def co2_like_series(rows=770, seed=0, dtype=torch.float64):
     """Mauna-Loa-shaped monthly series (decimal date, ppm): quadratic trend + annual and
