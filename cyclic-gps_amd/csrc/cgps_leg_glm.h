@@ -8,7 +8,8 @@
 //             a = z^T K z,  b = z^T K delta,  c = delta^T K delta,
 //           and the likelihood one sum per candidate: sum_ic [l(eta + alpha dEta) - l(eta)] for alpha = 1, 1/2, ..,
 //           2^-(GLM_CANDIDATES - 1), each difference written so that nothing of the size of l itself cancels
-//           (Poisson: y t - e^eta expm1(t); Bernoulli: y t - log1p(sigma(eta) expm1(t)); Gaussian: a polynomial in t).
+//           (Poisson: y t - e^eta expm1(t); Bernoulli: y' t' - log1p(m expm1(t')) with m = sigma(-|eta|) <= 1/2 and
+//           (y', t') = (y, t) at eta <= 0, (1 - y, -t) at eta > 0; Gaussian: a polynomial in t).
 //           gain(alpha) = that sum - alpha b - alpha^2 c / 2 is the objective's change, in fp64 in both precisions.
 //           A candidate whose gain is NaN or infinite (e^eta overflowed) fails `gain >= 0` and is rejected.
 //   choose  the largest alpha with a finite gain >= 0.  None: the series keeps z; by concavity no step along delta gains
@@ -43,15 +44,18 @@ __device__ __forceinline__ double glm_abs(double x) { return fabs(x); }
 __device__ __forceinline__ double glm_wave_all(double v) { return __shfl(wave_sum(v), 0, 64); }
 
 // What a family needs of one entry at the linear predictor eta: the log density l (without lgamma(y + 1)), its
-// derivative g, the weight w = -l'' >= 0, and `base`, the factor of the line difference (diff below).
+// derivative g, the weight w = -l'' >= 0, and `base`, the factor of the line difference (diff below); `up`: Bernoulli
+// with eta > 0, where the difference is taken on the mirror image l(eta; y) = l(-eta; 1 - y).
 template <typename T>
 struct GlmPoint {
   T l, g, w, base;
+  bool up;
 };
 
 template <typename T>
 __device__ __forceinline__ GlmPoint<T> glm_point(int family, T y, T eta, T s) {
   GlmPoint<T> p;
+  p.up = false;
   if (family == GLM_POISSON) {
     const T e = glm_exp(eta);
     p.l = y * eta - e;
@@ -65,7 +69,8 @@ __device__ __forceinline__ GlmPoint<T> glm_point(int family, T y, T eta, T s) {
     p.l = y * eta - ((eta > T(0) ? eta : T(0)) + glm_log1p(e));
     p.g = y - sig;
     p.w = e * r * r;                                        // sigma (1 - sigma)
-    p.base = sig;
+    p.base = e * r;                                         // sigma(-|eta|): sigma at eta <= 0, 1 - sigma at eta > 0
+    p.up = eta > T(0);
   } else {
     const T is = T(1) / s, res = y - eta;
     p.l = T(-0.5) * res * res * is - T(0.5) * glm_log(T(6.283185307179586476925) * s);
@@ -76,11 +81,19 @@ __device__ __forceinline__ GlmPoint<T> glm_point(int family, T y, T eta, T s) {
   return p;
 }
 
-// l(eta + t) - l(eta) from the point at eta; +-inf or NaN where e^t overflows
+// l(eta + t) - l(eta) from the point at eta; +-inf or NaN where e^t overflows.
+// Bernoulli: softplus(eta + t) - softplus(eta) = log1p(sigma(eta) expm1(t)), but 1 + sigma expm1(t) = (1 - sigma) + sigma e^t
+// is then formed from two numbers that have each been rounded to about 1 when eta >> 0 and t << 0 (at eta = 18, t = -20
+// in fp32 it rounds to 0 and the difference to +inf).  So the line is always walked from the side on which sigma <= 1/2:
+// at eta > 0 on the mirror image (-eta, -t, 1 - y), which is the same function.  Then m <= 1/2 and expm1 >= -1 put the
+// argument of log1p at or above -1/2, nothing cancels, and a data set and its mirror image take bit-equal differences.
 template <typename T>
 __device__ __forceinline__ T glm_diff(int family, T y, const GlmPoint<T>& p, T t) {
   if (family == GLM_POISSON) return y * t - p.base * glm_expm1(t);
-  if (family == GLM_BERNOULLI) return y * t - glm_log1p(p.base * glm_expm1(t));
+  if (family == GLM_BERNOULLI) {
+    const T ym = p.up ? T(1) - y : y, tm = p.up ? -t : t;
+    return ym * tm - glm_log1p(p.base * glm_expm1(tm));
+  }
   return t * (p.g - T(0.5) * t * p.base);
 }
 

@@ -3370,25 +3370,29 @@ def _glm_step_hip(op, z, prop, state):
 
 
 def _glm_point(family, y, eta, s):
-    """(log density, its derivative g, the weight w = -l'', the factor of ``_glm_diff``) at the linear predictor eta"""
+    """(log density, its derivative g, the weight w = -l'', the factor of ``_glm_diff``, ``up``) at the linear predictor
+    eta; ``up``: Bernoulli entries with eta > 0, whose line difference is taken on the mirror image (None elsewhere)"""
     if family == _hip.GLM_POISSON:
         e = torch.exp(eta)
-        return y * eta - e, y - e, e, e
+        return y * eta - e, y - e, e, e, None
     if family == _hip.GLM_BERNOULLI:
         e = torch.exp(-eta.abs())
         r = 1.0 / (1.0 + e)
         sig = torch.where(eta >= 0, r, e * r)
-        return y * eta - (eta.clamp(min=0) + torch.log1p(e)), y - sig, e * r * r, sig
+        return y * eta - (eta.clamp(min=0) + torch.log1p(e)), y - sig, e * r * r, e * r, eta > 0
     inv, res = 1.0 / s, y - eta
-    return -0.5 * res * res * inv - 0.5 * torch.log(2 * math.pi * s), res * inv, inv, inv
+    return -0.5 * res * res * inv - 0.5 * torch.log(2 * math.pi * s), res * inv, inv, inv, None
 
 
-def _glm_diff(family, y, g, base, t):
-    """l(eta + t) - l(eta) with nothing of the size of l cancelling"""
+def _glm_diff(family, y, g, base, up, t):
+    """l(eta + t) - l(eta) with nothing of the size of l cancelling: the arithmetic of ``glm_diff`` (csrc/cgps_leg_glm.h).
+    Bernoulli: from the side on which sigma <= 1/2, i.e. on the mirror image (1 - y, -t) where eta > 0; base =
+    sigma(-|eta|), so the argument of log1p stays at or above -1/2."""
     if family == _hip.GLM_POISSON:
         return y * t - base * torch.expm1(t)
     if family == _hip.GLM_BERNOULLI:
-        return y * t - torch.log1p(base * torch.expm1(t))
+        ym, tm = torch.where(up, 1.0 - y, y), torch.where(up, -t, t)
+        return ym * tm - torch.log1p(base * torch.expm1(tm))
     return t * (g - 0.5 * t * base)
 
 
@@ -3433,19 +3437,19 @@ def _glm_step_composed(op, z, prop, state):
     qa, qb, qc = quad(z, z), quad(z, delta), quad(delta, delta)
     _, eta0 = predictor(z)
     de = delta @ op.Bm.T
-    _, g0, _, base0 = _glm_point(fam, op.ys, eta0, s)
+    _, g0, _, base0, up0 = _glm_point(fam, op.ys, eta0, s)
     gd = ssum(torch.where(mask, g0 * de, zero).sum(-1))
     alpha = torch.zeros(B, dtype=F64, device=z.device)
     gain, found = torch.zeros_like(alpha), torch.zeros_like(active)
     for k in range(GLM_CANDIDATES):
         ak = 0.5 ** k
-        gk = ssum(torch.where(mask, _glm_diff(fam, op.ys, g0, base0, ak * de), zero).sum(-1)) - ak * qb - 0.5 * ak * ak * qc
+        gk = ssum(torch.where(mask, _glm_diff(fam, op.ys, g0, base0, up0, ak * de), zero).sum(-1)) - ak * qb - 0.5 * ak * ak * qc
         ok = active & ~found & (gk >= 0) & torch.isfinite(gk)
         alpha, gain, found = torch.where(ok, ak, alpha), torch.where(ok, gk, gain), found | ok
     a_row = alpha[seg].to(dt).unsqueeze(-1)
     z_out = z if prop is None else torch.where(a_row == 1, prop, torch.where(a_row == 0, z, z + a_row * (prop - z)))
     bz, eta = predictor(z_out)
-    l, g, w, _ = _glm_point(fam, op.ys, eta, s)
+    l, g, w, _, _ = _glm_point(fam, op.ys, eta, s)
     wm, u = torch.where(mask, w, zero), torch.where(mask, w * bz + g, zero)
     J_Rs = op.Rs + torch.einsum("rc,ca,cb->rab", wm, op.Bm, op.Bm)
     rhs = u @ op.Bm

@@ -303,3 +303,117 @@ def test_a_series_does_not_depend_on_its_neighbours():
         a, b = leg.laplace_posterior_batch(mm, ts, ys, **kw), leg.laplace_posterior_batch(mm, tsn, ysn, **kwn)
         for x, y in zip(_results(a) + [a.iterations, a.converged], _results(b) + [b.iterations, b.converged]):
             assert torch.equal(x, y)
+
+
+# ---- the loop, end to end: the other families in fp32, the mirror image, max_iter, a stall ---------------------------------
+def _fp32_against_the_truth(case, what):
+    m = _model(case, F32, "cuda")
+    ts, ys, kw = _ragged(case, F32)
+    r = leg.laplace_posterior_batch(m, ts, ys, **kw)
+    yard = _composed(lambda: leg.laplace_posterior_batch(m, ts, ys, **kw))
+    worst = _assert_fp32(_results(r), _results(yard), _truth_arrays(case), what)
+    print("%s: worst ratio to the fp32 bound %.3f, iterations %s" % (what, worst, r.iterations.tolist()))
+    return r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d,obs", lr.FORMS_FP32)
+def test_the_bernoulli_family_in_fp32(d, obs):
+    _fp32_against_the_truth(lr.batch_case(d, obs, "bernoulli", lr.LENGTHS_FP32, 3), "bernoulli fp32 d %d obs %d" % (d, obs))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d,obs", lr.FORMS_FP32)
+def test_the_gaussian_family_in_fp32(d, obs):
+    _fp32_against_the_truth(lr.batch_case(d, obs, "gaussian", lr.LENGTHS_FORMS, 2), "gaussian fp32 d %d obs %d" % (d, obs))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [F64, F32], ids=["fp64", "fp32"])
+def test_near_certain_events_and_their_mirror_image(dtype):
+    """Bernoulli data with offsets near +8, and (1 - y, -offset, -B): the same posterior, so the same iteration.  Both
+    converge, in the same number of steps per series, each to its own dense truth."""
+    runs = []
+    for mirrored in (False, True):
+        case = lr.mirror_case(mirrored)
+        what = "offsets near %s8" % ("-" if mirrored else "+")
+        if dtype == F64:
+            m = _model(case, F64, "cuda")
+            ts, ys, kw = _ragged(case, F64)
+            r = leg.laplace_posterior_batch(m, ts, ys, **kw)
+            _assert_fp64(_results(r), _truth_arrays(case), what)
+        else:
+            r = _fp32_against_the_truth(case, what)
+        assert bool(r.converged.all()), (what, r.converged.tolist(), r.iterations.tolist())
+        runs.append(r)
+    print("iterations", runs[0].iterations.tolist(), runs[1].iterations.tolist())
+    assert runs[0].iterations.tolist() == runs[1].iterations.tolist()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("start", ["zeros", "a point"])
+def test_max_iter_0_returns_the_newton_system_at_init(start):
+    """no step is taken: the mean is ``init`` bit for bit, cov the blocks of the dense J(init)^-1, and log_evidence
+    psi(init) + (log|K| - log|J(init)|) / 2"""
+    case = lr.batch_case(3, 2, "poisson", lr.LENGTHS_FORMS, 1)
+    m = _model(case, F64, "cuda")
+    ts, ys, kw = _ragged(case, F64)
+    R = sum(case.lengths)
+    init = None if start == "zeros" else 0.3 * torch.randn(R, 3, generator=torch.Generator().manual_seed(5), dtype=F64)
+    r = leg.laplace_posterior_batch(m, ts, ys, max_iter=0, init=None if init is None else init.cuda(), **kw)
+    z = torch.zeros(R, 3, dtype=F64) if init is None else init
+    assert torch.equal(r.mean.cpu(), z)
+    assert r.iterations.tolist() == [0] * len(case.lengths) and r.converged.tolist() == [False] * len(case.lengths)
+    diags, offs, evs, s = [], [], [], 0
+    for b, t in enumerate(case.truths()):
+        n = case.lengths[b]
+        cd, co, ev = lr.newton_system_at(t, case.family, z[s:s + n])
+        diags.append(cd)
+        offs.append(co)
+        if b + 1 < len(case.lengths):
+            offs.append(torch.zeros(1, 3, 3, dtype=F64))
+        evs.append(ev)
+        s += n
+    _assert_fp64(_results(r), (z, torch.cat(diags), torch.cat(offs), torch.tensor(evs, dtype=F64)), "max_iter 0 from " + start)
+
+
+@pytest.mark.gpu
+def test_max_iter_runs_out_and_a_restart_carries_on():
+    """two steps are not enough for the slow series of the independence case: it reports so; restarted from where it
+    stopped it takes the steps that were left, and ends where one run ends"""
+    case = lr.independence_case()
+    m = _model(case, F64, "cuda")
+    ts, ys, kw = _ragged(case, F64)
+    full = leg.laplace_posterior_batch(m, ts, ys, max_iter=50, **kw)
+    assert bool(full.converged.all())
+    short = leg.laplace_posterior_batch(m, ts, ys, max_iter=2, **kw)
+    assert not bool(short.converged[1]) and int(short.iterations[1]) == 2, (short.converged.tolist(), short.iterations.tolist())
+    assert int(full.iterations[1]) > 2 and int(short.iterations.max()) <= 2
+    rest = leg.laplace_posterior_batch(m, ts, ys, max_iter=48, init=short.mean, **kw)
+    print("iterations: one run %s, two steps %s, the restart %s" % (full.iterations.tolist(), short.iterations.tolist(), rest.iterations.tolist()))
+    assert bool(rest.converged.all())
+    for b in range(len(case.lengths)):
+        if not bool(short.converged[b]):
+            assert int(short.iterations[b]) + int(rest.iterations[b]) == int(full.iterations[b]), b
+    for a, w in zip(_results(rest), _results(full)):
+        assert float((a - w).abs().max()) <= 1e-10 * max(1.0, float(w.abs().max()))
+
+
+@pytest.mark.gpu
+def test_counts_near_a_million_stall_from_zero_and_converge_from_a_warm_start():
+    """twelve candidates reach counts of 10^4 from a zero start; at 10^6 the smallest candidate still puts eta
+    near 500, nothing gains, and the series is flagged STALLED at its first step -- reported, finite, at z = 0.  With
+    ``init`` = log(y + 1) mapped through B the same data converges to the dense truth."""
+    case = lr.stall_case()
+    m = _model(case, F64, "cuda")
+    ts, ys, kw = _ragged(case, F64)
+    r = leg.laplace_posterior_batch(m, ts, ys, **kw)
+    assert r.converged.tolist() == [False] and r.iterations.tolist() == [1]
+    assert float(r.mean.abs().max()) == 0.0
+    assert all(bool(torch.isfinite(t).all()) for t in (r.mean, r.cov[0], r.cov[1], r.log_evidence))
+    sr = case.series[0]
+    init = torch.log(sr["ys"] + 1) @ torch.linalg.pinv(case.B).T              # B init = log(y + 1): obs <= d
+    w = leg.laplace_posterior_batch(m, ts, ys, init=init.cuda(), **kw)
+    assert bool(w.converged.all()), w.iterations.tolist()
+    print("warm start: %d iterations" % int(w.iterations[0]))
+    _assert_fp64(_results(w), _truth_arrays(case), "counts near 1e6 from a warm start")
