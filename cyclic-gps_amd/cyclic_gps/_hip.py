@@ -1,4 +1,5 @@
-"""ctypes binding of libcgps.so (C ABI: include/cgps.h, and include/cgps_glm.h for the extension entry points).
+"""ctypes binding of libcgps.so (C ABI: include/cgps.h, and include/cgps_glm.h and include/cgps_glm_grad.h for the
+extension entry points).
 
 The library is the product: if it is missing this module raises, it never falls
 back to a CPU or torch implementation.
@@ -92,6 +93,11 @@ _SIGNATURES = {
 _EXTENSION_SIGNATURES = {
     "cgps_leg_glm_step": (_int, [_vp] * 10 + [_i64] * 2 + [_int] * 4 + [ctypes.c_double] + [_vp] * 6),
 }
+# Entry points declared in include/cgps_glm_grad.h (the gradient of the Laplace evidence): a third table
+_GLM_GRADIENT_SIGNATURES = {
+    "cgps_leg_glm_evidence_rhs": (_int, [_vp] * 7 + [_i64] + [_int] * 4 + [_vp] * 2),
+    "cgps_leg_glm_evidence_adjoint": (_int, [_vp] * 13 + [_i64] * 2 + [_int] * 4 + [_vp] * 6),
+}
 GLM_POISSON, GLM_BERNOULLI, GLM_GAUSSIAN = range(3)
 GLM_CONVERGED, GLM_STALLED = 1, 2
 GLM_STATE = 4
@@ -110,6 +116,11 @@ def extension_symbols():
     return sorted(_EXTENSION_SIGNATURES)
 
 
+def glm_gradient_symbols():
+    """the entry points of include/cgps_glm_grad.h"""
+    return sorted(_GLM_GRADIENT_SIGNATURES)
+
+
 def lib():
     """Load libcgps.so once; raise loudly when it is not there."""
     global _lib
@@ -125,7 +136,8 @@ def lib():
         if os.path.exists(rt):
             ctypes.CDLL(rt, mode=ctypes.RTLD_GLOBAL)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_EXTENSION_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_EXTENSION_SIGNATURES.items()) + list(
+                _GLM_GRADIENT_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -3517,9 +3517,9 @@ def _laplace_args(m, ts, ys, lengths, family, observed, offset, log_exposure, no
     return fam, ts, ys, lengths, observed, offset, extra, init, dense, bn, float(tol)
 
 
-def _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_iter, tol):
+def _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_iter, tol, saved=None):
     """The Newton loop on the concatenated batch: (mean [R, d], cov_diag, cov_off, log_evidence [B], iterations [B],
-    converged [B])."""
+    converged [B]).  ``saved``: a dict that receives the operands of the evidence's backward (``_LaplaceEvidenceFn``)."""
     d, dt, dev = m.N.shape[0], m.N.dtype, m.N.device
     plan = _cached_batch_plan(lengths, dev)
     c = lambda t: None if t is None else t.to(dt).contiguous()       # noqa: E731
@@ -3535,7 +3535,8 @@ def _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_it
         z, J_Rs, rhs, state = _glm_step(op, z, prop, state)
         if bool((state[:, 2] != 0).all()):                           # one flag read on the host per iteration
             break
-    Sd, So = cr.inverse_blocks(cr.decompose(J_Rs, Os))              # J at the mode: the step wrote it at z_out
+    dec = cr.decompose(J_Rs, Os)                                    # J at the mode: the step wrote it at z_out
+    Sd, So = cr.inverse_blocks(dec)
     if plan.B > 1:
         So.index_fill_(0, plan.boundary_rows(1), 0)
     _, logdet_J = cr.mahal_and_det_batch(J_Rs, Os, None, lengths=lengths)
@@ -3546,11 +3547,180 @@ def _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_it
         if observed is not None:
             lg = torch.where(observed, lg, lg.new_zeros(()))
         ev = ev - torch.zeros_like(ev).index_add_(0, plan.per_row(torch.arange(plan.B, device=dev)), lg.sum(-1))
-    return z, Sd, So, ev, state[:, 1].to(torch.int64), (state[:, 2].to(torch.int64) & _hip.GLM_CONVERGED) != 0
+    conv = (state[:, 2].to(torch.int64) & _hip.GLM_CONVERGED) != 0
+    if saved is not None:                                            # what the gradient of the evidence reads
+        s_rhs = _glm_evidence_rhs(op, z, Sd)
+        u = torch.zeros_like(s_rhs) if fam == _hip.GLM_GAUSSIAN else cr._solve_raw(dec, s_rhs)
+        Pd, Po = cr.inverse_blocks(cr.decompose(Rs, Os))
+        saved.update(op=op, z=z, u=u, Sd=Sd, So=So, Pd=Pd, Po=Po, conv=conv, ts=ts.to(dt).contiguous(), G=m.G.contiguous())
+    return z, Sd, So, ev, state[:, 1].to(torch.int64), conv
+
+
+# ---- the gradient of the Laplace evidence at the mode -------------------------------------------------
+def _glm_composed():
+    return os.environ.get("CGPS_LEG_GLM_COMPOSED") == "1"
+
+
+def _glm_evidence_rhs_hip(op, z, Sd):
+    """One launch of cgps_leg_glm_evidence_rhs: s [R, d] = dE / dz at the mode."""
+    R, d = z.shape
+    s = torch.empty(R, d, dtype=z.dtype, device=z.device)
+    P = _hip.ptr
+    _hip.check(_hip.lib().cgps_leg_glm_evidence_rhs(
+        P(z), P(Sd), P(op.ys), P(op.pattern), P(op.offset), P(op.extra), P(op.Bm), R, d, op.ys.shape[1],
+        _hip.dtype_code(z.dtype), op.family, P(s), _hip.stream_ptr()))
+    return s
+
+
+def _glm_evidence_adjoint_hip(op, z, u, Sd, So, Pd, Po, gE):
+    """One call of cgps_leg_glm_evidence_adjoint: (gRs [R, d, d], gOs [R - 1, d, d], g_extra [R, obs], gB_part
+    [B, obs, d], goffset_part [B, obs]), the last two fp64 and per series."""
+    R, d = z.shape
+    dt, dev, obs, B = z.dtype, z.device, op.ys.shape[1], op.plan.B
+    gRs = torch.empty(R, d, d, dtype=dt, device=dev)
+    gOs = torch.empty(R - 1, d, d, dtype=dt, device=dev)
+    g_extra = torch.empty(R, obs, dtype=dt, device=dev)
+    gB_part = torch.empty(B, obs, d, dtype=torch.float64, device=dev)
+    goffset_part = torch.empty(B, obs, dtype=torch.float64, device=dev)
+    P = _hip.ptr
+    _hip.check(_hip.lib().cgps_leg_glm_evidence_adjoint(
+        P(z), P(u), P(Sd), P(So), P(Pd), P(Po), P(op.ys), P(op.pattern), P(op.offset), P(op.extra), P(op.Bm),
+        P(op.plan.offsets), P(gE), B, R, d, obs, _hip.dtype_code(dt), op.family, P(gRs), P(gOs), P(g_extra), P(gB_part),
+        P(goffset_part), _hip.stream_ptr()))
+    return gRs, gOs, g_extra, gB_part, goffset_part
+
+
+def _glm_wprime(family, eta, w):
+    """dw / d eta: the arithmetic of ``glm_wprime`` (csrc/cgps_leg_glm_grad.h)"""
+    if family == _hip.GLM_POISSON:
+        return w
+    if family == _hip.GLM_BERNOULLI:
+        e = torch.exp(-eta.abs())
+        t = (1.0 - e) / (1.0 + e)
+        return torch.where(eta >= 0, -w * t, w * t)
+    return torch.zeros_like(w)
+
+
+def _glm_evidence_entries(op, z, Sd):
+    """(mask, g, w, w', v, S B^T [R, obs, d]) of every entry at z, as torch passes; g, w, w' are zero where nothing is
+    observed (whatever ys and extra hold there)."""
+    fam = op.family
+    mask = op.observed if op.observed is not None else torch.ones_like(op.ys, dtype=torch.bool)
+    zero = z.new_zeros(())
+    eta = z @ op.Bm.T
+    if op.offset is not None:
+        eta = eta + op.offset
+    if fam != _hip.GLM_GAUSSIAN and op.extra is not None:
+        eta = eta + op.extra
+    _, g, w, _, _ = _glm_point(fam, op.ys, eta, op.extra if fam == _hip.GLM_GAUSSIAN else None)
+    wp = _glm_wprime(fam, eta, w)
+    SB = torch.einsum("rak,ck->rca", Sd, op.Bm)
+    v = (SB * op.Bm).sum(-1)
+    return mask, torch.where(mask, g, zero), torch.where(mask, w, zero), torch.where(mask, wp, zero), v, SB
+
+
+def _glm_evidence_rhs_composed(op, z, Sd):
+    """cgps_leg_glm_evidence_rhs as torch passes (CGPS_LEG_GLM_COMPOSED=1): the same arithmetic in the arrays' dtype."""
+    _, _, _, wp, v, _ = _glm_evidence_entries(op, z, Sd)
+    return (-0.5 * (wp * v) @ op.Bm).contiguous()
+
+
+def _glm_evidence_adjoint_composed(op, z, u, Sd, So, Pd, Po, gE):
+    """cgps_leg_glm_evidence_adjoint as torch passes over [R, obs], [R, obs, d] and [R, d, d] arrays
+    (CGPS_LEG_GLM_COMPOSED=1): the same arithmetic in the arrays' dtype, the sums per series in fp64 (``index_add_``: not
+    in a fixed order).  For A/B timing, and the yardstick of the kernels' fp32 error."""
+    plan, fam, dt = op.plan, op.family, z.dtype
+    F64 = torch.float64
+    B, R = plan.B, z.shape[0]
+    obs, d = op.Bm.shape
+    seg = plan.per_row(torch.arange(B, device=z.device))
+    ge = gE[seg].to(dt)
+    mask, g, w, wp, v, SB = _glm_evidence_entries(op, z, Sd)
+    e = g - 0.5 * wp * v - w * (u @ op.Bm.T)
+    if fam == _hip.GLM_GAUSSIAN:
+        g_extra = torch.where(mask, 0.5 * (g * g - w + v * w * w), z.new_zeros(())) * ge[:, None]
+    else:
+        g_extra = e * ge[:, None]
+    keep, keep_b = (ge != 0), (gE != 0)                              # a dropped series: selected, not multiplied, as the kernels do
+    zero = z.new_zeros(())
+    g_extra = torch.where(keep[:, None], g_extra, zero)
+    outer = lambda a, b: a.unsqueeze(-1) * b.unsqueeze(-2)           # noqa: E731
+    gRs = torch.where(keep[:, None, None], (0.5 * ge)[:, None, None] * (Pd - Sd - outer(z, z) - outer(u, z) - outer(z, u)), zero)
+    gOs = z.new_zeros(max(R - 1, 0), d, d)
+    if R > 1:
+        inner = Po - So - outer(z[1:], z[:-1]) - outer(u[1:], z[:-1]) - outer(z[1:], u[:-1])
+        gOs = torch.where(((plan.cut == 0) & keep[:-1])[:, None, None], ge[:-1, None, None] * inner, zero)
+    rowB = e.unsqueeze(-1) * z.unsqueeze(1) + g.unsqueeze(-1) * u.unsqueeze(1) - w.unsqueeze(-1) * SB
+    zero64 = gE.new_zeros(())
+    gB_part = torch.zeros(B, obs, d, dtype=F64, device=z.device).index_add_(0, seg, rowB.to(F64)) * gE[:, None, None]
+    goffset_part = torch.zeros(B, obs, dtype=F64, device=z.device).index_add_(0, seg, e.to(F64)) * gE[:, None]
+    gB_part, goffset_part = torch.where(keep_b[:, None, None], gB_part, zero64), torch.where(keep_b[:, None], goffset_part, zero64)
+    return gRs.contiguous(), gOs.contiguous(), g_extra.contiguous(), gB_part, goffset_part
+
+
+def _glm_evidence_rhs(op, z, Sd):
+    return _glm_evidence_rhs_composed(op, z, Sd) if _glm_composed() else _glm_evidence_rhs_hip(op, z, Sd)
+
+
+def _glm_evidence_adjoint(op, z, u, Sd, So, Pd, Po, gE):
+    fn = _glm_evidence_adjoint_composed if _glm_composed() else _glm_evidence_adjoint_hip
+    return fn(op, z, u, Sd, So, Pd, Po, gE)
+
+
+_LAPLACE_SAVED = ("z", "u", "Sd", "So", "Pd", "Po", "conv", "ts", "G")
+
+
+def _laplace_saved(log_evidence):
+    """What the backward of a differentiable ``log_evidence`` will read, as a dict: the operands ``op`` (_GlmOperands),
+    the mode z, u = J^-1 dE/dz, the blocks of J^-1 (Sd, So) and of K^-1 (Pd, Po), ``conv``, and ts and G as the prior
+    blocks were built from them.  For the tests and tools that call the two entries on their own."""
+    node = log_evidence.grad_fn
+    while node is not None and not hasattr(node, "op"):              # (a 0-d evidence is a select of the [1] tensor)
+        node = node.next_functions[0][0] if node.next_functions else None
+    return dict(zip(_LAPLACE_SAVED, node.saved_tensors), op=node.op)
+
+
+class _LaplaceEvidenceFn(torch.autograd.Function):
+    """log_evidence [B] as a function of (G, B, offset, extra, ts): the forward hands on the values the Newton loop
+    computed, the backward is the closed-form gradient at the mode: cgps_leg_glm_evidence_adjoint, then
+    cgps_peg_precision_adjoint_seg for G and ts, then the sums over the series.  ``extra`` and ``ts`` are the caller's
+    tensors in the caller's layout; their gradients go back in that layout and dtype.  No second derivatives."""
+
+    @staticmethod
+    def forward(ctx, ev, G, Bm, offset, extra, ts, saved):
+        ctx.op, ctx.extra_per_row = saved["op"], saved["extra_per_row"]
+        ctx.save_for_backward(*(saved[k] for k in _LAPLACE_SAVED))   # freed with the graph: a second backward raises
+        ctx.like = tuple(None if t is None else (tuple(t.shape), t.dtype) for t in (G, Bm, offset, extra, ts))
+        return ev.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gE):
+        sv, needs, op = dict(zip(_LAPLACE_SAVED, ctx.saved_tensors)), ctx.needs_input_grad, ctx.op
+        gE = torch.where(sv["conv"], gE.to(torch.float64), gE.new_zeros((), dtype=torch.float64)).contiguous()
+        gRs, gOs, g_extra, gB_part, goffset_part = _glm_evidence_adjoint(op, sv["z"], sv["u"], sv["Sd"], sv["So"], sv["Pd"],
+                                                                         sv["Po"], gE)
+        out = [None] * 7
+        if needs[1] or needs[5]:
+            gG, gts = _peg_precision_adjoint_models(sv["ts"], sv["G"], op.plan.cut, gRs, gOs, needs[5])
+            if needs[1]:
+                out[1] = gG.to(ctx.like[0][1])
+            if needs[5]:
+                out[5] = gts.reshape(ctx.like[4][0]).to(ctx.like[4][1])
+        if needs[2]:
+            out[2] = gB_part.sum(0).to(ctx.like[1][1])
+        if needs[3]:
+            out[3] = goffset_part.sum(0).to(ctx.like[2][1])
+        if needs[4]:
+            shape, dtype = ctx.like[3]
+            # (one value per row, a dimension less than ys: the cotangents of the row's entries add up)
+            out[4] = (g_extra.sum(-1) if ctx.extra_per_row else g_extra).reshape(shape).to(dtype)
+        return tuple(out)
 
 
 def laplace_posterior_batch(m, ts, ys, lengths=None, family=None, observed=None, offset=None, log_exposure=None,
-                            noise_var=None, init=None, max_iter=50, tol=None):
+                            noise_var=None, init=None, max_iter=50, tol=None, differentiable=False,
+                            allow_unconverged=False):
     """The Laplace approximation of the posterior of B independent series whose observations are counts, binary outcomes
     or Gaussian values: ``LaplacePosterior(mean, cov, log_evidence, iterations, converged)``.
 
@@ -3568,7 +3738,18 @@ def laplace_posterior_batch(m, ts, ys, lengths=None, family=None, observed=None,
     observe nothing take part, so target times go in through ``merge_targets``; a padded dense batch is the mask whose
     tail rows are False.  What ys, log_exposure and noise_var hold at unobserved entries is ignored, NaN included.
     Values of ys are not checked (as those of ``noise_var`` are not elsewhere).  B = 0 returns empty tensors.  Every
-    ValueError is raised before anything is launched.  Inference only: runs under ``torch.no_grad``.
+    ValueError is raised before anything is launched.  By default inference only: runs under ``torch.no_grad``.
+
+    ``differentiable=True`` (the keyword of the filter calls): ``log_evidence`` carries an autograd graph to whichever of
+    ``m.N, m.R, m.B, offset, log_exposure, noise_var, ts`` require grad; everything else in the result stays detached, and
+    the values are those of the default call bit for bit (the loop is the same one).  The gradient is the closed form at
+    the mode (the implicit function theorem, not a graph through the Newton loop): the forward also
+    computes dE / dz (cgps_leg_glm_evidence_rhs), one more solve on the factor of J and the blocks of K^-1; the backward
+    is cgps_leg_glm_evidence_adjoint, the adjoint of the prior blocks and the sums over the series.  Gradients come back
+    in the dtype of their inputs; ``m.Lambda`` takes no part and gets none; there are no second derivatives.  The formula
+    holds at the mode only: a series that has not converged raises ``CgpsError`` naming the first such series, unless
+    ``allow_unconverged=True``, with which such a series keeps its value but is treated as a constant (its cotangent is
+    dropped: it contributes zero to every gradient).
 
     How: Newton's method on the concatenated block-tridiagonal system.  cgps_peg_precision_seg writes
     the prior blocks once; every iteration is one ``cr.decompose_solve`` (the proposal J^-1 r) and one launch of
@@ -3578,13 +3759,17 @@ def laplace_posterior_batch(m, ts, ys, lengths=None, family=None, observed=None,
     not depend on how long its neighbours take.  The loop reads ONE flag on the host per iteration (have all series
     finished?) and stops early when they have; a series that has not converged within ``max_iter`` steps does not raise,
     ``converged`` reports it.  Then one factorisation at the mode, ``cr.inverse_blocks``, and two
-    ``cr.mahal_and_det_batch`` calls for log|J| and log|K| per series.  CGPS_LEG_GLM_COMPOSED=1 composes the step from
-    torch passes instead (A/B timing).
+    ``cr.mahal_and_det_batch`` calls for log|J| and log|K| per series.  CGPS_LEG_GLM_COMPOSED=1 composes the step, and
+    the two gradient entries, from torch passes instead (A/B timing).
 
     One workgroup per series makes this a call for batches: one series of 2^20 rows runs on one workgroup.  Every rank
     1..8, obs_dim <= 8, both precisions.  CPU tensors raise ``CgpsError``: there is no CPU implementation."""
     with torch.no_grad():
-        like = ts
+        like, user_offset, user_extra = ts, offset, (noise_var if noise_var is not None else log_exposure)
+        if differentiable and isinstance(user_extra, torch.Tensor) and isinstance(ys, torch.Tensor):
+            extra_per_row = user_extra.dim() == ys.dim() - 1        # (the caller's ys: [.., obs_dim])
+        else:
+            extra_per_row = False
         fam, ts, ys, lengths, observed, offset, extra, init, dense, bn, tol = _laplace_args(
             m, ts, ys, lengths, family, observed, offset, log_exposure, noise_var, init, max_iter, tol)
         d, dt = m.N.shape[0], m.N.dtype
@@ -3594,22 +3779,34 @@ def laplace_posterior_batch(m, ts, ys, lengths=None, family=None, observed=None,
             mean, cov = ((e(0, n, d), (e(0, n, d, d), e(0, max(n - 1, 0), d, d))) if dense else
                          (e(0, d), (e(0, d, d), e(0, d, d))))
             return LaplacePosterior(mean, cov, e(0, dtype=torch.float64), e(0, dtype=torch.int64), e(0, dtype=torch.bool))
-        mean, Sd, So, ev, iters, conv = _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_iter, tol)
+        saved = {"extra_per_row": extra_per_row} if differentiable else None
+        mean, Sd, So, ev, iters, conv = _laplace_flat(m, fam, ts, ys, lengths, observed, offset, extra, init, max_iter, tol,
+                                                      saved)
         if dense:
             mean, (Sd, So) = _dense_posterior(mean, Sd, So, bn[0], bn[1])
-        return LaplacePosterior(mean, (Sd, So), ev, iters, conv)
+        if not differentiable:
+            return LaplacePosterior(mean, (Sd, So), ev, iters, conv)
+        if not allow_unconverged and not bool(conv.all()):
+            b = int(torch.nonzero(~conv)[0])
+            raise _hip.CgpsError("the Laplace posterior of series %d has not converged after %d steps: the gradient of the "
+                                 "evidence holds at the mode only (raise max_iter, or pass allow_unconverged=True to treat "
+                                 "such a series as a constant)" % (b, int(iters[b])))
+    ev = _LaplaceEvidenceFn.apply(ev, m.G, m.B, user_offset, user_extra, like, saved)
+    return LaplacePosterior(mean, (Sd, So), ev, iters, conv)
 
 
 def laplace_posterior(m, ts, ys, family, observed=None, offset=None, log_exposure=None, noise_var=None, init=None,
-                      max_iter=50, tol=None):
+                      max_iter=50, tol=None, differentiable=False, allow_unconverged=False):
     """``laplace_posterior_batch`` of one series ts[n], ys[n, obs_dim]: ``LaplacePosterior`` with mean [n, d], cov
     ([n, d, d], [n-1, d, d]) and 0-d ``log_evidence``, ``iterations`` and ``converged``.  The series runs on one
-    workgroup: the call is meant for series of moderate length, many of them through the batch form."""
+    workgroup: the call is meant for series of moderate length, many of them through the batch form.
+    ``differentiable`` and ``allow_unconverged``: as there."""
     if not isinstance(ts, torch.Tensor) or not isinstance(ys, torch.Tensor) or ts.dim() != 1 or ys.dim() != 2:
         raise ValueError("one series wants ts[n] and ys[n, obs_dim]")
     if ts.shape[0] < 1:
         raise ValueError("series of length 0")
-    r = laplace_posterior_batch(m, ts, ys, [ts.shape[0]], family, observed, offset, log_exposure, noise_var, init, max_iter, tol)
+    r = laplace_posterior_batch(m, ts, ys, [ts.shape[0]], family, observed, offset, log_exposure, noise_var, init, max_iter, tol,
+                                differentiable, allow_unconverged)
     return LaplacePosterior(r.mean, r.cov, r.log_evidence[0], r.iterations[0], r.converged[0])
 
 
