@@ -1,5 +1,5 @@
-"""ctypes binding of libcgps.so (C ABI: include/cgps.h, and include/cgps_glm.h and include/cgps_glm_grad.h for the
-extension entry points).
+"""ctypes binding of libcgps.so (C ABI: include/cgps.h, and include/cgps_glm.h, include/cgps_glm_grad.h and
+include/cgps_glm_predict.h for the extension entry points).
 
 The library is the product: if it is missing this module raises, it never falls
 back to a CPU or torch implementation.
@@ -98,6 +98,10 @@ _GLM_GRADIENT_SIGNATURES = {
     "cgps_leg_glm_evidence_rhs": (_int, [_vp] * 7 + [_i64] + [_int] * 4 + [_vp] * 2),
     "cgps_leg_glm_evidence_adjoint": (_int, [_vp] * 13 + [_i64] * 2 + [_int] * 4 + [_vp] * 6),
 }
+# The entry point declared in include/cgps_glm_predict.h (predictions on the response scale): a fourth table
+_GLM_PREDICT_SIGNATURES = {
+    "cgps_leg_glm_predict": (_int, [_vp] * 7 + [_i64] + [_int] * 4 + [_vp] * 6),
+}
 GLM_POISSON, GLM_BERNOULLI, GLM_GAUSSIAN = range(3)
 GLM_CONVERGED, GLM_STALLED = 1, 2
 GLM_STATE = 4
@@ -121,6 +125,11 @@ def glm_gradient_symbols():
     return sorted(_GLM_GRADIENT_SIGNATURES)
 
 
+def glm_predict_symbols():
+    """the entry points of include/cgps_glm_predict.h"""
+    return sorted(_GLM_PREDICT_SIGNATURES)
+
+
 def lib():
     """Load libcgps.so once; raise loudly when it is not there."""
     global _lib
@@ -137,7 +146,7 @@ def lib():
             ctypes.CDLL(rt, mode=ctypes.RTLD_GLOBAL)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_EXTENSION_SIGNATURES.items()) + list(
-                _GLM_GRADIENT_SIGNATURES.items()):
+                _GLM_GRADIENT_SIGNATURES.items()) + list(_GLM_PREDICT_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L

@@ -3471,9 +3471,10 @@ def _glm_step(op, z, prop, state):
     return _glm_step_hip(op, z, prop, state)
 
 
-def _laplace_args(m, ts, ys, lengths, family, observed, offset, log_exposure, noise_var, init, max_iter, tol):
+def _laplace_args(m, ts, ys, lengths, family, observed, offset, log_exposure, noise_var, init, max_iter, tol, on_gpu=True):
     """Everything the Laplace calls check, before anything is launched: (family code, ts [R], ys [R, obs], lengths,
-    observed [R, obs] or None, offset [obs] or None, extra [R, obs] or None, init [R, d] or None, dense, (B, n), tol)."""
+    observed [R, obs] or None, offset [obs] or None, extra [R, obs] or None, init [R, d] or None, dense, (B, n), tol).
+    ``on_gpu=False`` leaves the refusal of CPU tensors to a caller that has ValueErrors of its own to raise first."""
     if family not in _FAMILIES:
         raise ValueError("family must be one of %s, got %r" % (sorted(_FAMILIES), family))
     fam = _FAMILIES[family]
@@ -3512,7 +3513,7 @@ def _laplace_args(m, ts, ys, lengths, family, observed, offset, log_exposure, no
     elif not tol >= 0:
         raise ValueError("tol must be >= 0, got %r" % (tol,))
     tensors = [t for t in (m.N, ts, ys, observed, offset, extra, init) if t is not None]
-    if lengths and not all(t.is_cuda for t in tensors):
+    if on_gpu and lengths and not all(t.is_cuda for t in tensors):
         raise _hip.CgpsError("the Laplace posterior runs on GPU tensors only (there is no CPU implementation)")
     return fam, ts, ys, lengths, observed, offset, extra, init, dense, bn, float(tol)
 
@@ -3808,6 +3809,198 @@ def laplace_posterior(m, ts, ys, family, observed=None, offset=None, log_exposur
     r = laplace_posterior_batch(m, ts, ys, [ts.shape[0]], family, observed, offset, log_exposure, noise_var, init, max_iter, tol,
                                 differentiable, allow_unconverged)
     return LaplacePosterior(r.mean, r.cov, r.log_evidence[0], r.iterations[0], r.converged[0])
+
+
+# ---- predictions on the response scale from a latent Gaussian -----------------------------------------
+GlmPredictive = collections.namedtuple("GlmPredictive", ["eta_mean", "eta_var", "mean", "var", "logpdf"])
+
+GLM_PREDICT_NEWTON = 12
+"""Clipped Newton steps from u = 0 to the centre of the quadrature rule (cgps_leg_glm_predict takes the same)."""
+# the positive half of the 32 physicists' Gauss-Hermite nodes x_i, and c_i = log(w_i / sqrt(pi)) + x_i^2: the literals of
+# csrc/cgps_leg_glm_predict.h
+_GH_X = (0.19484074156939933, 0.58497876543593245, 0.97650046358968284, 1.3703764109528718,
+         1.7676541094632016, 2.1694991836061122, 2.5772495377323175, 2.9924908250023742,
+         3.4171674928185707, 3.8537554854714446, 4.3055479533511984, 4.7771645035025964,
+         5.2755509865158801, 5.8122259495159138, 6.4094981492696604, 7.1258139098307276)
+_GH_C = (-1.5145958763594943, -1.5122499826361202, -1.507502504881913, -1.5002376390668201,
+         -1.4902698653576023, -1.4773274278750061, -1.4610256034209449, -1.4408237003057275,
+         -1.4159543626976631, -1.3853025051344199, -1.3471855059889207, -1.298921160459867,
+         -1.2358809264517319, -1.1490650649154518, -1.0171680130339496, -0.76526240024416115)
+
+
+def _glm_predict_hip(family, zm, zc, ys, observed, offset, extra, Bm):
+    """One launch of cgps_leg_glm_predict on zm [P, d], zc [P, d, d] (contiguous, of Bm's dtype): (eta_mean, eta_var, mean,
+    var, logpdf or None), each [P, obs].  ``observed``: bool [P, obs] or None, packed into the pattern bytes here (or the
+    pattern bytes themselves, uint8 [P])."""
+    P_, d = zm.shape
+    obs, dt, dev = Bm.shape[0], zm.dtype, zm.device
+    pattern = None
+    if observed is not None and observed.dtype == torch.uint8:
+        pattern = observed
+    elif observed is not None and ys is not None:
+        pattern = (observed * (1 << torch.arange(obs, device=dev))).sum(1).to(torch.uint8).contiguous()
+    outs = [torch.empty(P_, obs, dtype=dt, device=dev) for _ in range(5 if ys is not None else 4)]
+    if ys is None:
+        outs.append(None)
+    P = _hip.ptr
+    _hip.check(_hip.lib().cgps_leg_glm_predict(
+        P(zm), P(cr._aligned16(zc)), P(ys), P(pattern), P(offset), P(extra), P(Bm), P_, d, obs, _hip.dtype_code(dt), family,
+        *[P(t) for t in outs], _hip.stream_ptr()))
+    return tuple(outs)
+
+
+def _glm_predict_l(family, y, eta):
+    """l(y, eta) without lgamma(y + 1): the arithmetic of ``glm_predict_l`` (csrc/cgps_leg_glm_predict.h)"""
+    if family == _hip.GLM_POISSON:
+        return y * eta - torch.exp(eta)
+    return (y - (eta > 0).to(eta.dtype)) * eta - torch.log1p(torch.exp(-eta.abs()))
+
+
+def _glm_predict_point(family, y, eta):
+    """(l, g, w) at eta: the arithmetic of ``glm_predict_point``"""
+    if family == _hip.GLM_POISSON:
+        e = torch.exp(eta)
+        return y * eta - e, y - e, e
+    e = torch.exp(-eta.abs())
+    r = 1.0 / (1.0 + e)
+    m = e * r
+    up = (eta > 0).to(eta.dtype)
+    return (y - up) * eta - torch.log1p(e), (y - up) + torch.where(eta > 0, m, -m), m * r
+
+
+def _glm_log_integral(family, y, mu, v):
+    """log of the integral of exp(l(y, eta)) N(eta; mu, v) by the rule of ``glm_log_integral``, as fp64 torch passes over
+    arrays of the entries' shape and, for the nodes, that shape x 16 (Poisson without its -lgamma(y + 1))"""
+    sv = v.sqrt()
+    cap = 1.0 / sv
+    u = torch.zeros_like(mu)
+    for _ in range(GLM_PREDICT_NEWTON):
+        _, g, w = _glm_predict_point(family, y, mu + sv * u)
+        step = (sv * g - u) / (1.0 + v * w)
+        u = u + torch.where(step > cap, cap, step)
+    l, _, w = _glm_predict_point(family, y, mu + sv * u)
+    s = 1.0 / (1.0 + v * w).sqrt()
+    x = torch.tensor(_GH_X, dtype=mu.dtype, device=mu.device)
+    c = torch.tensor(_GH_C, dtype=mu.dtype, device=mu.device)
+    e = lambda t: t.unsqueeze(-1)                                    # noqa: E731
+    dl = math.sqrt(2.0) * e(s) * x
+    lp = _glm_predict_l(family, e(y), e(mu) + e(sv) * (e(u) + dl))
+    lm = _glm_predict_l(family, e(y), e(mu) + e(sv) * (e(u) - dl))
+    total = (torch.exp(c + (lp - e(l)) - dl * (e(u) + 0.5 * dl)) + torch.exp(c + (lm - e(l)) + dl * (e(u) - 0.5 * dl))).sum(-1)
+    return torch.log(s) + (l - 0.5 * u * u) + torch.log(total)
+
+
+def _glm_predict_composed(family, zm, zc, ys, observed, offset, extra, Bm):
+    """cgps_leg_glm_predict as torch passes (CGPS_LEG_GLM_COMPOSED=1): mu and v in the arrays' dtype, the moments and the
+    rule in fp64, as the kernel takes them.  For A/B timing, the yardstick of the kernel's fp32 error, and -- it accepts
+    CPU tensors -- the test of the rule without a GPU."""
+    F64, dt = torch.float64, zm.dtype
+    mu = zm @ Bm.T
+    if offset is not None:
+        mu = mu + offset
+    if family != _hip.GLM_GAUSSIAN and extra is not None:
+        mu = mu + extra
+    vT = (torch.einsum("pab,cb->pca", zc, Bm) * Bm).sum(-1)
+    vT = torch.where(vT < 0, torch.zeros_like(vT), vT)
+    mu64, v = mu.to(F64), vT.to(F64)
+    given = None
+    if ys is not None:
+        given = torch.ones_like(mu, dtype=torch.bool) if observed is None else observed
+        y = torch.where(given, ys.to(F64), torch.zeros_like(mu64))
+    lp = None
+    if family == _hip.GLM_GAUSSIAN:
+        tot = v + extra.to(F64)
+        mean, var = mu64, tot
+        if ys is not None:
+            res = y - mu64
+            lp = -0.5 * res * res / tot - 0.5 * torch.log(2 * math.pi * tot)
+    elif family == _hip.GLM_POISSON:
+        mean = torch.exp(mu64 + 0.5 * v)
+        var = mean + mean * mean * torch.expm1(v)
+        if ys is not None:
+            lp = _glm_log_integral(family, y, mu64, v) - torch.lgamma(y + 1.0)
+    else:
+        L1 = _glm_log_integral(family, torch.ones_like(mu64), mu64, v)
+        L0 = _glm_log_integral(family, torch.zeros_like(mu64), mu64, v)
+        mean, var = torch.exp(L1), torch.exp(L1 + L0)
+        if ys is not None:
+            lp = torch.where(y == 1, L1, L0)
+            other = (y != 1) & (y != 0)                              # (values of ys are not checked: the rule at y itself)
+            if bool(other.any()):
+                lp = torch.where(other, _glm_log_integral(family, y, mu64, v), lp)
+    if lp is not None:
+        lp = torch.where(given, lp, torch.zeros_like(lp)).to(dt)
+    return mu.contiguous(), vT.contiguous(), mean.to(dt), var.to(dt), lp
+
+
+def _glm_predict(family, zm, zc, ys, observed, offset, extra, Bm):
+    fn = _glm_predict_composed if _glm_composed() else _glm_predict_hip
+    return fn(family, zm, zc, ys, observed, offset, extra, Bm)
+
+
+def _glm_predict_family(family, log_exposure, noise_var, what=""):
+    """the family's code; raises the ValueErrors about which of log_exposure / noise_var belongs to which family
+    (``what``: the prefix of the argument names in the caller's signature)"""
+    if family not in _FAMILIES:
+        raise ValueError("family must be one of %s, got %r" % (sorted(_FAMILIES), family))
+    fam = _FAMILIES[family]
+    if fam == _hip.GLM_GAUSSIAN and noise_var is None:
+        raise ValueError("family 'gaussian' needs %snoise_var, the variance of every predicted entry" % what)
+    if fam != _hip.GLM_GAUSSIAN and noise_var is not None:
+        raise ValueError("%snoise_var belongs to family 'gaussian', got family %r" % (what, family))
+    if fam == _hip.GLM_GAUSSIAN and log_exposure is not None:
+        raise ValueError("%slog_exposure belongs to the families 'poisson' and 'bernoulli'" % what)
+    return fam
+
+
+def glm_predictive(m, z_mean, z_cov, family, offset=None, log_exposure=None, noise_var=None, ys=None, observed=None):
+    """What a latent Gaussian says about an observation of the families of ``laplace_posterior_batch``:
+    ``GlmPredictive(eta_mean, eta_var, mean, var, logpdf)``, each [..., obs_dim].
+
+    ``z_mean`` [..., d] and ``z_cov`` [..., d, d] of any leading shape: the latent at target times
+    (``predict.laplace_predictions_batch`` does that in one call), or ``LaplacePosterior.mean`` and ``cov[0]`` for
+    in-sample posterior predictive checks.  Per entry the linear predictor eta = B[c, :] z + offset[c] + log_exposure is
+    N(eta_mean, eta_var); ``mean`` and ``var`` are the moments of y on the response scale (a Poisson rate, a Bernoulli
+    probability; Gaussian: eta_mean and eta_var + noise_var), and ``logpdf`` = log of the integral of p(ys | eta) over that
+    Gaussian -- the log predictive density of held-out data -- or None without ``ys``.  ``observed`` (bool, like ys): the
+    entries of ys that exist; elsewhere logpdf is exact zero and ys is ignored, NaN included.  ``log_exposure`` /
+    ``noise_var`` ([..., obs_dim]) are used at EVERY entry.  ``offset`` [obs_dim].
+
+    Gaussian in closed form; Poisson mean and variance in closed form; the Poisson logpdf and everything Bernoulli by
+    adaptive Gauss-Hermite quadrature with 32 nodes in fp64 (cgps_leg_glm_predict, a lane per entry; DESIGN.md 4.28 for
+    its accuracy: within the fp64 test bound up to eta_var = 2, about 2e-5 relative at eta_var = 4).  Inference only, GPU
+    tensors only; CGPS_LEG_GLM_COMPOSED=1 composes it from torch passes instead.  Every ValueError is raised before
+    anything is launched."""
+    fam = _glm_predict_family(family, log_exposure, noise_var)
+    obs, d = m.B.shape
+    dt = m.B.dtype
+    if not 1 <= d <= 8 or obs > MAX_PATTERN_OBS or dt not in (torch.float32, torch.float64):
+        raise ValueError("glm_predictive is built for rank 1..8, obs_dim <= %d, float32 / float64" % MAX_PATTERN_OBS)
+    if not isinstance(z_mean, torch.Tensor) or not isinstance(z_cov, torch.Tensor) or not z_mean.dtype.is_floating_point:
+        raise ValueError("z_mean and z_cov must be floating-point tensors")
+    lead = tuple(z_mean.shape[:-1])
+    if z_mean.dim() < 1 or z_mean.shape[-1] != d or tuple(z_cov.shape) != lead + (d, d):
+        raise ValueError("z_mean must be [..., %d] and z_cov [..., %d, %d], got %s and %s"
+                         % (d, d, d, tuple(z_mean.shape), tuple(z_cov.shape)))
+    extra = noise_var if fam == _hip.GLM_GAUSSIAN else log_exposure
+    if observed is not None and ys is None:
+        raise ValueError("observed says which entries of ys exist: it needs ys")
+    for name, t, ok in (("ys", ys, lambda q: q.is_floating_point), ("observed", observed, lambda q: q == torch.bool),
+                        ("noise_var" if fam == _hip.GLM_GAUSSIAN else "log_exposure", extra, lambda q: q.is_floating_point)):
+        if t is not None and (not isinstance(t, torch.Tensor) or not ok(t.dtype) or tuple(t.shape) != lead + (obs,)):
+            raise ValueError("%s must be a %s tensor %s" % (name, "bool" if name == "observed" else "floating-point", lead + (obs,)))
+    if offset is not None and (not isinstance(offset, torch.Tensor) or not offset.dtype.is_floating_point or
+                               tuple(offset.shape) != (obs,)):
+        raise ValueError("offset must be a floating-point tensor [%d]" % obs)
+    tensors = [t for t in (m.B, z_mean, z_cov, ys, observed, offset, extra) if t is not None]
+    if not _glm_composed() and not all(t.is_cuda for t in tensors):
+        raise _hip.CgpsError("glm_predictive runs on GPU tensors only (there is no CPU implementation)")
+    with torch.no_grad():
+        c = lambda t, shape: None if t is None else t.to(dt).reshape(shape).contiguous()      # noqa: E731
+        out = _glm_predict(fam, c(z_mean, (-1, d)), c(z_cov, (-1, d, d)), c(ys, (-1, obs)),
+                           None if observed is None else observed.reshape(-1, obs), c(offset, (obs,)), c(extra, (-1, obs)),
+                           c(m.B, (obs, d)))
+        return GlmPredictive(*[None if t is None else t.reshape(lead + (obs,)) for t in out])
 
 
 # ---- the config-5 workload -----------------------------------------------------------------

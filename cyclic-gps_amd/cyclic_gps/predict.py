@@ -24,6 +24,7 @@ The in-sample posterior itself (``decompose`` / ``solve`` / ``inverse_blocks``) 
 (``leg.insample_posterior``).  Pinned by ``tests/golden/leg_*.npz`` (``pp_mean``, ``pp_cov``,
 ``pred_mean``, ``pred_cov`` recorded from the reference's own ``make_predictions``).
 """
+import collections
 import os
 
 import torch
@@ -328,6 +329,135 @@ def make_predictions_batch(m, ts, xs, target_ts, lengths=None, target_lengths=No
     with torch.no_grad():
         pm, pv = predictive_posterior_batch(m, ts, xs, target_ts, lengths, target_lengths, observed, noise_var, check_sorted)
         return pm @ m.B.T, m.B @ pv @ m.B.T
+
+
+# ---- counts and binary outcomes: predictions from the Laplace posterior -------------------------------
+GlmPredictions = collections.namedtuple("GlmPredictions", ["z_mean", "z_cov", "eta_mean", "eta_var", "mean", "var", "logpdf",
+                                                           "converged"])
+_TARGET_SPECS = {
+    "target_ys": ("target_ys", "a floating-point tensor", lambda dtype: dtype.is_floating_point),
+    "target_observed": ("target_observed", "a bool tensor", lambda dtype: dtype == torch.bool),
+    "target_log_exposure": ("target_log_exposure", "a floating-point tensor", lambda dtype: dtype.is_floating_point),
+    "target_noise_var": ("target_noise_var", "a floating-point tensor", lambda dtype: dtype.is_floating_point),
+}
+
+
+def _flat_posterior(posterior, dense, bn, R, d):
+    """(mean [R, d], Sd [R, d, d], So [R - 1, d, d], converged [B]) of a ``LaplacePosterior`` in the layout of the call
+    (the blocks of So between two series of a dense batch are zeros: nothing reads them); ValueError when its shapes are
+    not those of the data."""
+    try:
+        mean, (Sd, So), conv = posterior.mean, posterior.cov, posterior.converged
+    except (AttributeError, TypeError, ValueError):
+        raise ValueError("posterior must be a LaplacePosterior, what leg.laplace_posterior_batch returns for the same data")
+    B = bn[0] if dense else None
+    want = ((B, bn[1], d), (B, bn[1], d, d), (B, bn[1] - 1, d, d)) if dense else ((R, d), (R, d, d), (max(R - 1, 0), d, d))
+    got = tuple(tuple(t.shape) if isinstance(t, torch.Tensor) else None for t in (mean, Sd, So))
+    if got != want:
+        raise ValueError("posterior is not of this data: mean and cov of shapes %s, the data wants %s" % (got, want))
+    if dense:
+        So = torch.cat([So, So.new_zeros(B, 1, d, d)], 1).reshape(R, d, d)[:R - 1]
+    return mean.reshape(R, d), Sd.reshape(R, d, d), So, conv
+
+
+def laplace_predictions_batch(m, ts, ys, target_ts, lengths=None, target_lengths=None, family=None, observed=None,
+                              offset=None, log_exposure=None, noise_var=None, target_log_exposure=None,
+                              target_noise_var=None, target_ys=None, target_observed=None, posterior=None, init=None,
+                              max_iter=50, tol=None, check_sorted=True):
+    """Predictions at new times for B independent series of counts, binary outcomes or Gaussian values, from the Laplace
+    posterior of ``leg.laplace_posterior_batch``: ``GlmPredictions(z_mean, z_cov, eta_mean, eta_var, mean, var, logpdf,
+    converged)``.  Inference only, GPU tensors only.
+
+    The data arguments (ts, ys, lengths, family, observed, offset, log_exposure, noise_var, init, max_iter, tol) are
+    those of ``leg.laplace_posterior_batch``; targets, ``target_lengths`` and ``check_sorted`` those of
+    ``predictive_posterior_batch`` (dense target_ts [B, p] or [p], ragged [P] with host ``target_lengths``; a series may
+    have no target).  ``target_log_exposure`` / ``target_noise_var`` (the latter required by ``family="gaussian"``),
+    ``target_ys`` (held-out values) and ``target_observed`` (which of them exist) are in the layout of the targets:
+    [B, p, obs_dim] dense, [P, obs_dim] ragged.
+
+    ``z_mean`` [.., d] and ``z_cov`` [.., d, d] are the latent Gaussian at every target; ``eta_mean``, ``eta_var``, ``mean``,
+    ``var`` and ``logpdf`` [.., obs_dim] what ``leg.glm_predictive`` says of it (``logpdf`` is None without ``target_ys``);
+    ``converged`` [B] is the Newton loop's report: a series that has not converged within ``max_iter`` steps still
+    predicts, from the point the loop left it at.
+
+    How: the Newton loop of ``leg.laplace_posterior_batch`` -- unless ``posterior=`` hands in the ``LaplacePosterior`` of
+    the same data, in which case no Newton step runs --, then ONE launch of cgps_leg_intercast_seg (a lane per target,
+    never across a series boundary) and ONE of cgps_leg_glm_predict (a lane per target and channel).  Every ValueError is
+    raised before anything is launched."""
+    with torch.no_grad():
+        fam_t = leg._glm_predict_family(family, target_log_exposure, target_noise_var, "target_")
+        for name, t in (("target_ys", target_ys), ("target_observed", target_observed)):
+            if t is not None and not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a tensor" % name)
+        if target_observed is not None and target_ys is None:
+            raise ValueError("target_observed says which entries of target_ys exist: it needs target_ys")
+        fam, ts_f, ys_f, lens, observed, offset, extra, init, dense, bn, tol = leg._laplace_args(
+            m, ts, ys, lengths, family, observed, offset, log_exposure, noise_var, init, max_iter, tol, on_gpu=False)
+        tt, tlens, bp = _batch_targets(target_ts, target_lengths, lens, dense)
+        obs, d = m.B.shape
+        dt, dev = m.N.dtype, ts_f.device
+        P, R = sum(tlens), sum(lens)
+        like = (bp + (obs,)) if dense else (P, obs)
+        flat = {}
+        for name, t in (("target_ys", target_ys), ("target_observed", target_observed),
+                        ("target_log_exposure", target_log_exposure), ("target_noise_var", target_noise_var)):
+            if t is not None:
+                t = leg._batch_like_xs(t, _TARGET_SPECS[name], like, dense)
+                flat[name] = t.unsqueeze(-1).expand(-1, obs) if t.dim() == 1 else t
+        if posterior is not None:
+            post = _flat_posterior(posterior, dense, bn, R, d)
+        tensors = [t for t in (m.N, ts_f, ys_f, observed, offset, extra, init, tt) if t is not None] + list(flat.values())
+        if posterior is not None:
+            tensors += list(post)
+        if lens and not all(t.is_cuda for t in tensors):
+            raise leg._hip.CgpsError("the Laplace predictions run on GPU tensors only (there is no CPU implementation)")
+        shape = bp if dense else (P,)
+        e = lambda *tail, dtype=dt: torch.empty(shape + tail, dtype=dtype, device=dev)      # noqa: E731
+        if not lens:
+            return GlmPredictions(e(d), e(d, d), e(obs), e(obs), e(obs), e(obs), None if target_ys is None else e(obs),
+                                  torch.empty(0, dtype=torch.bool, device=dev))
+        tt = tt.to(ts_f.dtype)
+        tplan = leg._cached_batch_plan(tlens, dev, make=_TargetPlan)
+        if check_sorted and P > 1:
+            assert bool(((tt[1:] - tt[:-1] > 0) | tplan.across).all())         # reference :471, per series
+        if posterior is None:
+            mean, Sd, So, _, _, conv = leg._laplace_flat(m, fam, ts_f, ys_f, lens, observed, offset, extra, init, max_iter, tol)
+        else:
+            mean, Sd, So, conv = post
+        if P == 0:
+            return GlmPredictions(e(d), e(d, d), e(obs), e(obs), e(obs), e(obs), None if target_ys is None else e(obs), conv)
+        plan = leg._cached_batch_plan(lens, dev)
+        zm, zc = _intercast_models_hip(m.G, mean, Sd, So, ts_f, plan, tt, tplan)
+        c = lambda t: None if t is None else t.to(dt).contiguous()             # noqa: E731
+        t_extra = flat.get("target_noise_var") if fam_t == leg._hip.GLM_GAUSSIAN else flat.get("target_log_exposure")
+        t_obs = flat.get("target_observed")
+        out = leg._glm_predict(fam_t, zm, zc, c(flat.get("target_ys")), None if t_obs is None else t_obs.contiguous(),
+                               c(offset), c(t_extra), c(m.B))
+        r = lambda t, *tail: None if t is None else t.reshape(shape + tail)      # noqa: E731
+        return GlmPredictions(r(zm, d), r(zc, d, d), *[r(t, obs) for t in out], conv)
+
+
+def laplace_predictions(m, ts, ys, target_ts, family, observed=None, offset=None, log_exposure=None, noise_var=None,
+                        target_log_exposure=None, target_noise_var=None, target_ys=None, target_observed=None,
+                        posterior=None, init=None, max_iter=50, tol=None, check_sorted=True):
+    """``laplace_predictions_batch`` of one series ts[n], ys[n, obs_dim] at target_ts[p]: ``GlmPredictions`` with z_mean
+    [p, d], z_cov [p, d, d], the rest [p, obs_dim] and a 0-d ``converged``; the ``target_*`` arguments [p, obs_dim];
+    ``posterior``: what ``leg.laplace_posterior`` returned for the same series."""
+    if not isinstance(ts, torch.Tensor) or not isinstance(ys, torch.Tensor) or ts.dim() != 1 or ys.dim() != 2:
+        raise ValueError("one series wants ts[n] and ys[n, obs_dim]")
+    if ts.shape[0] < 1:
+        raise ValueError("series of length 0")
+    if not isinstance(target_ts, torch.Tensor) or target_ts.dim() != 1:
+        raise ValueError("one series wants target_ts[p]")
+    if posterior is not None:
+        try:
+            posterior = leg.LaplacePosterior(posterior.mean, posterior.cov, None, None, posterior.converged.reshape(1))
+        except (AttributeError, TypeError):
+            raise ValueError("posterior must be a LaplacePosterior, what leg.laplace_posterior returns for the same series")
+    r = laplace_predictions_batch(m, ts, ys, target_ts, [ts.shape[0]], [target_ts.shape[0]], family, observed, offset,
+                                  log_exposure, noise_var, target_log_exposure, target_noise_var, target_ys, target_observed,
+                                  posterior, init, max_iter, tol, check_sorted)
+    return r._replace(converged=r.converged[0])
 
 
 # ---- many models over one batch --------------------------------------------------------------------------------
